@@ -8,13 +8,21 @@ operator API (GaussianRasterizer -> autograd -> C ABI -> gfx950 kernels) on one
 synthetic frame whose inputs are already resident in HBM.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload metric|C2|C5|tiny]
+                  [--dump-outputs DIR] [--full]
 
 N > 1 is launched by the driver as `python -m torch.distributed.run ... bench.py
 --gpus N ...`: one rank per GPU, each rank renders its own frame (frames are
 independent units: weak scaling, no data-path collective).  Rank 0 prints ONE JSON
-line.  Also in the line: `roofline` for the dominant kernel (HIP events on the
-launch stream, algorithmic bytes of SURVEY.md 8(d)) and `cpu_baseline` (the CPU
-oracle timed on this box's host cores; rank 0, N = 1 only).
+line.
+
+A plain run sets up, spins the device up, runs W warm-up and K timed steps and prints
+the headline figure (`value`, `ms_per_step` = the mean of the K timed steps).
+`--dump-outputs DIR` writes what the last timed step handed to its caller (outputs and
+gradients; a fixed, seeded sample of the large ones) as DIR/<name>.npy.  `--full` adds
+everything else the line used to carry: the median leg, `roofline` for the dominant
+kernel (HIP events on the launch stream, algorithmic bytes of SURVEY.md 8(d)), the
+measurements beside the headline (`extras`) and `cpu_baseline` (the CPU oracle timed on
+this box's host cores; rank 0, N = 1 only).
 """
 import argparse
 import json
@@ -220,9 +228,11 @@ def gpu_step_fn(scene, dev):
     leaf = {k: t(v).requires_grad_(True) for k, v in g.items() if v is not None}
     means2D = torch.zeros((cfg["P"], 3), device=dev, requires_grad=True)
     gr = {k: t(v) for k, v in scene["grads"].items()}
-    state = {}
+    # keep_outputs (--dump-outputs): the step's 11 outputs stay in state["outs"] until the next step starts
+    state = {"means2D": means2D, "keep_outputs": False}
 
     def step():
+        state.pop("outs", None)
         for v in leaf.values():
             v.grad = None
         means2D.grad = None
@@ -233,6 +243,8 @@ def gpu_step_fn(scene, dev):
                             phase_offset=scene["phase_offset"], dc_offset=scene["dc_offset"])
             state["radii"] = outs[10]
             state["pixels"] = outs[8]
+            if state["keep_outputs"]:
+                state["outs"] = outs
             return
         outs = rast(means3D=leaf["means3D"], means2D=means2D, opacities=leaf["opacities"], shs=leaf["shs"],
                     shs_p=leaf.get("shs_p"), scales=leaf["scales"], rotations=leaf["rotations"],
@@ -243,8 +255,52 @@ def gpu_step_fn(scene, dev):
                                 [gr["color"], gr["phasor"], gr["depth"], gr["acc"], gr["depth_distortion"]])
         state["radii"] = outs[10]
         state["pixels"] = outs[8]
+        if state["keep_outputs"]:
+            state["outs"] = outs
 
     return step, state, leaf
+
+
+# the rasterizer's 11-tuple (api.native_forward)
+RASTER_OUTPUTS = ("color", "phasor", "depth", "normal", "acc", "entropy", "depth_distortion", "amp_distortion", "pixels",
+                  "distribution", "radii")
+
+
+def step_outputs(state, leaf):
+    """(name, tensor) pairs of what a caller of the timed step holds after its last call: the rasterizer's outputs and the
+    gradients the backward left on the inputs (none for a forward-only workload); for the composed C4 step also the
+    deformation network's gradients after the exchange."""
+    if "frame_step" in state:
+        fs = state["frame_step"]
+        outs, ssp = fs.last
+        arrays = list(zip(RASTER_OUTPUTS, outs)) + [("grad_means2D", ssp.grad)]
+        arrays += [("grad_net." + n, p.grad) for n, p in fs.net.named_parameters()]
+    else:
+        arrays = list(zip(RASTER_OUTPUTS, state["outs"])) + [("grad_means2D", state["means2D"].grad)]
+    return arrays + [("grad_" + k, v.grad) for k, v in leaf.items()]
+
+
+def dump_outputs(out_dir, arrays, budget_bytes=60 << 20):
+    """Writes every tensor of `arrays` as out_dir/<name>.npy (float64 stays float64, everything else becomes float32),
+    at most `budget_bytes` in all.  The smallest arrays go first, each whole if it fits its share of what is left; a
+    larger one is written as a fixed sample of its flattened elements (sorted indices drawn from a generator seeded by the
+    name), so two runs with the same arguments write the same elements."""
+    import zlib
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(((n, t.detach()) for n, t in arrays if t is not None), key=lambda a: a[1].numel())
+    left = budget_bytes
+    for i, (name, t) in enumerate(items):
+        dtype = torch.float64 if t.dtype == torch.float64 else torch.float32
+        cap = left // (len(items) - i) // (8 if dtype == torch.float64 else 4)
+        if t.numel() > cap:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            idx = np.unique(rng.integers(0, t.numel(), size=cap))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.to(dtype).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def c4_step_fn(scene, dev, dist, rank, world):
@@ -1316,16 +1372,53 @@ def main_cpu_rehearsal(args, env, world):
         dist.destroy_process_group()
 
 
+def headline_line(args, world, dist, scene, state, elapsed, composed):
+    """The fields of the result line that a plain run prints: the headline figure of the K timed steps and the frame it
+    rendered (`--full` adds its legs' figures to this dict)."""
+    from gftorf_amd import api
+    cfg = scene["cfg"]
+    P, W, H = cfg["P"], cfg["W"], cfg["H"]
+    value = world * args.steps / elapsed
+    out = {
+        "metric": "train iters/sec (fwd+bwd raster) + Mpix/s, 1M Gaussians @ 640x480 ToF",
+        "value": value, "unit": "it/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        # ranks of the process group the timed region's barriers ran on (backend nccl = RCCL; gloo in a rehearsal)
+        "rccl_ranks": dist.get_world_size() if (dist is not None and dist.get_backend() == "nccl") else (1 if dist is None else 0),
+        "process_group": ("%s x%d" % (dist.get_backend(), dist.get_world_size())) if dist is not None else "none",
+        "config": {"workload": scene["label"], "P": P, "W": W, "H": H, "sh_degree": cfg["D"],
+                   "P_visible": int((state["radii"] > 0).sum().item()), "num_rendered": int(api.last_call_stats["num_rendered"]),
+                   "longest_tile_list": int(api.last_call_stats["max_tile_list"]), "frames_per_step": world,
+                   "parallelism": ("frame-sharded x%d (no collective in the raster path; one all-reduce of the deform-network "
+                                   "gradient bucket per step, inside the timed step: deform_exchange)" % world) if composed else
+                                  ("frame-sharded x%d (no collective in the raster path; the deform-gradient all-reduce is "
+                                   "measured in deform_exchange)" % world)},
+        "mpix_per_s": value * W * H / 1e6,
+    }
+    if composed:
+        out["metric"] = ("composed frame steps/sec: network query + input assembly + raster fwd+bwd + network backward + "
+                         "gradient all-reduce, 1M Gaussians (30 % dynamic) @ 640x480 ToF, one frame per rank")
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default 100, SURVEY 8(d); 7000 iterations for --workload C3)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="metric", choices=list(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all: a fixed, seeded sample of the large arrays)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the median leg, the per-stage roofline leg, the composed step's phases, the "
+                         "deform exchange (N > 1), the measurements beside the headline and the CPU baseline; a plain run "
+                         "only times the K steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
-    ap.add_argument("--no-extras", action="store_true", help="skip the measurements beside the headline step")
-    ap.add_argument("--extras", default="all", help="comma list of extras to run (render_pair, varying_views, c3_loop, assemble_inputs, knn, "
+    ap.add_argument("--no-extras", action="store_true", help="--full without the measurements beside the headline step")
+    ap.add_argument("--extras", default="all", help="--full: comma list of extras to run (render_pair, varying_views, c3_loop, assemble_inputs, knn, "
                                                     "adam, deform_network, densify, train_iteration) or `all`")
     ap.add_argument("--spin-up", type=float, default=0.3, help="seconds of untimed steps before the warm-up")
     ap.add_argument("--torch-loss", action="store_true", help="--workload C3: the loss's SSIM and L2 terms as stock torch (eight "
@@ -1374,7 +1467,8 @@ def main():
             raise SystemExit("process group has %d ranks, --gpus %d" % (dist.get_world_size(), args.gpus))
 
     from gftorf_amd import api
-    api.keep_last_buffers = True          # the walked-entries figure of path_roofline is read from the last forward's scratch
+    if args.full:
+        api.keep_last_buffers = True      # the walked-entries figure of path_roofline is read from the last forward's scratch
     if args.workload == "C3":
         return main_loop(args, env, world, dev, dist)
     scene = build_scene(args.workload, env["rank"], world)
@@ -1395,9 +1489,10 @@ def main():
             except Exception as e:
                 print("bench.py: single-rank RCCL group unavailable (%s: %s): the step runs without its exchange"
                       % (type(e).__name__, e), file=sys.stderr)
-        step, state, _ = c4_step_fn(scene, dev, dist, env["rank"], world)
+        step, state, leaf = c4_step_fn(scene, dev, dist, env["rank"], world)
     else:
-        step, state, _ = gpu_step_fn(scene, dev)
+        step, state, leaf = gpu_step_fn(scene, dev)
+        state["keep_outputs"] = bool(args.dump_outputs)
     sync = torch.cuda.synchronize
 
     # Device spin-up before the W warm-up steps: the power management raises the clocks over the first
@@ -1428,6 +1523,17 @@ def main():
     sync()
 
     elapsed = timed_steps(step, args.steps, args.warmup, sync, dist)
+    if args.dump_outputs and env["rank"] == 0:
+        dump_outputs(args.dump_outputs, step_outputs(state, leaf))
+    state["keep_outputs"] = False
+    state.pop("outs", None)
+    if not args.full:
+        if env["rank"] == 0:
+            print(json.dumps(headline_line(args, world, dist, scene, state, elapsed, composed)), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- median leg ("median of 100"): the same K steps once more with one event per step on the launch stream;
     # `ms_per_step` stays the mean of the timed region above, `ms_per_step_median` is the median of these device-side step times
@@ -1572,22 +1678,9 @@ def main():
                 "resident_waves_per_simd": cnt.get("mean_resident_waves_per_simd") if cnt else None,
                 "issue_slot_frac": cnt.get("valu_issue_slot_frac") if cnt else None,
                 "source": cnt["source"] if cnt else None}
-        out = {
-            "metric": "train iters/sec (fwd+bwd raster) + Mpix/s, 1M Gaussians @ 640x480 ToF",
-            "value": value, "unit": "it/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "ms_per_step_median": median_ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            # ranks of the process group the timed region's barriers ran on (backend nccl = RCCL; gloo in a rehearsal)
-            "rccl_ranks": dist.get_world_size() if (dist is not None and dist.get_backend() == "nccl") else (1 if dist is None else 0),
-            "process_group": ("%s x%d" % (dist.get_backend(), dist.get_world_size())) if dist is not None else "none",
-            "config": {"workload": scene["label"], "P": P, "W": W, "H": H, "sh_degree": cfg["D"],
-                       "P_visible": P_vis, "num_rendered": R,
-                       "longest_tile_list": int(api.last_call_stats["max_tile_list"]), "frames_per_step": world,
-                       "parallelism": ("frame-sharded x%d (no collective in the raster path; one all-reduce of the deform-network "
-                                       "gradient bucket per step, inside the timed step: deform_exchange)" % world) if composed else
-                                      ("frame-sharded x%d (no collective in the raster path; the deform-gradient all-reduce is "
-                                       "measured in deform_exchange)" % world)},
-            "mpix_per_s": value * N / 1e6,
+        out = headline_line(args, world, dist, scene, state, elapsed, composed)
+        out["ms_per_step_median"] = median_ms
+        out.update({
             "roofline": roofline,
             # whole step: per-unit bytes of SURVEY 8(d) x units processed (P_app, R_bin, R_walk, P_blend, see
             # algorithmic_bytes) / step time; `reference_formula_*`: 8(d) as written for the reference algorithm.
@@ -1616,7 +1709,7 @@ def main():
             "tile_pull_binning": {k: walked[k] for k in ("tile_pull", "supertile_entries", "head_ids", "flagged_quadrants",
                                                          "completed_list_ids", "gaussians_with_appearance")} if walked else None,
             "stage_ms": stage_ms,
-        }
+        })
         if per_rank_stage_ms is not None:
             out["per_rank_stage_ms"] = per_rank_stage_ms
         if exchange is not None:
@@ -1631,8 +1724,6 @@ def main():
             # `roofline` describes it; the rasterizer's own dominant kernel moves to `raster_roofline`
             out["raster_roofline"] = out["roofline"]
             out["roofline"] = dict(composed_step["dominant"], traffic=None)
-            out["metric"] = ("composed frame steps/sec: network query + input assembly + raster fwd+bwd + network backward + "
-                             "gradient all-reduce, 1M Gaussians (30 % dynamic) @ 640x480 ToF, one frame per rank")
         # (the measurements beside the headline belong to the metric workload; named explicitly they run on any workload's
         # scene, e.g. `--workload C5 --extras varying_views`)
         if world == 1 and not args.no_extras and (args.workload == "metric" or args.extras != "all"):
@@ -1699,31 +1790,27 @@ def main_loop(args, env, world, dev, dist):
         holder["step"] = step_fn
         return timed_steps(step_fn, n, args.warmup, sync, dist)
     elapsed, rep, info = bench_loop.run(dev, args.steps, sync, region, pair=args.pair, graph=args.graph, fused_loss=not args.torch_loss)
-    # roofline leg: per-stage HIP events of the rasterizer calls over 200 more iterations
-    _lib.profile_reset()
-    _lib.profile_enable(True)
-    n_prof = 200
-    for _ in range(n_prof):
-        holder["step"]()
-    sync()
-    prof = _lib.profile_read()
-    _lib.profile_enable(False)
+    if args.dump_outputs and env["rank"] == 0:
+        # what the loop hands its caller: the optimised parameters after the last timed iteration, and the loss trace
+        arrays = [("param_" + k, v) for k, v in info["par"].items()] + [("net." + n, p) for n, p in info["net"].named_parameters()]
+        dump_outputs(args.dump_outputs, arrays + [("loss_trace", torch.tensor(rep["loss_trace"], dtype=torch.float64))])
+    if args.full:
+        # roofline leg: per-stage HIP events of the rasterizer calls over 200 more iterations
+        _lib.profile_reset()
+        _lib.profile_enable(True)
+        n_prof = 200
+        for _ in range(n_prof):
+            holder["step"]()
+        sync()
+        prof = _lib.profile_read()
+        _lib.profile_enable(False)
     if env["rank"] == 0:
         cfg = bench_loop.C3
         P, W, H = cfg["P"], cfg["W"], cfg["H"]
         N, T = W * H, ((W + 15) // 16) * ((H + 15) // 16)
         R = int(api.last_call_stats["num_rendered"])
-        walked = walked_instances(dev)
-        fwd_calls, bwd_calls = max(prof["forward_calls"], 1), max(prof["backward_calls"], 1)
-        # two forwards and one backward per iteration: per-call stage times
-        stage_ms = {k[:-3]: prof[k] / (bwd_calls if k in ("render_bwd_ms", "preprocess_bwd_ms", "memset_ms") else fwd_calls)
-                    for k in prof if k.endswith("_ms")}
-        raster_ms_per_it = sum(prof[k] for k in prof if k.endswith("_ms")) / n_prof
-        dom = max(stage_ms, key=lambda k: stage_ms[k])
-        per_kernel, whole = algorithmic_bytes(P, P, R, N, T, units={"R_walk": walked["per_tile_deepest"]} if walked else None)
         ms = elapsed / args.steps * 1e3
         value = world * args.steps / elapsed
-        achieved = per_kernel[dom] / (stage_ms[dom] * 1e-3) / 1e9 if stage_ms[dom] > 0 else 0.0
         out = {
             "metric": "train iters/sec (fwd+bwd raster) + Mpix/s, 1M Gaussians @ 640x480 ToF",
             "value": value, "unit": "it/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
@@ -1739,15 +1826,27 @@ def main_loop(args, env, world, dev, dist):
                        "parallelism": "replicas x%d" % world},
             "mpix_per_s": value * 2 * N / 1e6,
             "loop": rep,
-            "raster_ms_per_iteration": raster_ms_per_it, "raster_share_of_iteration": raster_ms_per_it / ms,
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": None, "algorithmic_bytes_per_launch": per_kernel[dom],
-                         "avg_launch_ms": stage_ms[dom],
-                         "note": "at 100k Gaussians / 320x240 a rasterizer call is ~0.1 ms of kernels: the iteration is bound by "
-                                 "launch latency and the host, not by HBM (raster_share_of_iteration)"},
-            "stage_ms": stage_ms,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            walked = walked_instances(dev)
+            fwd_calls, bwd_calls = max(prof["forward_calls"], 1), max(prof["backward_calls"], 1)
+            # two forwards and one backward per iteration: per-call stage times
+            stage_ms = {k[:-3]: prof[k] / (bwd_calls if k in ("render_bwd_ms", "preprocess_bwd_ms", "memset_ms") else fwd_calls)
+                        for k in prof if k.endswith("_ms")}
+            raster_ms_per_it = sum(prof[k] for k in prof if k.endswith("_ms")) / n_prof
+            dom = max(stage_ms, key=lambda k: stage_ms[k])
+            per_kernel, whole = algorithmic_bytes(P, P, R, N, T, units={"R_walk": walked["per_tile_deepest"]} if walked else None)
+            achieved = per_kernel[dom] / (stage_ms[dom] * 1e-3) / 1e9 if stage_ms[dom] > 0 else 0.0
+            out.update({
+                "raster_ms_per_iteration": raster_ms_per_it, "raster_share_of_iteration": raster_ms_per_it / ms,
+                "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, "traffic": None, "algorithmic_bytes_per_launch": per_kernel[dom],
+                             "avg_launch_ms": stage_ms[dom],
+                             "note": "at 100k Gaussians / 320x240 a rasterizer call is ~0.1 ms of kernels: the iteration is bound by "
+                                     "launch latency and the host, not by HBM (raster_share_of_iteration)"},
+                "stage_ms": stage_ms,
+            })
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # CPU beside it: the oracle's rasterizer forward+backward on one C3-shaped ToF frame (the rest of the loop is
             # host-side torch in the reference as well)
             from gftorf_amd import synth

@@ -122,7 +122,7 @@ def test_bench_c4_runs_with_two_ranks(tmp_path):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-                        "--workload", "C4", "--no-cpu-baseline", "--spin-up", "0.05"],
+                        "--workload", "C4", "--full", "--no-cpu-baseline", "--spin-up", "0.05"],
                        env=env, capture_output=True, text=True, timeout=420, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
