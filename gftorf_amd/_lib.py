@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgftorf_rast.so")
-ABI_VERSION = 14
+ABI_VERSION = 15
 DEFORM_MAX_INPUTS = 96          # GFT_DEFORM_MAX_INPUTS (include/gftorf_deform.h)
 ACC_STRIDE = 16
 
@@ -48,6 +48,7 @@ BACKWARD_FIELDS = [
     "geom", "img", "binning", "acc",
     "dL_dmeans3D", "dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dcov3D", "dL_dsh", "dL_dsh_p",
     "dL_dscales", "dL_drotations", "dL_dphase_offset", "dL_ddc_offset", "det_partials", "dirty_rows", "rows_report",
+    "phase_offset_dev", "dc_offset_dev",
 ]
 
 LAYOUT_FIELDS = [
@@ -64,7 +65,7 @@ PROFILE_FIELDS = ["preprocess_fwd_ms", "tile_count_ms", "tile_scatter_ms", "tile
 
 class ForwardIO(C.Structure):
     _fields_ = [(n, _fp) for n in FORWARD_FIELDS] + [("grads_zero", _fp), ("grads_zero_bytes", C.c_size_t), ("tile_hints", _fp), ("tile_weights", _fp),
-                                                           ("cell_sched", _fp)]
+                                                           ("cell_sched", _fp), ("phase_offset_dev", _fp), ("dc_offset_dev", _fp)]
 
 
 class BackwardIO(C.Structure):

@@ -408,6 +408,23 @@ def _scalar(x):
     return float(x)
 
 
+def _offset_arg(x, dev):
+    """(scalar, tensor) of a phase / DC offset.  A float32 tensor of one element on the rasterizer's device -- the
+    reference's learnable ``_phase_offset`` / ``_dc_offset`` (gaussian_model.py:225-226) -- goes to the kernels by address
+    (``gft_*_io.phase_offset_dev`` / ``dc_offset_dev``): they read it when they run, so the host never waits for it and a
+    captured call follows the values an optimiser writes between replays.  Anything else (a float, a CPU tensor, another
+    dtype) is read on the host and goes by value, as before: (value, None)."""
+    if not isinstance(x, torch.Tensor):
+        return float(x), None
+    if x.dtype == torch.float32 and x.numel() == 1 and x.device == dev:
+        return 0.0, x             # (the config's scalar is ignored where the address is given)
+    return _scalar(x), None
+
+
+def _offsets_dev(ph_dev, dc_dev):
+    return None if ph_dev is None and dc_dev is None else (ph_dev, dc_dev)
+
+
 def _bg_strides(bg, H, W, dev):
     """Background as [7,H,W] element strides.  The reference reads
     bg[c*H*W + pix] for c < 7 on every call (forward.cu:644,649) after
@@ -526,10 +543,12 @@ def _p0(t):
 
 def native_forward(s, means3D, sh, sh_p, colors_precomp, phasors_precomp, opacities, scales, rotations,
                    cov3Ds_precomp, ph_off, dc_off, want_bw, with_acc, stream=None, hint_slot=0, share_grads=None,
-                   pre_launch=None, acc_any_stream=False, nowait=None):
+                   pre_launch=None, acc_any_stream=False, nowait=None, off_dev=None):
     """One forward of the native rasterizer (``RasterizeGaussiansCUDA``, rasterize_points.cu:42-165): allocates the
     outputs and the three scratch buffers, runs the C ABI on torch's current stream.  ``s`` holds the settings fields
     (``GaussianRasterizationSettings`` or ``_Settings``), ``ph_off`` / ``dc_off`` are floats.  Returns a dict.
+    ``off_dev`` = (phase, dc) offsets as one-element float32 tensors on the device, either may be None (:func:`_offset_arg`):
+    the kernels of this forward and of its backward read those instead of the floats.
 
     For :mod:`gftorf_amd.pair`: ``stream`` = raw hipStream_t to launch on instead of torch's current stream (the caller
     orders it against the current stream), ``hint_slot`` keeps the buffer-size hints of the two cameras of a pair apart,
@@ -604,7 +623,8 @@ def native_forward(s, means3D, sh, sh_p, colors_precomp, phasors_precomp, opacit
                       _p0(rot_c), _p0(cov_c), view_c.data_ptr(), proj_c.data_ptr(), campos_c.data_ptr(), _p0(sh_c), _p0(sh_p_c),
                       geom.data_ptr(), img.data_ptr(), 0,
                       pl, pl + 3 * hw4, pl + 10 * hw4, pl + 11 * hw4, pl + 14 * hw4, pl + 15 * hw4, pl + 16 * hw4, pl + 17 * hw4,
-                      pixels.data_ptr() if P else 0, pl + 18 * hw4, radii.data_ptr() if P else 0, 0, 0, 0, 0, 0, 0)
+                      pixels.data_ptr() if P else 0, pl + 18 * hw4, radii.data_ptr() if P else 0, 0, 0, 0, 0, 0, 0,
+                      *((0, 0) if off_dev is None else (_p0(off_dev[0]), _p0(off_dev[1]))))
     # the backward's accumulator: cleared by the forward beside its binning kernels -- unless it comes from the pool of
     # buffers that the last backward left zero (_AccLease)
     lease = None
@@ -621,7 +641,7 @@ def native_forward(s, means3D, sh, sh_p, colors_precomp, phasors_precomp, opacit
                                 (bg_c, bsc, bsy, bsx), (view_c, proj_c, campos_c), ph_off, dc_off, acc_buf,
                                 colors_c is not None, cov_c is not None, want_bw, pixels,
                                 share_grads=share_grads, acc_lease=lease,
-                                pooled=not capturing)
+                                pooled=not capturing, off_dev=off_dev)
         if prep["zero_buf"] is not None:
             io.grads_zero = prep["zero_buf"].data_ptr()
             io.grads_zero_bytes = prep["zero_buf"].numel() * 4
@@ -794,7 +814,7 @@ def native_forward(s, means3D, sh, sh_p, colors_precomp, phasors_precomp, opacit
 
 def prepare_backward(s, means3D, opac, sh, sh_p, scales, rotations, cov3D, radii, geom, img, bg, consts, ph_off, dc_off,
                      acc, want_colors, want_cov, want_bw_records=True, pixels=None, zero_fill=False, share_grads=None,
-                     acc_lease=None, pooled=True):
+                     acc_lease=None, pooled=True, off_dev=None):
     """Everything of a backward that does not depend on the upstream gradients: the gradient tensors, the argument
     block, the config.  The forward calls it BEFORE it queues its kernels, so that this host work overlaps the device's
     previous work instead of sitting between the forward's last kernel and the backward's first one."""
@@ -959,7 +979,8 @@ def prepare_backward(s, means3D, opac, sh, sh_p, scales, rotations, cov3D, radii
                       geom.data_ptr(), img.data_ptr(), 0, acc.data_ptr() if P else 0,
                       g["means3D"].data_ptr() if P else 0, g["means2D"].data_ptr() if P else 0, _p0(g["colors"]),
                       g["opacities"].data_ptr() if P else 0, _p0(g["cov3D"]), _p0(g["sh"]), _p0(g["sh_p"]), _p0(g["scales"]),
-                      _p0(g["rotations"]), off_ptr, off_ptr + 4 if off_ptr else 0, 0, dirty_ptr, report_ptr)
+                      _p0(g["rotations"]), off_ptr, off_ptr + 4 if off_ptr else 0, 0, dirty_ptr, report_ptr,
+                      *((0, 0) if off_dev is None else (_p0(off_dev[0]), _p0(off_dev[1]))))
     last_call_stats["grads_reused"] = bool(reused_grads)
     last_call_stats["grads_rows_only"] = bool(rows_only)
     return dict(grads=g, cfg=cfg, io=io, acc=acc, acc_lease=acc_lease, pixels=pixels, zero_buf=zero_buf, dev=dev, P=P, H=H, W=W,
@@ -1028,10 +1049,10 @@ def run_backward(prep, grads_out, geom, binning, img, debug=False):
 
 
 def native_backward(s, means3D, opac, sh, sh_p, scales, rotations, cov3D, radii, geom, binning, img, bg, consts,
-                    ph_off, dc_off, grads_out, acc, want_colors, want_cov, want_bw_records=True):
+                    ph_off, dc_off, grads_out, acc, want_colors, want_cov, want_bw_records=True, off_dev=None):
     """One backward of the native rasterizer: :func:`prepare_backward` + :func:`run_backward` in one go."""
     prep = prepare_backward(s, means3D, opac, sh, sh_p, scales, rotations, cov3D, radii, geom, img, bg, consts, ph_off,
-                            dc_off, acc, want_colors, want_cov, want_bw_records)
+                            dc_off, acc, want_colors, want_cov, want_bw_records, off_dev=off_dev)
     return run_backward(prep, grads_out, geom, binning, img, bool(s.debug))
 
 
@@ -1040,12 +1061,12 @@ class _RasterizeGaussians(torch.autograd.Function):
     def forward(ctx, means3D, means2D, sh, sh_p, colors_precomp, phasors_precomp, opacities,
                 scales, rotations, cov3Ds_precomp, phase_offset, dc_offset, raster_settings):
         s = raster_settings
-        ph_off = _scalar(phase_offset)
-        dc_off = _scalar(dc_offset)
+        ph_off, ph_dev = _offset_arg(phase_offset, means3D.device)
+        dc_off, dc_dev = _offset_arg(dc_offset, means3D.device)
         # the backward can only run if autograd tracks one of the inputs
         want_bw = any(ctx.needs_input_grad)
         r = native_forward(s, means3D, sh, sh_p, colors_precomp, phasors_precomp, opacities, scales, rotations,
-                           cov3Ds_precomp, ph_off, dc_off, want_bw, True)
+                           cov3Ds_precomp, ph_off, dc_off, want_bw, True, off_dev=_offsets_dev(ph_dev, dc_dev))
         means3D_c, opac_c, sh_c, sh_p_c, scales_c, rot_c, cov_c, colors_c, phasors_c = r["inputs"]
         ctx.raster_settings = s
         ctx.num_rendered = r["R"]
@@ -1063,12 +1084,16 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         dummy = means3D_c.new_empty(0)
         radii = r["outputs"][10]
+        # (offsets the kernels read by address are saved too, behind the others -- only when there are any: host time)
+        offs = () if ph_dev is None and dc_dev is None else (ph_dev if ph_dev is not None else dummy,
+                                                             dc_dev if dc_dev is not None else dummy)
+        ctx.off_dev = (ph_dev is not None, dc_dev is not None)
         ctx.save_for_backward(means3D_c, opac_c if opac_c is not None else dummy,
                               sh_c if sh_c is not None else dummy, sh_p_c if sh_p_c is not None else dummy,
                               scales_c if scales_c is not None else dummy, rot_c if rot_c is not None else dummy,
                               cov_c if cov_c is not None else dummy, radii, r["geom"], r["binning"], r["img"],
-                              r["outputs"][8])     # `pixels`: the backward reads it (which Gaussians were blended), so an
-                                                   # in-place edit between forward and backward must raise, not zero rows
+                              r["outputs"][8],     # `pixels`: the backward reads it (which Gaussians were blended), so an
+                              *offs)               # in-place edit between forward and backward must raise, not zero rows
         ctx.mark_non_differentiable(radii)
         return r["outputs"]
 
@@ -1076,7 +1101,9 @@ class _RasterizeGaussians(torch.autograd.Function):
     def backward(ctx, grad_out_color, grad_out_phasor, grad_out_depth, grad_out_normal, grad_out_acc,
                  grad_entropy, grad_depth_distortion, grad_amp_distortion, grad_pixels, grad_distribution, _):
         s = ctx.raster_settings
-        means3D, opac, sh, sh_p, scales, rotations, cov3D, radii, geom, binning, img, _pixels = ctx.saved_tensors
+        saved = ctx.saved_tensors
+        means3D, opac, sh, sh_p, scales, rotations, cov3D, radii, geom, binning, img, _pixels = saved[:12]
+        ph_dev, dc_dev = saved[12:] if len(saved) > 12 else (None, None)
         has_sh, has_sh_p, has_colors, has_phasors, has_scales, has_cov = ctx.present
         ph_off, dc_off = ctx.scalars
         acc, ctx.acc = ctx.acc, None
@@ -1088,7 +1115,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             g = native_backward(s, means3D, opac, sh if has_sh else None, sh_p if has_sh_p else None,
                                 scales if has_scales else None, rotations if has_scales else None,
                                 cov3D if has_cov else None, radii, geom, binning, img, ctx.bg, ctx.consts, ph_off, dc_off,
-                                grads_out, None, has_colors, has_cov, ctx.want_bw)
+                                grads_out, None, has_colors, has_cov, ctx.want_bw,
+                                off_dev=_offsets_dev(ph_dev if ctx.off_dev[0] else None, dc_dev if ctx.off_dev[1] else None))
         op_shape, ph_shape, dc_shape = ctx.in_shapes
         grad_phase = grad_dc = None
         if s.optimize_phase_offset and ph_shape is not None:

@@ -253,9 +253,10 @@ __device__ __forceinline__ void lds_row_load(float* v, const float4* row)
 // on its (R, I, Am) basis, the direction gradients for the backward and the clamp flags -> rec_b, dirgrad, clamped.
 // Called by k_preprocess_fwd for the Gaussians of the near slab (all of them without a depth cut) and by
 // k_appearance_far for the others when a quadrant asks for the far slab: most far Gaussians are never blended, and
-// their 320 bytes of SH coefficients are then never read.
+// their 320 bytes of SH coefficients are then never read.  `phase_offset`: the call's phase offset, read by the kernel
+// at its entry (gft_offset_value).
 __device__ __forceinline__ void appearance_fwd(const PreFwdArgs& a, int idx, int lane, const float4* sh_l, const float4* shp_l,
-                           float px, float py, float pz, float vx, float vy, float vz)
+                           float px, float py, float pz, float vx, float vy, float vz, float phase_offset)
 {
     const float3 cam = make_float3(a.io.campos[0], a.io.campos[1], a.io.campos[2]);
     const float dox = px - cam.x, doy = py - cam.y, doz = pz - cam.z;
@@ -356,7 +357,7 @@ __device__ __forceinline__ void appearance_fwd(const PreFwdArgs& a, int idx, int
         }
         phase_sh = res[0];
         amplitude = res[1];
-        phase = dist * a.dist2phase + a.c.phase_offset;
+        phase = dist * a.dist2phase + phase_offset;
         if (a.c.use_view_dependent_phase) phase += phase_sh;
         have_phasor = true;
     }

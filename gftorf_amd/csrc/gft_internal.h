@@ -221,6 +221,14 @@ hipError_t gft_launch_mark_visible(hipStream_t s, int32_t P, const float* means3
 #define GFT_DPP_ROW_BCAST15 0x142
 #define GFT_DPP_ROW_BCAST31 0x143
 
+// ToF phase / DC offset of a call (ABI 15): the caller's device word when it gives one (gft_*_io.phase_offset_dev /
+// dc_offset_dev), else the gft_config scalar.  Called at kernel entry, in front of every store of the kernel: the address
+// is uniform and nothing has written memory yet, so this is one scalar load per wave, not a load per lane.
+__device__ __forceinline__ float gft_offset_value(const float* dev, float scalar)
+{
+    return dev != nullptr ? *dev : scalar;
+}
+
 // Sum over the 64 lanes of a wave; the total is valid in lane 63.
 __device__ __forceinline__ float gft_wave_sum_to_lane63(float v)
 {

@@ -12,6 +12,7 @@ struct RenderFwdArgs {
     const float* __restrict__ bg;
     int64_t bsc, bsy, bsx;
     float dc_offset;
+    const float* dc_offset_dev;          // the caller's device word (gft_forward_io.dc_offset_dev; NULL: dc_offset): read at kernel entry
     float4* __restrict__ pix_state;
     float4* __restrict__ pix_sums;
     uint32_t* __restrict__ quad_max;
@@ -115,7 +116,8 @@ __device__ __forceinline__ bool stage_splat(uint32_t id, int slot, const float4*
 // between).  Both translation units compile it with the same contraction setting (k_pull.hip includes this header in
 // front of the one that switches contraction off) and without the SLP vectoriser: the same arithmetic, bit for bit.
 // `sA`, `sB`: RB * 2 float4 of LDS each, this wave's own.
-__device__ __forceinline__ void render_fwd_walk(const RenderFwdArgs& a, const int v, const int lane, float4* sA, float4* sB)
+__device__ __forceinline__ void render_fwd_walk(const RenderFwdArgs& a, const int v, const int lane, float4* sA, float4* sB,
+                                                float dc_offset /* resolved at kernel entry: gft_offset_value */)
 {
     auto wave_sync = [] { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); };
     const int tile = v >> 2, quad = v & 3;
@@ -308,7 +310,7 @@ __device__ __forceinline__ void render_fwd_walk(const RenderFwdArgs& a, const in
         a.out_color[2 * HW + pix] = C2 + T * g2;
         // phasor planes share background planes 0..6, weighted by T (not T^2)
         // planes 3..6 = (+-cos + dc, +-sin + dc) A/d^2 blended = +-PR + dc PA, +-PI + dc PA
-        const float dcA = a.dc_offset * PA;
+        const float dcA = dc_offset * PA;
         a.out_phasor[pix] = PR + T * g0;
         a.out_phasor[HW + pix] = PI + T * g1;
         a.out_phasor[2 * HW + pix] = PA + T * g2;

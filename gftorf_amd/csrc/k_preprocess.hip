@@ -254,6 +254,7 @@ __device__ __forceinline__ void dnorm_dv(float vx, float vy, float vz, const flo
 
 __global__ __launch_bounds__(PRE_BLOCK) void k_preprocess_fwd(PreFwdArgs a)
 {
+    const float phase_offset = gft_offset_value(a.io.phase_offset_dev, a.c.phase_offset);
     extern __shared__ float4 lds_rows[];
     const int idx = blockIdx.x * PRE_BLOCK + threadIdx.x;
     const int P = a.c.P;
@@ -288,7 +289,7 @@ __global__ __launch_bounds__(PRE_BLOCK) void k_preprocess_fwd(PreFwdArgs a)
                     store_rec_a(a, idx, sg, vx, vy, vz);
                     // Tile-pull binning: the appearance (320 B of SH coefficients read, 161 B written) follows in k_appearance
                     // for the Gaussians that come to stand in the sorted part of a tile list -- in a dense frame most never do.
-                    if (!a.defer_appearance) appearance_fwd(a, idx, lane, sh_l, shp_l, px, py, pz, vx, vy, vz);
+                    if (!a.defer_appearance) appearance_fwd(a, idx, lane, sh_l, shp_l, px, py, pz, vx, vy, vz, phase_offset);
                     radius = (int)sg.my_radius;
                     tiles = area;
                     rect = make_ushort4((unsigned short)x0, (unsigned short)y0, (unsigned short)x1, (unsigned short)y1);
@@ -323,6 +324,7 @@ __global__ __launch_bounds__(APP_THREADS) void k_appearance(PreFwdArgs a, uint32
     __shared__ uint32_t s_ids[APP_CHUNK];
     __shared__ uint32_t s_n;
     if (a.ctrl[GFT_CTRL_TOTAL] > cap) return;
+    const float phase_offset = gft_offset_value(a.io.phase_offset_dev, a.c.phase_offset);
     const int tid = threadIdx.x, lane = tid & 63;
     // Workgroup 0, on the side: the heavy-first order in which the forward blend deals its quadrant waves, from the walk
     // lengths the previous frame of this camera left with the caller (any contents give a permutation of the tiles; no
@@ -375,7 +377,7 @@ __global__ __launch_bounds__(APP_THREADS) void k_appearance(PreFwdArgs a, uint32
         const float vz = V.m[2] * px + V.m[6] * py + V.m[10] * pz + V.m[14];
         const float vx = V.m[0] * px + V.m[4] * py + V.m[8] * pz + V.m[12];
         const float vy = V.m[1] * px + V.m[5] * py + V.m[9] * pz + V.m[13];
-        appearance_fwd(a, idx, lane, nullptr, nullptr, px, py, pz, vx, vy, vz);
+        appearance_fwd(a, idx, lane, nullptr, nullptr, px, py, pz, vx, vy, vz, phase_offset);
     }
 }
 
@@ -814,8 +816,15 @@ __device__ __forceinline__ void preprocess_bwd_body(PreBwdArgs a, int row_idx = 
     }
 }
 
-__global__ __launch_bounds__(PRE_BLOCK) void k_preprocess_bwd(PreBwdArgs a) { preprocess_bwd_body<false>(a); }
-__global__ __launch_bounds__(PRE_BLOCK) void k_preprocess_bwd_common(PreBwdArgs a) { preprocess_bwd_body<true>(a); }
+// The two offsets at kernel entry (gft_offset_value): the phasor chain of preprocess_bwd_body reads them from `a.c`.
+__device__ __forceinline__ void resolve_offsets(PreBwdArgs& a)
+{
+    a.c.phase_offset = gft_offset_value(a.io.phase_offset_dev, a.c.phase_offset);
+    a.c.dc_offset = gft_offset_value(a.io.dc_offset_dev, a.c.dc_offset);
+}
+
+__global__ __launch_bounds__(PRE_BLOCK) void k_preprocess_bwd(PreBwdArgs a) { resolve_offsets(a); preprocess_bwd_body<false>(a); }
+__global__ __launch_bounds__(PRE_BLOCK) void k_preprocess_bwd_common(PreBwdArgs a) { resolve_offsets(a); preprocess_bwd_body<true>(a); }
 
 // The backward over the rows of blended Gaussians only (cfg.grads_zeroed = 2: the caller's gradient tensors are zero but
 // for what this call writes).  A dense frame blends a fraction of its Gaussians (metric frame: 66 k of 1 M) and they are
@@ -848,6 +857,7 @@ __global__ __launch_bounds__(ROWS_THREADS) void k_preprocess_bwd_rows(PreBwdArgs
     // ~66 blended rows -- one wave of four had work, and the ~1000 workgroups needed two rounds at two waves per SIMD
     // (measured, 1 M / 5 M Gaussians: 1024 per workgroup 28 / 79 us, 2048: 26 / 51, 4096: 32.5 / 41).
     constexpr int ROWS_CHUNK = ROWS_CHUNK_OF(ROWS_SUBS);
+    resolve_offsets(a);
     __shared__ uint32_t s_ids[ROWS_CHUNK];
     __shared__ uint32_t s_stale[ROWS_CHUNK];
     __shared__ uint32_t s_wt[ROWS_THREADS / 64];

@@ -964,7 +964,7 @@ struct TailArgs {
     int dbg;
 };
 
-__device__ __forceinline__ void tail_appearance(const TailArgs& a, uint32_t id)
+__device__ __forceinline__ void tail_appearance(const TailArgs& a, uint32_t id, float phase_offset)
 {
     // 1 = it has its appearance from k_appearance.  3 = some tile's tail builder is giving (or has given) it one in THIS launch:
     // that does not help the tile at hand -- its resumed walk reads the records a moment from now and cannot wait for another
@@ -977,7 +977,7 @@ __device__ __forceinline__ void tail_appearance(const TailArgs& a, uint32_t id)
     const float vz = V.m[2] * px + V.m[6] * py + V.m[10] * pz + V.m[14];
     const float vx = V.m[0] * px + V.m[4] * py + V.m[8] * pz + V.m[12];
     const float vy = V.m[1] * px + V.m[5] * py + V.m[9] * pz + V.m[13];
-    appearance_fwd(a.pre, (int)id, threadIdx.x & 63, nullptr, nullptr, px, py, pz, vx, vy, vz);
+    appearance_fwd(a.pre, (int)id, threadIdx.x & 63, nullptr, nullptr, px, py, pz, vx, vy, vz, phase_offset);
 }
 
 __global__ __launch_bounds__(TAIL_THREADS) void k_tail_build(TailArgs a)
@@ -988,6 +988,9 @@ __global__ __launch_bounds__(TAIL_THREADS) void k_tail_build(TailArgs a)
     __shared__ uint32_t s_m, s_pool, s_hi, s_chunk;
     __shared__ unsigned long long s_nearest;
     if (a.ctrl[GFT_CTRL_TOTAL] > a.cap) return;
+    // (the two offsets in front of the first store: scalar loads, gft_offset_value)
+    const float phase_offset = gft_offset_value(a.pre.io.phase_offset_dev, a.pre.c.phase_offset);
+    const float dc_offset = gft_offset_value(a.render.dc_offset_dev, a.render.dc_offset);
     const uint32_t nflag = a.ctrl[GFT_CTRL_NFLAG];
     const int T = a.sh.T;
     // The backward's heavy-first tile order rides on this launch (no separate launch in the backward): by the deepest
@@ -1093,7 +1096,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void k_tail_build(TailArgs a)
         // sorts the n keys in LDS (n <= TAIL_LDS_KEYS), gives their Gaussians an appearance, writes the ids
         auto finish_lds = [&](uint32_t n, uint32_t* dst) {
             __syncthreads();
-            if (PHASE_DBG(a) != 3) for (uint32_t i = tid; i < n; i += TAIL_THREADS) tail_appearance(a, (uint32_t)sk[sort_slot(i)]);
+            if (PHASE_DBG(a) != 3) for (uint32_t i = tid; i < n; i += TAIL_THREADS) tail_appearance(a, (uint32_t)sk[sort_slot(i)], phase_offset);
             if (PHASE_DBG(a) == 4) return;
             if (n <= 1024u) {
                 // a short tail (the usual case: a few hundred survivors): runs of 256 keys are sorted by one wave each in
@@ -1169,7 +1172,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void k_tail_build(TailArgs a)
                     scan(2, lo, hi, dst);
                     __threadfence_block();
                     __syncthreads();
-                    for (uint32_t i = tid; i < c; i += TAIL_THREADS) tail_appearance(a, dst[i]);
+                    for (uint32_t i = tid; i < c; i += TAIL_THREADS) tail_appearance(a, dst[i], phase_offset);
                     auto ld = [&](uint32_t i) {
                         const uint32_t id = __hip_atomic_load(&dst[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                         return ((uint64_t)__float_as_uint(a.pre.g.depth[id]) << 32) | id;
@@ -1194,7 +1197,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void k_tail_build(TailArgs a)
             const uint32_t fl = w == 0 ? f.x : w == 1 ? f.y : w == 2 ? f.z : f.w;
             if (w < 4 && fl != 0u) {
                 float4* stage = reinterpret_cast<float4*>(sk_dyn) + (size_t)w * (RB * 4);
-                render_fwd_walk(a.render, 4 * tile + w, lane, stage, stage + RB * 2);
+                render_fwd_walk(a.render, 4 * tile + w, lane, stage, stage + RB * 2, dc_offset);
             }
         }
     }

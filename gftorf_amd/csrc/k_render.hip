@@ -43,6 +43,7 @@ __global__ __launch_bounds__(64) void k_render_fwd(RenderFwdArgs a)
     __shared__ float4 sA[RB * 2];
     __shared__ float4 sB[RB * 2];
 
+    const float dc_offset = gft_offset_value(a.dc_offset_dev, a.dc_offset);
     // binning buffer smaller than the instance count: nothing was binned, the host re-runs stage 2
     if (a.ctrl && a.ctrl[GFT_CTRL_TOTAL] > a.cap) return;
     if (a.resume && *a.nflag == 0u) return;               // no quadrant asked for its tail
@@ -60,7 +61,7 @@ __global__ __launch_bounds__(64) void k_render_fwd(RenderFwdArgs a)
         v = unit_of_block(blockIdx.x, V);
     }
     if (v >= V) return;
-    render_fwd_walk(a, v, (int)threadIdx.x, sA, sB);
+    render_fwd_walk(a, v, (int)threadIdx.x, sA, sB, dc_offset);
 }
 
 // ---------------------------------------------------------------------------
@@ -96,6 +97,7 @@ __global__ __launch_bounds__(64 * FSEG_WAVES) __attribute__((amdgpu_waves_per_eu
     __shared__ float sT[FSEG_WAVES][64];                 // transmittance factor of every segment, per pixel
     __shared__ uint8_t sCnt[FSEG_WAVES][FSEG_SPEC_MAX];  // speculative pass: pixels that blended every entry of the segment
 
+    const float dc_offset = gft_offset_value(a.dc_offset_dev, a.dc_offset);
     if (a.ctrl && a.ctrl[GFT_CTRL_TOTAL] > a.cap) return;
     const int V = a.T * 4;
     const int v = unit_of_block(blockIdx.x, V);
@@ -491,7 +493,7 @@ __global__ __launch_bounds__(64 * FSEG_WAVES) __attribute__((amdgpu_waves_per_eu
         a.out_color[pix] = C0 + T * g0;
         a.out_color[HW + pix] = C1 + T * g1;
         a.out_color[2 * HW + pix] = C2 + T * g2;
-        const float dcA = a.dc_offset * PA;
+        const float dcA = dc_offset * PA;
         a.out_phasor[pix] = PR + T * g0;
         a.out_phasor[HW + pix] = PI + T * g1;
         a.out_phasor[2 * HW + pix] = PA + T * g2;
@@ -529,6 +531,7 @@ struct RenderBwdArgs {
     const float* __restrict__ bg;
     int64_t bsc, bsy, bsx;
     float dc_offset;
+    const float* dc_offset_dev;          // gft_backward_io.dc_offset_dev (NULL: dc_offset): read at kernel entry
     const float4* __restrict__ pix_state;
     const float4* __restrict__ pix_sums;
     int split;                 // 1: deep quadrants are shared by several waves
@@ -654,6 +657,7 @@ __global__ __launch_bounds__(64) void k_render_bwd(RenderBwdArgs a)
     // (a forward that was queued without a host read and did not fit its buffer has left no lists: nothing to walk -- its
     // caller learns of it from the status block, gft_forward_enqueue)
     if (a.ctrl[GFT_CTRL_TOTAL] > a.cap) return;
+    const float dc_offset = gft_offset_value(a.dc_offset_dev, a.dc_offset);
     const int per_seg = (int)gridDim.x / a.nseg;
     const int sgroup = (int)blockIdx.x / per_seg;          // launch group: the workgroups of group 0 start first
     const int bid = (int)blockIdx.x - sgroup * per_seg;
@@ -735,7 +739,7 @@ __global__ __launch_bounds__(64) void k_render_bwd(RenderBwdArgs a)
     // upstream phasor gradients folded onto the per-splat basis (R, I, Am):
     // sum_k p_k g_k = R*GR + I*GI + Am*GA; K9 needs sum w_p*{GR, GI, g2, GQ}
     const float GR = gp0 + gp3 - gp4, GI = gp1 + gp5 - gp6, GQ = (gp3 + gp4) + (gp5 + gp6);
-    const float GA = gp2 + a.dc_offset * GQ;
+    const float GA = gp2 + dc_offset * GQ;
     // per-pixel factors of the eight sums that are (pixel constant) x (w_c or w_p), as register pairs
     const v2f gA01 = {gc0, gc1}, gA23 = {gc2, gd}, gB01 = {GR, GI}, gB23 = {gp2, GQ};
 
@@ -952,7 +956,7 @@ RenderFwdArgs gft_render_fwd_args(const gft_config& c, const gft_forward_io& io,
     a.T = a.gx * gy;
     a.ranges = im.ranges; a.point_list = b.point_list; a.rec_a = g.rec_a; a.rec_b = g.rec_b;
     a.bg = io.bg; a.bsc = c.bg_stride_c; a.bsy = c.bg_stride_y; a.bsx = c.bg_stride_x;
-    a.dc_offset = c.dc_offset;
+    a.dc_offset = c.dc_offset; a.dc_offset_dev = io.dc_offset_dev;
     a.pix_state = im.pix_state; a.quad_max = im.tile_max;
     a.pix_sums = im.pix_sums;
     a.out_color = io.out_color; a.out_phasor = io.out_phasor; a.out_depth = io.out_depth;
@@ -1008,7 +1012,7 @@ hipError_t gft_launch_render_bwd(hipStream_t s, const gft_config& c, const gft_b
     a.T = a.gx * gy;
     a.ranges = im.ranges; a.point_list = b.point_list; a.rec_a = g.rec_a; a.rec_b = g.rec_b;
     a.bg = io.bg; a.bsc = c.bg_stride_c; a.bsy = c.bg_stride_y; a.bsx = c.bg_stride_x;
-    a.dc_offset = c.dc_offset;
+    a.dc_offset = c.dc_offset; a.dc_offset_dev = io.dc_offset_dev;
     a.pix_state = im.pix_state; a.quad_max = im.tile_max;
     a.g_color = io.dL_dout_color; a.g_phasor = io.dL_dout_phasor; a.g_depth = io.dL_dout_depth;
     a.g_acc = io.dL_dout_acc; a.g_dd = io.dL_dout_depth_distortion;

@@ -19,7 +19,7 @@ calls (``gaussian_renderer/__init__.py:29-34``).
 import torch
 import torch.nn as nn
 
-from .api import (_scalar, native_forward, native_backward, run_backward)
+from .api import (_offset_arg, _offsets_dev, native_forward, native_backward, run_backward)
 
 _side_streams = {}
 
@@ -39,9 +39,13 @@ class _RasterizePair(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, sh_p, colors_precomp, phasors_precomp, opacities, scales, rotations,
                 cov3Ds_precomp, phase_offset_a, dc_offset_a, phase_offset_b, dc_offset_b, settings_a, settings_b):
-        offs = [(_scalar(phase_offset_a), _scalar(dc_offset_a)), (_scalar(phase_offset_b), _scalar(dc_offset_b))]
-        want_bw = any(ctx.needs_input_grad)
         dev = means3D.device
+        # (per view: the floats, and the one-element device tensors the kernels read by address -- api._offset_arg)
+        args = [(_offset_arg(phase_offset_a, dev), _offset_arg(dc_offset_a, dev)),
+                (_offset_arg(phase_offset_b, dev), _offset_arg(dc_offset_b, dev))]
+        offs = [(ph[0], dc[0]) for ph, dc in args]
+        devs = [(ph[1], dc[1]) for ph, dc in args]
+        want_bw = any(ctx.needs_input_grad)
         overlap = dev.type == "cuda" and means3D.size(0) > 0
         if overlap:
             main = torch.cuda.current_stream(dev)
@@ -55,14 +59,15 @@ class _RasterizePair(torch.autograd.Function):
                 ev.record(main)
                 side.wait_event(ev)
         ra = native_forward(settings_a, means3D, sh, sh_p, colors_precomp, phasors_precomp, opacities, scales, rotations,
-                            cov3Ds_precomp, offs[0][0], offs[0][1], want_bw, True, hint_slot=1)
+                            cov3Ds_precomp, offs[0][0], offs[0][1], want_bw, True, hint_slot=1, off_dev=_offsets_dev(*devs[0]))
         # (B's buffers come from the current stream's pool like A's: it is joined below before anything is returned,
         # and A's call frees nothing that B could be handed while A's kernels still use it)
         rb = native_forward(settings_b, means3D, sh, sh_p, colors_precomp, phasors_precomp, opacities, scales, rotations,
                             cov3Ds_precomp, offs[1][0], offs[1][1], want_bw, True,
                             stream=side.cuda_stream if overlap else None, hint_slot=2, share_grads=ra["prep"],
                             pre_launch=fork if overlap else None,
-                            acc_any_stream=overlap)      # (a kept accumulator's last kernels ran on the main stream: fork() orders them)
+                            acc_any_stream=overlap,      # (a kept accumulator's last kernels ran on the main stream: fork() orders them)
+                            off_dev=_offsets_dev(*devs[1]))
         if overlap:
             join = torch.cuda.Event()
             join.record(side)
@@ -83,14 +88,18 @@ class _RasterizePair(torch.autograd.Function):
         ctx.save_for_backward(means3D_c, opt(opac_c), opt(sh_c), opt(sh_p_c), opt(scales_c), opt(rot_c), opt(cov_c),
                               ra["outputs"][10], ra["geom"], ra["binning"], ra["img"],
                               rb["outputs"][10], rb["geom"], rb["binning"], rb["img"],
-                              ra["outputs"][8], rb["outputs"][8])       # `pixels` of both views (read by the backward)
+                              ra["outputs"][8], rb["outputs"][8],       # `pixels` of both views (read by the backward)
+                              *[t if t is not None else dummy for v in devs for t in v])   # offsets read by address, per view
+        ctx.off_dev = [(ph is not None, dc is not None) for ph, dc in devs]
         ctx.mark_non_differentiable(ra["outputs"][10], rb["outputs"][10])
         return tuple(ra["outputs"]) + tuple(rb["outputs"])
 
     @staticmethod
     def backward(ctx, *grads):
         (means3D, opac, sh, sh_p, scales, rotations, cov3D, radii_a, geom_a, bin_a, img_a,
-         radii_b, geom_b, bin_b, img_b, _pix_a, _pix_b) = ctx.saved_tensors
+         radii_b, geom_b, bin_b, img_b, _pix_a, _pix_b, ph_a, dc_a, ph_b, dc_b) = ctx.saved_tensors
+        saved_off = [(ph_a if ctx.off_dev[0][0] else None, dc_a if ctx.off_dev[0][1] else None),
+                     (ph_b if ctx.off_dev[1][0] else None, dc_b if ctx.off_dev[1][1] else None)]
         has_sh, has_sh_p, has_colors, has_phasors, has_scales, has_cov = ctx.present
         views = [(ctx.settings[0], radii_a, geom_a, bin_a, img_a, grads[0:11]),
                  (ctx.settings[1], radii_b, geom_b, bin_b, img_b, grads[11:22])]
@@ -110,7 +119,8 @@ class _RasterizePair(torch.autograd.Function):
                 res = native_backward(s, means3D, opac, sh if has_sh else None, sh_p if has_sh_p else None,
                                       scales if has_scales else None, rotations if has_scales else None,
                                       cov3D if has_cov else None, radii, geom, binning, img, ctx.extra[v][0], ctx.extra[v][1],
-                                      ctx.offs[v][0], ctx.offs[v][1], go, None, has_colors, has_cov, ctx.want_bw)
+                                      ctx.offs[v][0], ctx.offs[v][1], go, None, has_colors, has_cov, ctx.want_bw,
+                                      off_dev=_offsets_dev(*saved_off[v]))
                 if g is not None:
                     for k in g:
                         if k != "offsets" and g[k] is not None:

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define GFT_ABI_VERSION 14
+#define GFT_ABI_VERSION 15
 
 /* compile-time constants of the reference (RAST/cuda_rasterizer/config.h:15-23) */
 #define GFT_NUM_CHANNELS 3
@@ -62,7 +62,7 @@ typedef struct gft_config {
     float scale_modifier;
     float near_n, far_n;
     float depth_range;
-    float phase_offset, dc_offset;
+    float phase_offset, dc_offset;   /* ignored where gft_forward_io / gft_backward_io give phase_offset_dev / dc_offset_dev */
     int32_t use_view_dependent_phase;
     int32_t prefiltered;
     int32_t debug;   /* synchronise + check after every stage (reference CHECK_CUDA) */
@@ -167,6 +167,13 @@ typedef struct gft_forward_io {
      * capacity, or words that are no schedule, are found on the device: nothing is rendered from them, gft_forward runs the
      * counted flow in the same call.  Any contents are safe.  NULL: count, then scatter, every frame. */
     uint32_t* cell_sched;
+    /* optional (ABI 15): one float each in device memory that holds the ToF phase / DC offset (the reference's learnable
+     * _phase_offset / _dc_offset, gaussian_model.py:225-226).  The kernels read the value when they run, so a call captured
+     * in a HIP graph follows a parameter the optimiser updates between replays and the host never reads it.  Non-NULL: the
+     * gft_config scalar of the same name is ignored.  NULL: gft_config's scalar, as before.  Bit-identical results either way
+     * for the same value. */
+    const float* phase_offset_dev;
+    const float* dc_offset_dev;
 } gft_forward_io;
 
 /* Tensors of the backward call (RAST/rasterize_points.cu:167-198). */
@@ -232,6 +239,10 @@ typedef struct gft_backward_io {
      * dense frame: 7 %); a frame that blends most of its Gaussians is better served by a full write (grads_zeroed = 0
      * into the same tensors: marks every row): gftorf_amd/api.py switches on this count. */
     uint32_t* rows_report;
+    /* optional (ABI 15): the offsets in device memory, as gft_forward_io.phase_offset_dev / dc_offset_dev (the same values
+     * as in the forward call; NULL: gft_config's scalar).  The phasor chain of the backward reads both. */
+    const float* phase_offset_dev;
+    const float* dc_offset_dev;
 } gft_backward_io;
 
 /* Byte offsets of the sub-arrays inside the scratch buffers (the forward <->
