@@ -1,13 +1,12 @@
-// k_deform.hip -- the deformation network (reference utils/time_utils.py:56-127) on the gfx950 fp32
-// matrix cores.  See include/gftorf_deform.h for the contract.
+// k_deform.hip -- the deformation network (reference utils/time_utils.py:56-127) on the gfx950 matrix cores, to fp32
+// accuracy.  See include/gftorf_deform.h for the contract.
 //
-// v_mfma_f32_32x32x2_f32: D[32x32] += A[32x2] * B[2x32]; lane l holds A[i = l & 31][k = l >> 5] and
-// B[k = l >> 5][j = l & 31]; D: column = l & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (l >> 5).
-// 64 cycles per instruction per SIMD = the fp32 peak (157 TFLOP/s), so the kernels only have to
-// keep one wave per SIMD fed.  The walks keep a tile of points' activations in LDS (16-byte reads,
-// 4 k per read) and stream the weights L2 -> registers, each wave its own 64 output columns (the packed
-// weights are interleaved [k/4][n][4] for 16-byte loads), one 16-k chunk ahead of the multiply; the
-// weight-gradient kernel reads both operands straight from global memory.
+// v_mfma_f32_32x32x16_bf16 / _f16: D[32x32] += A[32x16] * B[16x32]; lane l holds A[i = l & 31][k = 8 (l >> 5) .. +7] and
+// B[k = 8 (l >> 5) .. +7][j = l & 31]; D: column = l & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (l >> 5).  An fp32
+// operand is split into planes of the narrow type (three bf16 or two fp16) and a product is the sum of the plane products
+// that matter (six or three MFMAs) in one fp32 accumulator.  The walks keep a tile of 64 points' activations in LDS as
+// such planes and stream the weights L2 -> registers from the packed buffer's plane copies, each wave its own output
+// columns; the weight-gradient kernels read both operands as fp32 straight from global memory and split them.
 #include "gft_internal.h"
 #include "gftorf_deform.h"
 #include "gftorf_densify.h"
@@ -28,14 +27,10 @@ constexpr int DF_INK = GFT_DEFORM_MAX_INPUTS;   // encoding as a GEMM k-extent (
 constexpr int DF_EMB = GFT_DEFORM_MAX_INPUTS;   // stored encoding row (3 column tiles of the weight-gradient GEMM)
 static_assert(DF_INK == 96, "the encoding tiles assume 96 columns");
 constexpr int DF_HEAD = 64;                // head columns: 48 (d_sh, [coefficient][channel]) + 3 (d_xyz) + pad
-// 32-point row tiles per wave = points per workgroup / 32.  Measured on MI355X (300 k points): forward 64 points
-// 2.70 ms (one workgroup per CU; 2.83 with two), 96 points 3.21 ms; backward 64 points 2.89 ms, 96 points 2.81 ms.
-constexpr int DF_NR_FWD = 2;
-constexpr int DF_NR_BWD = 3;
-constexpr int DF_PAD = 192;                // point counts are padded to a multiple of both walk tiles and of 64
-constexpr int DF_ES = 100;                 // LDS row stride of the encoding (16-byte reads of 16 rows hit 16 bank groups)
+// Point counts are padded to a multiple of DF_PAD, itself a multiple of the walks' 64-point workgroups and of DF_DW_TILE.
+// The value sets the saved and scratch buffer sizes and where the weight-gradient splits begin (their summation order).
+constexpr int DF_PAD = 192;
 constexpr int DF_DW_TILE = 64;             // point granularity of the weight-gradient splits
-constexpr int DF_HS = 260;                 // LDS row strides (floats): 16-byte reads of 16 rows hit 16 bank groups
 
 // packed parameter buffer (floats): forward stream, backward stream, biases
 constexpr int64_t DF_F_SZ0 = (int64_t)DF_INK * DF_W;                  // 20480
@@ -190,7 +185,7 @@ __global__ __launch_bounds__(256) void k_deform_pack_bf(const float* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------
-// the streamed GEMM both walks use: acc[rt][ct] += (A[64 x K] * W[K x ncol])^T, 16 k per chunk.
+// the streamed GEMM of the walks (stream_gemm_bf, stream_gemm_h): acc[rt][ct] += (A[64 x K] * W[K x ncol])^T, 16 k per chunk.
 // The weights are the MFMA's A operand and the activations its B operand, so a result tile has the POINT on
 // the lane and the output column on the registers: registers 4g..4g+3 of lane (j, hh) are columns
 // 8g + 4hh .. +3 of point j -- 16-byte LDS and global stores in the epilogues.
@@ -205,69 +200,6 @@ __device__ __forceinline__ void zero_acc(f32x16 (&acc)[NR][NC])
 #pragma unroll
             for (int q = 0; q < 16; q++) acc[r][c][q] = 0.f;
 }
-
-__device__ __forceinline__ float f4_get(const float4& v, int s) { return s == 0 ? v.x : s == 1 ? v.y : s == 2 ? v.z : v.w; }
-
-// A wave owns its columns of W: no other wave reads them, so the weights go L2 -> registers directly
-// (lane (j, hh) reads the float4 [k/4 = 2r + hh][column j]: 512 contiguous bytes per half wave), one
-// chunk ahead of the multiply; the A tile (activations, shared by the four waves) is read from LDS, one
-// chunk ahead as well.  No barrier inside a layer.
-// k order inside a chunk: (0,4) (1,5) (2,6) (3,7) (8,12) ... -- any fixed order is a valid fp32 sum.
-template <int NC, int NCOL>
-__device__ __forceinline__ void load_w(float4 (&w)[2][NC], const float4* wlane)
-{
-#pragma unroll
-    for (int r = 0; r < 2; r++)
-#pragma unroll
-        for (int ct = 0; ct < NC; ct++) w[r][ct] = wlane[2 * r * NCOL + ct * 32];
-}
-
-// wlane: the lane's float4 of the segment's first chunk ([hh][first column + j]); wcur: that chunk, already
-// loaded.  more_after: the stream continues with a chunk of the same shape (it is prefetched into wcur).
-template <int NR, int NC, int NCOL>
-__device__ __forceinline__ void stream_gemm(f32x16 (&acc)[NR][NC], const float* a_lane, int a_stride, int nchunks,
-                                            const float4*& wlane, float4 (&wcur)[2][NC], bool more_after)
-{
-    float4 acur[2][NR];
-#pragma unroll
-    for (int r = 0; r < 2; r++)
-#pragma unroll
-        for (int rt = 0; rt < NR; rt++) acur[r][rt] = *reinterpret_cast<const float4*>(a_lane + rt * 32 * a_stride + 8 * r);
-    for (int c = 0; c < nchunks; c++) {
-        const bool last = c + 1 >= nchunks;
-        // (unconditional loads from clamped addresses: conditionally filled arrays end up in scratch)
-        const float4* wn = wlane + ((!last || more_after) ? 4 * NCOL : 0);
-        const float* an = a_lane + (last ? c : c + 1) * 16;
-        float4 wnxt[2][NC], anxt[2][NR];
-        load_w<NC, NCOL>(wnxt, wn);
-#pragma unroll
-        for (int r = 0; r < 2; r++)
-#pragma unroll
-            for (int rt = 0; rt < NR; rt++) anxt[r][rt] = *reinterpret_cast<const float4*>(an + rt * 32 * a_stride + 8 * r);
-        // keep the loads above the multiply (the scheduler otherwise sinks them to their use, after it)
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int r = 0; r < 2; r++)
-#pragma unroll
-            for (int s = 0; s < 4; s++)
-#pragma unroll
-                for (int rt = 0; rt < NR; rt++)
-#pragma unroll
-                    for (int ct = 0; ct < NC; ct++)
-                        acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(f4_get(wcur[r][ct], s), f4_get(acur[r][rt], s),
-                                                                           acc[rt][ct], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        wlane = wn;
-#pragma unroll
-        for (int r = 0; r < 2; r++) {
-#pragma unroll
-            for (int ct = 0; ct < NC; ct++) wcur[r][ct] = wnxt[r][ct];
-#pragma unroll
-            for (int rt = 0; rt < NR; rt++) acur[r][rt] = anxt[r][rt];
-        }
-    }
-}
-
 
 // first column (within its 32-column tile) of register group g = registers 4g..4g+3
 __device__ __forceinline__ int acc_col4(int g, int hh) { return 8 * g + 4 * hh; }
@@ -306,168 +238,13 @@ struct FwdArgs {
 
 constexpr int DF_BIAS_FLOATS = DF_D * DF_W + DF_HEAD;      // 2368
 constexpr int DF_SIGN_WORDS = DF_W / 32;                   // ReLU sign bits of one point and layer: 8 words
-constexpr size_t DF_FWD_LDS = ((size_t)32 * DF_NR_FWD * (DF_HS + DF_ES) + DF_BIAS_FLOATS) * 4;   // activations + encoding + all biases: 97536
-constexpr size_t DF_BWD_LDS = (size_t)32 * DF_NR_BWD * DF_HS * 4;                               // 99840
-
-template <bool SAVE>
-__global__ __launch_bounds__(256) void k_deform_fwd(FwdArgs a)
-{
-    extern __shared__ float4 df_lds[];
-    if (a.plan) {      // counts the device keeps (DevPlan): the launch is the capacity's, surplus workgroups return
-        if ((int64_t)blockIdx.x * (32 * DF_NR_FWD) >= a.plan->n_ext) return;
-        a.n = a.plan->n;
-    }
-    float* hA = reinterpret_cast<float*>(df_lds);
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31, hh = lane >> 5;
-    const int64_t p0 = (int64_t)blockIdx.x * (32 * DF_NR_FWD);
-    const int n0 = wave * 64;
-    const float4* wlane = reinterpret_cast<const float4*>(a.packed) + hh * DF_W + n0 + li;
-    float4 wcur[2][2];
-    load_w<2, DF_W>(wcur, wlane);
-    // all biases (9.5 KB) go to LDS once: an epilogue then waits for an LDS read, not for L2
-    float* eA = hA + (32 * DF_NR_FWD) * DF_HS;
-    float* bL = eA + (32 * DF_NR_FWD) * DF_ES;
-    for (int q = tid; q < DF_BIAS_FLOATS; q += 256) bL[q] = a.packed[DF_BIAS_BASE + q];
-
-    // positional encoding (time_utils.py:24-53): [x, sin(2^f x), cos(2^f x)]_f for all dims, then t
-    for (int pb = 0; pb < (32 * DF_NR_FWD); pb += 64) {
-        const int pt = pb + (tid & 63), grp = tid >> 6;
-        if (pt >= (32 * DF_NR_FWD)) break;
-        const int64_t p = p0 + pt;
-        float* e = eA + pt * DF_ES;
-        if (grp < 3) {
-            const float v = p < a.n ? a.xyz[3 * p + grp] : 0.f;
-            e[grp] = v;
-            for (int f = 0; f < a.xm; f++) {
-                float sn, cs;
-                sincosf(v * (float)(1 << f), &sn, &cs);
-                e[3 + 6 * f + grp] = sn;
-                e[6 + 6 * f + grp] = cs;
-            }
-        } else {
-            const float v = p < a.n ? a.t[p * a.t_stride] : 0.f;
-            const int t0 = 3 + 6 * a.xm;
-            e[t0] = v;
-            for (int f = 0; f < a.tm; f++) {
-                float sn, cs;
-                sincosf(v * (float)(1 << f), &sn, &cs);
-                e[t0 + 1 + 2 * f] = sn;
-                e[t0 + 2 + 2 * f] = cs;
-            }
-            for (int c = t0 + 1 + 2 * a.tm; c < DF_INK; c++) e[c] = 0.f;
-        }
-    }
-    __syncthreads();
-    if (SAVE) {
-        for (int q = tid; q < (32 * DF_NR_FWD) * DF_EMB; q += 256) {
-            const int row = q / DF_EMB, col = q - row * DF_EMB;
-            a.emb[(p0 + row) * DF_EMB + col] = eA[row * DF_ES + col];
-        }
-    }
-
-    const float* h_lane = hA + li * DF_HS + 4 * hh;
-    const float* e_lane = eA + li * DF_ES + 4 * hh;
-    f32x16 acc[DF_NR_FWD][2];
-    for (int l = 0; l < DF_D; l++) {
-        zero_acc(acc);
-        if (l == 0) {
-            stream_gemm<DF_NR_FWD, 2, DF_W>(acc, e_lane, DF_ES, DF_INK / 16, wlane, wcur, true);
-        } else {
-            // after layer 4 the encoding is concatenated in front (time_utils.py:112-113)
-            if (l == 5) stream_gemm<DF_NR_FWD, 2, DF_W>(acc, e_lane, DF_ES, DF_INK / 16, wlane, wcur, true);
-            stream_gemm<DF_NR_FWD, 2, DF_W>(acc, h_lane, DF_HS, DF_W / 16, wlane, wcur, l < 7);
-        }
-        // bias, ReLU -> next layer's A tile
-        float4 bv[2][4];
-#pragma unroll
-        for (int ct = 0; ct < 2; ct++)
-#pragma unroll
-            for (int g = 0; g < 4; g++)
-                bv[ct][g] = *reinterpret_cast<const float4*>(bL + l * DF_W + n0 + 32 * ct + acc_col4(g, hh));
-        __syncthreads();      // every wave is past its last read of this layer's input
-#pragma unroll
-        for (int rt = 0; rt < DF_NR_FWD; rt++)
-#pragma unroll
-            for (int ct = 0; ct < 2; ct++) {
-                uint32_t bits = 0;
-#pragma unroll
-                for (int g = 0; g < 4; g++) {
-                    const int row = 32 * rt + li, col = n0 + 32 * ct + acc_col4(g, hh);
-                    float4 v;
-                    v.x = fmaxf(acc[rt][ct][4 * g] + bv[ct][g].x, 0.f);
-                    v.y = fmaxf(acc[rt][ct][4 * g + 1] + bv[ct][g].y, 0.f);
-                    v.z = fmaxf(acc[rt][ct][4 * g + 2] + bv[ct][g].z, 0.f);
-                    v.w = fmaxf(acc[rt][ct][4 * g + 3] + bv[ct][g].w, 0.f);
-                    *reinterpret_cast<float4*>(hA + row * DF_HS + col) = v;
-                    if (SAVE) {
-                        *reinterpret_cast<float4*>(a.acts + ((int64_t)l * a.n_pad + p0 + row) * DF_W + col) = v;
-                        bits |= ((v.x > 0.f ? 1u : 0u) | (v.y > 0.f ? 2u : 0u) | (v.z > 0.f ? 4u : 0u) | (v.w > 0.f ? 8u : 0u))
-                                << acc_col4(g, hh);
-                    }
-                }
-                if (SAVE) {
-                    // the other half wave holds the other 16 columns of this 32-column word
-                    bits |= (uint32_t)__shfl_xor((int)bits, 32);
-                    if (hh == 0) a.signs[((int64_t)l * a.n_pad + p0 + 32 * rt + li) * DF_SIGN_WORDS + 2 * wave + ct] = bits;
-                }
-            }
-        __syncthreads();
-    }
-    // heads: 64 columns
-    {
-        const int ct = wave & 1;
-        const float4* hl = reinterpret_cast<const float4*>(a.packed + DF_F_TOTAL - DF_F_HEAD_SZ) + hh * DF_HEAD + 32 * ct + li;
-        float4 hw[2][1];
-        load_w<1, DF_HEAD>(hw, hl);
-        auto store_head = [&](const f32x16& t, int row0) {
-            const int64_t p = p0 + row0 + li;
-            if (p < a.n) {
-#pragma unroll
-                for (int g = 0; g < 4; g++) {
-                    const int col = 32 * ct + acc_col4(g, hh);
-                    const float4 bq = *reinterpret_cast<const float4*>(bL + DF_D * DF_W + col);
-                    const float4 v = make_float4(t[4 * g] + bq.x, t[4 * g + 1] + bq.y, t[4 * g + 2] + bq.z, t[4 * g + 3] + bq.w);
-                    if (col < 48) {
-                        *reinterpret_cast<float4*>(a.d_sh + p * 48 + col) = v;
-                    } else if (col == 48) {
-                        a.d_xyz[p * 3] = v.x;
-                        a.d_xyz[p * 3 + 1] = v.y;
-                        a.d_xyz[p * 3 + 2] = v.z;
-                    }
-                }
-            }
-        };
-        if (DF_NR_FWD == 3) {
-            // 3 row tiles x 2 column tiles over 4 waves: waves 0,1 take row tiles 0,1, waves 2,3 row tile 2
-            if (wave < 2) {
-                f32x16 hacc[2][1];
-                zero_acc(hacc);
-                stream_gemm<2, 1, DF_HEAD>(hacc, hA + li * DF_HS + 4 * hh, DF_HS, DF_W / 16, hl, hw, false);
-                store_head(hacc[0][0], 0);
-                store_head(hacc[1][0], 32);
-            } else {
-                f32x16 hacc[1][1];
-                zero_acc(hacc);
-                stream_gemm<1, 1, DF_HEAD>(hacc, hA + (64 + li) * DF_HS + 4 * hh, DF_HS, DF_W / 16, hl, hw, false);
-                store_head(hacc[0][0], 64);
-            }
-        } else {
-            // 2 x 2 tiles: one per wave
-            const int r0 = 32 * (wave >> 1);
-            f32x16 hacc[1][1];
-            zero_acc(hacc);
-            stream_gemm<1, 1, DF_HEAD>(hacc, hA + (r0 + li) * DF_HS + 4 * hh, DF_HS, DF_W / 16, hl, hw, false);
-            store_head(hacc[0][0], r0);
-        }
-    }
-}
 
 // ---------------------------------------------------------------------------------------------
-// forward walk on three bf16 planes: six bf16 MFMAs per product (hi*hi, hi*mid, mid*hi, hi*lo, lo*hi, mid*mid;
-// the three dropped terms are below 2^-23 of the product) accumulate in fp32 -- the error against float64 is
-// that of an fp32 fma chain (profiles/experiments/bf16x3_gemm.hip: 5.4e-7 vs 5.5e-7), at up to 2.7 x the rate
-// of v_mfma_f32_32x32x2_f32.  Activations live in LDS as three bf16 planes (the epilogue splits them),
-// weights come as three bf16 planes from the packed copy.
+// forward walk on three bf16 planes: every fp32 operand is hi + mid + lo bf16 (24 mantissa bits), and six
+// v_mfma_f32_32x32x16_bf16 per product (hi*hi, hi*mid, mid*hi, hi*lo, lo*hi, mid*mid; the three dropped terms are below
+// 2^-23 of the product) accumulate in fp32 -- the error against float64 is that of an fp32 fma chain
+// (profiles/experiments/bf16x3_gemm.hip: 5.4e-7 vs 5.5e-7).  Activations live in LDS as three bf16 planes (the epilogue
+// splits them), weights come as three bf16 planes from the packed copy.
 // ---------------------------------------------------------------------------------------------
 constexpr int DF_BH = 264;                 // bf16 per activation row of a plane (528 B: 16-byte reads of 16 rows hit 16 bank groups)
 constexpr int DF_BE = 104;                 // bf16 per encoding row of a plane (208 B: 16-byte reads of 16 rows hit 16 bank groups)
@@ -530,7 +307,7 @@ __device__ __forceinline__ void stream_gemm_bf(f32x16 (&acc)[NR][NC], const char
 #pragma unroll
             for (int rt = 0; rt < NR; rt++)
                 anxt[pl][rt] = *reinterpret_cast<const uint4*>(a_lane + pl * a_plane_bytes + (size_t)rt * 32 * a_row_bytes + cn * 32);
-        // weights are the MFMA's A operand, activations its B operand (point on the lane, see stream_gemm)
+        // weights are the MFMA's A operand, activations its B operand (point on the lane, see above zero_acc)
 #pragma unroll
         for (int term = 0; term < 6; term++) {
             const int pw = term == 0 ? 0 : term == 1 ? 1 : term == 2 ? 0 : term == 3 ? 2 : term == 4 ? 0 : 1;
@@ -1305,79 +1082,9 @@ struct BwdArgs {
     uint32_t* xflag;        // cleared by k_deform_bwd_h; k_deform_dw_h sets it when an activation does not fit its fp16 planes
 };
 
-__global__ __launch_bounds__(256) void k_deform_bwd(BwdArgs a)
-{
-    extern __shared__ float4 df_lds[];
-    if (a.plan) {      // counts the device keeps (DevPlan): the launch is the capacity's, surplus workgroups return
-        if ((int64_t)blockIdx.x * (32 * DF_NR_BWD) >= a.plan->n_ext) return;
-        a.n = a.plan->n;
-    }
-    float* gA = reinterpret_cast<float*>(df_lds);
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31, hh = lane >> 5;
-    const int64_t p0 = (int64_t)blockIdx.x * (32 * DF_NR_BWD);
-    const int n0 = wave * 64;
-    const float4* wlane = reinterpret_cast<const float4*>(a.packed + DF_B_BASE) + hh * DF_W + n0 + li;
-    float4 wcur[2][2];
-    load_w<2, DF_W>(wcur, wlane);
-
-    // upstream gradients as the head's output tile: [d_sh (48) | d_xyz (3) | 0], in the first 64 columns
-    for (int q = tid; q < (32 * DF_NR_BWD) * DF_HEAD; q += 256) {
-        const int row = q >> 6, col = q & 63;
-        const int64_t p = p0 + row;
-        float v = 0.f;
-        if (p < a.n) {
-            if (col < 48) v = a.g_dsh ? a.g_dsh[p * 48 + col] : 0.f;
-            else if (col < 51) v = a.g_dxyz ? a.g_dxyz[p * 3 + (col - 48)] : 0.f;
-        }
-        gA[row * DF_HS + col] = v;
-        a.dzh[p * DF_HEAD + col] = v;
-    }
-    __syncthreads();
-
-    const float* g_lane = gA + li * DF_HS + 4 * hh;
-    f32x16 acc[DF_NR_BWD][2];
-    // ReLU signs of the lane's point and the wave's 64 columns (2 words per row tile), fetched before the
-    // multiply that produces the gradient they gate
-    uint2 sg[DF_NR_BWD];
-    auto load_signs = [&](int l) {
-#pragma unroll
-        for (int rt = 0; rt < DF_NR_BWD; rt++)
-            sg[rt] = *reinterpret_cast<const uint2*>(a.signs + ((int64_t)l * a.n_pad + p0 + 32 * rt + li) * DF_SIGN_WORDS + 2 * wave);
-    };
-    load_signs(DF_D - 1);
-    zero_acc(acc);
-    stream_gemm<DF_NR_BWD, 2, DF_W>(acc, g_lane, DF_HS, DF_HEAD / 16, wlane, wcur, true);   // dh_7
-    for (int l = DF_D - 1; l >= 0; l--) {
-        __syncthreads();      // every wave is past its last read of the previous gradient tile
-#pragma unroll
-        for (int rt = 0; rt < DF_NR_BWD; rt++)
-#pragma unroll
-            for (int ct = 0; ct < 2; ct++) {
-                const int row = 32 * rt + li;
-                const uint32_t word = ct == 0 ? sg[rt].x : sg[rt].y;
-#pragma unroll
-                for (int g = 0; g < 4; g++) {
-                    const int col = n0 + 32 * ct + acc_col4(g, hh);
-                    const uint32_t m = word >> acc_col4(g, hh);
-                    float4 v;
-                    v.x = (m & 1u) ? acc[rt][ct][4 * g] : 0.f;
-                    v.y = (m & 2u) ? acc[rt][ct][4 * g + 1] : 0.f;
-                    v.z = (m & 4u) ? acc[rt][ct][4 * g + 2] : 0.f;
-                    v.w = (m & 8u) ? acc[rt][ct][4 * g + 3] : 0.f;
-                    if (l > 0) *reinterpret_cast<float4*>(gA + row * DF_HS + col) = v;
-                    *reinterpret_cast<float4*>(a.dz + ((int64_t)l * a.n_pad + p0 + row) * DF_W + col) = v;
-                }
-            }
-        if (l == 0) break;
-        __syncthreads();
-        load_signs(l - 1);
-        zero_acc(acc);
-        stream_gemm<DF_NR_BWD, 2, DF_W>(acc, g_lane, DF_HS, DF_W / 16, wlane, wcur, l > 1);   // dh_{l-1}
-    }
-}
-
-// backward walk on three bf16 planes (64 points per workgroup): as k_deform_bwd, with the gradient tile in LDS
-// as hi / mid / lo planes and the weights from the bf16 copy of the backward stream
+// backward walk on three bf16 planes (64 points per workgroup): the upstream gradients form the head's output tile, each
+// layer's product is gated by the saved ReLU signs; the gradient tile sits in LDS as hi / mid / lo planes, the weights
+// come from the bf16 copy of the backward stream, six v_mfma_f32_32x32x16_bf16 per product as in k_deform_fwd_bf
 constexpr size_t DF_BWD_BF_LDS = 3 * DF_BF_ACT_PLANE;   // 101376
 
 constexpr int DF_BWD_WAVES = 4;                        // as DF_FWD_WAVES; measured at 300 k points: 1.64 ms with 4, 1.76 ms with 8
@@ -1644,7 +1351,6 @@ __global__ __launch_bounds__(64 * DF_BWD_WAVES) __attribute__((amdgpu_waves_per_
 // weight / bias gradients: dW[out][in] = sum over points of dz[p][out] * x[p][in], split over point
 // ranges; operands are read straight from global (lane = consecutive column: coalesced rows)
 // ---------------------------------------------------------------------------------------------
-constexpr int DW_JOBS = 10;
 // partial-sum block of one split (floats)
 constexpr int64_t DW_OFF_L0 = 0;                                         // [256][96]
 constexpr int64_t DW_OFF_L(int l) { return (int64_t)DF_W * DF_EMB + (int64_t)(l - 1) * DF_F_SZ; }   // l = 1..7: [256][256] (layer 5: hidden part)
@@ -1668,94 +1374,12 @@ struct DwArgs {
     int only_if;            // k_deform_dw_bf's hidden-layer launch behind k_deform_dw_h: run only if that one could not
 };
 
-// V consecutive floats as one load / store (V = 2, 3, 4: global_load_dwordx2/x3/x4)
-template <int V> struct FVec { float v[V]; };
-template <> struct __attribute__((aligned(8))) FVec<2> { float v[2]; };
-template <> struct __attribute__((aligned(16))) FVec<4> { float v[4]; };
-
-// One wave's block of dW: 32*VN output rows (n) x 32*VK input columns (k), summed over the points of the range.
-// A lane loads VN consecutive columns of dz and VK consecutive columns of x for its point (two vector loads per
-// two points instead of VN + VK scalar ones: the loads' address processing, not the multiplies, set the pace
-// of the scalar version) and uses element t in tile t, so tile (tn, tk) holds rows n = n_base + VN*i + tn and
-// columns k = k_base + VK*j + tk: VK consecutive k per lane and register -> vector stores.
-template <int VN, int VK, bool BIAS>
-__device__ __forceinline__ void dw_job(const float* A, int lda, int n_base, const float* B, int ldb, int k_base, float* out,
-                                       int out_ld, float* bias_out, bool write_bias, int64_t p_begin, int64_t p_end, int li, int hh)
-{
-    f32x16 acc[VN][VK];
-    zero_acc(acc);
-    float bsum[VN];
-#pragma unroll
-    for (int x = 0; x < VN; x++) bsum[x] = 0.f;
-    const float* Ap = A + (p_begin + hh) * lda + n_base + VN * li;
-    const float* Bp = B + (p_begin + hh) * ldb + k_base + VK * li;
-    // operands of four 8-point steps in registers: three steps in flight ahead of the one being multiplied
-    FVec<VN> av[4][4];
-    FVec<VK> bv[4][4];
-    int64_t pf = p_begin;          // first point of the next step to fetch
-    auto fetch = [&](int slot) {
-        if (pf < p_end) {
-#pragma unroll
-            for (int s = 0; s < 4; s++) {
-                av[slot][s] = *reinterpret_cast<const FVec<VN>*>(Ap + (int64_t)2 * s * lda);
-                bv[slot][s] = *reinterpret_cast<const FVec<VK>*>(Bp + (int64_t)2 * s * ldb);
-            }
-            Ap += 8 * lda;
-            Bp += 8 * ldb;
-        }
-        pf += 8;
-    };
-    auto mul = [&](int slot) {
-#pragma unroll
-        for (int s = 0; s < 4; s++) {
-#pragma unroll
-            for (int x = 0; x < VN; x++) {
-                if (BIAS) bsum[x] += av[slot][s].v[x];
-#pragma unroll
-                for (int y = 0; y < VK; y++)
-                    acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[slot][s].v[x], bv[slot][s].v[y], acc[x][y], 0, 0, 0);
-            }
-        }
-    };
-    // 32 points per loop trip (the ranges are multiples of 64)
-    if (p_begin < p_end) {
-        fetch(0);
-        fetch(1);
-        fetch(2);
-        for (int64_t p = p_begin; p < p_end; p += 32) {
-            fetch(3);
-            mul(0);
-            fetch(0);
-            mul(1);
-            fetch(1);
-            mul(2);
-            fetch(2);
-            mul(3);
-        }
-    }
-#pragma unroll
-    for (int x = 0; x < VN; x++)
-#pragma unroll
-        for (int q = 0; q < 16; q++) {
-            FVec<VK> o;
-#pragma unroll
-            for (int y = 0; y < VK; y++) o.v[y] = acc[x][y][q];
-            *reinterpret_cast<FVec<VK>*>(out + (int64_t)(n_base + VN * acc_row(q, hh) + x) * out_ld + k_base + VK * li) = o;
-        }
-    if (BIAS && write_bias) {
-#pragma unroll
-        for (int x = 0; x < VN; x++) {
-            const float tot = bsum[x] + __shfl_xor(bsum[x], 32);
-            if (hh == 0) bias_out[n_base + VN * li + x] = tot;
-        }
-    }
-}
-
-// The same block of dW from six bf16 MFMAs per product: a lane loads, per 16-point step, the eight values of its
-// output row (column of dz) and of its input column (column of x) at its eight points -- v_mfma_f32_32x32x16_bf16
-// wants eight consecutive k per lane, k = point here -- splits them into hi / mid / lo and multiplies; the
-// operands stay fp32 in memory (4 B per element from HBM instead of 6), the split costs VALU time between the
-// multiplies of consecutive steps.
+// One wave's block of dW: 32*TN output rows (n) x 32*TK input columns (k), summed over the points of the range, from six
+// bf16 MFMAs per product; tile (x, y) holds rows n_base + 32x + i and columns k_base + 32y + j.  A lane loads, per
+// 16-point step, the eight values of its output row (column of dz) and of its input column (column of x) at its eight
+// points -- v_mfma_f32_32x32x16_bf16 wants eight consecutive k per lane, k = point here -- splits them into hi / mid / lo
+// and multiplies; the operands stay fp32 in memory (4 B per element from HBM instead of 6), the split costs VALU time
+// between the multiplies of consecutive steps.
 template <int TN, int TK, bool BIAS>
 __device__ __forceinline__ void dw_job_bf(const float* A, int lda, int n_base, const float* B, int ldb, int k_base, float* out,
                                           int out_ld, float* bias_out, bool write_bias, int64_t p_begin, int64_t p_end, int li, int hh)
@@ -2237,6 +1861,8 @@ __global__ __launch_bounds__(256) void k_deform_dw_bf(DwArgs a)
     if (a.only_if && __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(a.packed + DF_FLAG_OFF)) == 0u &&
         __hip_atomic_load(a.xflag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
         return;
+    // the job table: the 7 hidden-layer GEMMs of every split (layers 7..1, heaviest first), then the three light jobs of
+    // every split (layer 0, the encoding rows of layer 5, the heads)
     int job, split;
     if (a.plan) {      // counts the device keeps (DevPlan): the launch is the capacity's, surplus workgroups return below
         a.splits = a.plan->splits; a.tiles_per_split = a.plan->tiles_per_split; a.n_ext = a.plan->n_ext;
@@ -2272,46 +1898,6 @@ __global__ __launch_bounds__(256) void k_deform_dw_bf(DwArgs a)
     } else {
         dw_job_bf<2, 2, true>(a.dzh, DF_HEAD, 0, a.acts + 7 * plane, DF_W, 64 * wave, part + DW_OFF_HEAD, DF_W,
                               part + DW_OFF_BIAS + DF_D * DF_W, wave == 0, p_begin, p_end, li, hh);
-    }
-}
-
-__global__ __launch_bounds__(256) void k_deform_dw(DwArgs a)
-{
-    // heavy jobs first: the 7 hidden-layer GEMMs of every split (7 x splits workgroups, one resident per CU at
-    // a time), then the three light jobs, which fill the CUs as they run out of heavy ones
-    int job, split;
-    if (a.plan) { a.splits = a.plan->splits; a.tiles_per_split = a.plan->tiles_per_split; a.n_ext = a.plan->n_ext; }
-    if ((int)blockIdx.x < 7 * a.splits) {
-        job = blockIdx.x % 7;
-        split = blockIdx.x / 7;
-    } else {
-        const int r = blockIdx.x - 7 * a.splits;
-        job = 7 + r % 3;
-        split = r / 3;
-    }
-    if (split >= a.splits) return;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31, hh = lane >> 5;
-    const int64_t p_begin = (int64_t)split * a.tiles_per_split * DF_DW_TILE;
-    int64_t p_end = p_begin + (int64_t)a.tiles_per_split * DF_DW_TILE;
-    if (p_end > a.n_ext) p_end = a.n_ext;
-    float* part = a.part + (int64_t)split * DW_PART_FLOATS;
-    const int64_t plane = a.n_pad * DF_W;
-    if (job < 7) {
-        // hidden-input layers 7..1 (heaviest first): x = act_{l-1}; waves take the four 128 x 128 quadrants
-        const int l = 7 - job;
-        dw_job<4, 4, true>(a.dz + l * plane, DF_W, 128 * (wave & 1), a.acts + (l - 1) * plane, DF_W, 128 * (wave >> 1),
-                           part + DW_OFF_L(l), DF_W, part + DW_OFF_BIAS + l * DF_W, (wave >> 1) == 0, p_begin, p_end, li, hh);
-    } else if (job == 7) {
-        // layer 0 and the encoding rows of layer 5: x = encoding (96 stored columns); waves take 64 output rows each
-        dw_job<2, 3, true>(a.dz, DF_W, 64 * wave, a.emb, DF_EMB, 0, part + DW_OFF_L0, DF_EMB, part + DW_OFF_BIAS, true, p_begin,
-                           p_end, li, hh);
-    } else if (job == 8) {
-        dw_job<2, 3, false>(a.dz + 5 * plane, DF_W, 64 * wave, a.emb, DF_EMB, 0, part + DW_OFF_L5E, DF_EMB, nullptr, false,
-                            p_begin, p_end, li, hh);
-    } else {
-        // heads: 64 output rows, waves take 64 input columns each
-        dw_job<2, 2, true>(a.dzh, DF_HEAD, 0, a.acts + 7 * plane, DF_W, 64 * wave, part + DW_OFF_HEAD, DF_W,
-                           part + DW_OFF_BIAS + DF_D * DF_W, wave == 0, p_begin, p_end, li, hh);
     }
 }
 
@@ -2365,12 +1951,6 @@ __host__ __device__ int dw_splits(int64_t n_pad, int* tiles_per_split)
     return (int)((tiles + tps - 1) / tps);
 }
 
-// GFT_DEFORM_BF16X3=0: the walks multiply with v_mfma_f32_32x32x2_f32 instead of six bf16 MFMAs per product
-bool bf16_planes()
-{
-    static const bool on = [] { const char* e = getenv("GFT_DEFORM_BF16X3"); return e ? atoi(e) != 0 : true; }();
-    return on;
-}
 // GFT_DEFORM_FP16X2=0: the forward walk on three bf16 planes (six multiplies per product) instead of two fp16 planes (three)
 bool fp16_forward()
 {
@@ -2388,18 +1968,15 @@ bool fp16_backward()
 // the walks' dynamic-LDS opt-in, per device (gft_lds_opt_in)
 hipError_t set_attrs()
 {
-    static std::atomic<uint64_t> done[9];
-    struct { const void* fn; size_t bytes; } k[9] = {
+    static std::atomic<uint64_t> done[6];
+    struct { const void* fn; size_t bytes; } k[6] = {
         {reinterpret_cast<const void*>(&k_deform_bwd_h), DF_BWD_H_LDS},
         {reinterpret_cast<const void*>(&k_deform_fwd_h<true, DF_FWD_H_SAVE_WAVES>), DF_FWD_H_SAVE_LDS},
         {reinterpret_cast<const void*>(&k_deform_fwd_h<false, DF_FWD_WAVES>), DF_FWD_H_LDS},
         {reinterpret_cast<const void*>(&k_deform_bwd_bf), DF_BWD_BF_LDS},
         {reinterpret_cast<const void*>(&k_deform_fwd_bf<true>), DF_FWD_BF_LDS},
-        {reinterpret_cast<const void*>(&k_deform_fwd_bf<false>), DF_FWD_BF_LDS},
-        {reinterpret_cast<const void*>(&k_deform_fwd<true>), DF_FWD_LDS},
-        {reinterpret_cast<const void*>(&k_deform_fwd<false>), DF_FWD_LDS},
-        {reinterpret_cast<const void*>(&k_deform_bwd), DF_BWD_LDS}};
-    for (int i = 0; i < 9; i++) {
+        {reinterpret_cast<const void*>(&k_deform_fwd_bf<false>), DF_FWD_BF_LDS}};
+    for (int i = 0; i < 6; i++) {
         const hipError_t e = gft_lds_opt_in(k[i].fn, k[i].bytes, done[i]);
         if (e != hipSuccess) return e;
     }
@@ -2547,10 +2124,10 @@ static int deform_forward_impl(void* hip_stream, int xyz_multires, int t_multire
     a.d_xyz = d_xyz;
     a.d_sh = d_sh;
     // all padded rows are computed and saved: the weight-gradient GEMMs multiply them (by zero gradients)
-    const dim3 grid((unsigned)(a.n_pad / (32 * DF_NR_FWD)));
+    const dim3 grid((unsigned)(a.n_pad / 64));      // 64 points per workgroup
     a.gen = 0;
     a.only_if = 0;
-    if (bf16_planes() && fp16_forward()) {
+    if (fp16_forward()) {
         static std::atomic<uint32_t> calls{0};
         do a.gen = ++calls; while (a.gen == 0);
         if (saved)
@@ -2561,15 +2138,9 @@ static int deform_forward_impl(void* hip_stream, int xyz_multires, int t_multire
         GFT_CHECK_HIP(hipGetLastError());
         // the fp32-range walk behind it: its workgroups return at once unless the fp16 planes could not hold a value
         a.only_if = a.gen;
-        if (saved) hipLaunchKernelGGL(k_deform_fwd_bf<true>, grid, dim3(64 * DF_FWD_WAVES), DF_FWD_BF_LDS, (hipStream_t)hip_stream, a);
-        else hipLaunchKernelGGL(k_deform_fwd_bf<false>, grid, dim3(64 * DF_FWD_WAVES), DF_FWD_BF_LDS, (hipStream_t)hip_stream, a);
-    } else if (bf16_planes()) {
-        if (saved) hipLaunchKernelGGL(k_deform_fwd_bf<true>, grid, dim3(64 * DF_FWD_WAVES), DF_FWD_BF_LDS, (hipStream_t)hip_stream, a);
-        else hipLaunchKernelGGL(k_deform_fwd_bf<false>, grid, dim3(64 * DF_FWD_WAVES), DF_FWD_BF_LDS, (hipStream_t)hip_stream, a);
-    } else {
-        if (saved) hipLaunchKernelGGL(k_deform_fwd<true>, grid, dim3(256), DF_FWD_LDS, (hipStream_t)hip_stream, a);
-        else hipLaunchKernelGGL(k_deform_fwd<false>, grid, dim3(256), DF_FWD_LDS, (hipStream_t)hip_stream, a);
     }
+    if (saved) hipLaunchKernelGGL(k_deform_fwd_bf<true>, grid, dim3(64 * DF_FWD_WAVES), DF_FWD_BF_LDS, (hipStream_t)hip_stream, a);
+    else hipLaunchKernelGGL(k_deform_fwd_bf<false>, grid, dim3(64 * DF_FWD_WAVES), DF_FWD_BF_LDS, (hipStream_t)hip_stream, a);
     GFT_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -2623,7 +2194,7 @@ static int deform_backward_impl(void* hip_stream, int xyz_multires, int t_multir
     const int splits = dw_splits(n_pad, &tps);
     float* rowmax = part + (int64_t)splits * DW_PART_FLOATS;
     uint32_t* xflag = reinterpret_cast<uint32_t*>(rowmax + n_pad * DF_D);
-    const bool h_planes = bf16_planes() && fp16_backward();
+    const bool h_planes = fp16_backward();
     {
         BwdArgs a;
         a.plan = plan;
@@ -2639,9 +2210,8 @@ static int deform_backward_impl(void* hip_stream, int xyz_multires, int t_multir
             GFT_CHECK_HIP(hipGetLastError());
             // the fp32-range walk behind it: its workgroups return at once unless a weight does not fit the fp16 planes
             a.only_if_wflag = 1;
-            hipLaunchKernelGGL(k_deform_bwd_bf, dim3((unsigned)(n_pad / 64)), dim3(64 * DF_BWD_WAVES), DF_BWD_BF_LDS, s, a);
-        } else if (bf16_planes()) hipLaunchKernelGGL(k_deform_bwd_bf, dim3((unsigned)(n_pad / 64)), dim3(64 * DF_BWD_WAVES), DF_BWD_BF_LDS, s, a);
-        else hipLaunchKernelGGL(k_deform_bwd, dim3((unsigned)(n_pad / (32 * DF_NR_BWD))), dim3(256), DF_BWD_LDS, s, a);
+        }
+        hipLaunchKernelGGL(k_deform_bwd_bf, dim3((unsigned)(n_pad / 64)), dim3(64 * DF_BWD_WAVES), DF_BWD_BF_LDS, s, a);
         GFT_CHECK_HIP(hipGetLastError());
     }
     {
@@ -2654,33 +2224,31 @@ static int deform_backward_impl(void* hip_stream, int xyz_multires, int t_multir
         a.part = part;
         a.first_block = 0;
         a.packed = (const float*)packed; a.rowmax = rowmax; a.xflag = xflag; a.only_if = 0;
-        if (bf16_planes()) {
-            // Two launches of the same kernel: the hidden-layer jobs (7 x splits workgroups, one wave per SIMD, 96 KB
-            // of LDS), then the light jobs (dW of layer 0, of the encoding rows of layer 5, of the heads), which need no
-            // LDS and get the CUs to themselves.  Measured at 300 k points: 1.21 + 0.29 ms back to back; with the
-            // light jobs on a side stream beside the heavy ones 1.53 ms (the two share the CUs' issue slots and the
-            // heavy waves' hand-placed schedule has no room for a guest), light first 1.54 ms.
-            static std::atomic<uint64_t> done{0};
-            GFT_CHECK_HIP(gft_lds_opt_in(reinterpret_cast<const void*>(&k_deform_dw_bf), DW_SH_LDS, done));
-            if (h_planes) {
-                // the hidden layers on two fp16 planes; the bf16 job behind it returns at once unless a weight or an
-                // activation did not fit them
-                static std::atomic<uint64_t> done_h2{0}, done_h3{0};
-                GFT_CHECK_HIP(gft_lds_opt_in(reinterpret_cast<const void*>(&k_deform_dw_h<2>), DW_H_LDS, done_h2));
-                GFT_CHECK_HIP(gft_lds_opt_in(reinterpret_cast<const void*>(&k_deform_dw_h<3>), DW_H_LDS, done_h3));
-                // (three steps of loads in flight where the grid is a round or two of workgroups: see dw_job_h_shared)
-                if (n_pad < 200000) hipLaunchKernelGGL(k_deform_dw_h<3>, dim3(7 * splits), dim3(256), DW_H_LDS, s, a);
-                else hipLaunchKernelGGL(k_deform_dw_h<2>, dim3(7 * splits), dim3(256), DW_H_LDS, s, a);
-                GFT_CHECK_HIP(hipGetLastError());
-                a.only_if = 1;
-            }
-            hipLaunchKernelGGL(k_deform_dw_bf, dim3(7 * splits), dim3(256), DW_SH_LDS, s, a);
+        // Two launches of the same kernel: the hidden-layer jobs (7 x splits workgroups, one wave per SIMD, 96 KB
+        // of LDS), then the light jobs (dW of layer 0, of the encoding rows of layer 5, of the heads), which need no
+        // LDS and get the CUs to themselves.  Measured at 300 k points: 1.21 + 0.29 ms back to back; with the
+        // light jobs on a side stream beside the heavy ones 1.53 ms (the two share the CUs' issue slots and the
+        // heavy waves' hand-placed schedule has no room for a guest), light first 1.54 ms.
+        static std::atomic<uint64_t> done{0};
+        GFT_CHECK_HIP(gft_lds_opt_in(reinterpret_cast<const void*>(&k_deform_dw_bf), DW_SH_LDS, done));
+        if (h_planes) {
+            // the hidden layers on two fp16 planes; the bf16 job behind it returns at once unless a weight or an
+            // activation did not fit them
+            static std::atomic<uint64_t> done_h2{0}, done_h3{0};
+            GFT_CHECK_HIP(gft_lds_opt_in(reinterpret_cast<const void*>(&k_deform_dw_h<2>), DW_H_LDS, done_h2));
+            GFT_CHECK_HIP(gft_lds_opt_in(reinterpret_cast<const void*>(&k_deform_dw_h<3>), DW_H_LDS, done_h3));
+            // (three steps of loads in flight where the grid is a round or two of workgroups: see dw_job_h_shared)
+            if (n_pad < 200000) hipLaunchKernelGGL(k_deform_dw_h<3>, dim3(7 * splits), dim3(256), DW_H_LDS, s, a);
+            else hipLaunchKernelGGL(k_deform_dw_h<2>, dim3(7 * splits), dim3(256), DW_H_LDS, s, a);
             GFT_CHECK_HIP(hipGetLastError());
-            a.only_if = 0;
-            DwArgs light = a;
-            light.first_block = 7 * splits;
-            hipLaunchKernelGGL(k_deform_dw_bf, dim3(3 * splits), dim3(256), 0, s, light);
-        } else hipLaunchKernelGGL(k_deform_dw, dim3(DW_JOBS * splits), dim3(256), 0, s, a);
+            a.only_if = 1;
+        }
+        hipLaunchKernelGGL(k_deform_dw_bf, dim3(7 * splits), dim3(256), DW_SH_LDS, s, a);
+        GFT_CHECK_HIP(hipGetLastError());
+        a.only_if = 0;
+        DwArgs light = a;
+        light.first_block = 7 * splits;
+        hipLaunchKernelGGL(k_deform_dw_bf, dim3(3 * splits), dim3(256), 0, s, light);
         GFT_CHECK_HIP(hipGetLastError());
     }
     {

@@ -16,8 +16,7 @@
  * operand is split exactly into three bf16 numbers (hi + mid + lo = 24 mantissa bits) and a product is the sum of
  * six `v_mfma_f32_32x32x16_bf16` terms (hi*hi, hi*mid, mid*hi, hi*lo, lo*hi, mid*mid; the three dropped terms are
  * below 2^-23 of the product), accumulated in fp32: the error against a float64 product is that of an fp32 fma
- * chain (measured 5.4e-7 vs 5.5e-7 of the max-norm), at up to 2.7 x the rate of the fp32-operand MFMA.
- * GFT_DEFORM_BF16X3=0 in the environment selects `v_mfma_f32_32x32x2_f32` (fp32 operands) instead.
+ * chain (measured 5.4e-7 vs 5.5e-7 of the max-norm).
  * The forward walk goes one step further: its operands are split into two fp16 numbers, x = hi + lo (hi = fp16(x),
  * lo = fp16(x - hi): 22 mantissa bits), and a product is three `v_mfma_f32_32x32x16_f16` terms (hi*hi, hi*lo, lo*hi;
  * lo*lo is below 2^-22 of the product and dropped) into one fp32 accumulator.  fp16 has five exponent bits, so weights
