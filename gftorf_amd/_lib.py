@@ -144,6 +144,7 @@ EXPORTS = [
     "gft_deform_inputs", "gft_deform_packed_bytes", "gft_deform_saved_bytes", "gft_deform_scratch_bytes", "gft_deform_pack",
     "gft_deform_forward", "gft_deform_backward", "gft_deform_compact", "gft_deform_rows_work_bytes", "gft_deform_backward_rows",
     "gft_ssim_blocks", "gft_ssim_l2_forward", "gft_ssim_l2_backward",
+    "gft_image_loss_forward", "gft_image_loss_backward", "gft_pixel_loss_blocks", "gft_pixel_loss_forward", "gft_pixel_loss_backward",
     "gft_densify_stats", "gft_rows_rank_scratch_bytes", "gft_rows_rank", "gft_rows_rank_dev", "gft_rows_gather", "gft_rows_any_nonzero",
 ]
 
@@ -232,6 +233,18 @@ def load():
     lib.gft_ssim_l2_backward.restype = C.c_int
     lib.gft_ssim_l2_backward.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_float),
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
+    _kind_sizes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]
+    lib.gft_image_loss_forward.restype = C.c_int
+    lib.gft_image_loss_forward.argtypes = _kind_sizes + [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
+    lib.gft_image_loss_backward.restype = C.c_int
+    lib.gft_image_loss_backward.argtypes = _kind_sizes + [C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                                          C.c_float, C.c_void_p]
+    lib.gft_pixel_loss_blocks.restype = C.c_int64
+    lib.gft_pixel_loss_blocks.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.gft_pixel_loss_forward.restype = C.c_int
+    lib.gft_pixel_loss_forward.argtypes = _kind_sizes + [C.c_float, C.c_void_p]
+    lib.gft_pixel_loss_backward.restype = C.c_int
+    lib.gft_pixel_loss_backward.argtypes = _kind_sizes + [C.c_void_p, C.c_float, C.c_void_p]
     lib.gft_densify_stats.restype = C.c_int
     lib.gft_densify_stats.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8
     lib.gft_rows_rank_scratch_bytes.restype = C.c_size_t
