@@ -147,6 +147,9 @@ EXPORTS = [
     "gft_image_loss_forward", "gft_image_loss_backward", "gft_pixel_loss_blocks", "gft_pixel_loss_forward", "gft_pixel_loss_backward",
     "gft_densify_stats", "gft_rows_rank_scratch_bytes", "gft_rows_rank", "gft_rows_rank_dev", "gft_rows_gather", "gft_rows_any_nonzero",
 ]
+# include/gftorf_flow.h (the scene-flow term; no struct, so the ABI version is unchanged)
+FLOW_EXPORTS = ["gft_flow_loss_blocks", "gft_flow_loss_forward", "gft_flow_loss_backward", "gft_flow_points", "gft_flow_project",
+                "gft_flow_project_backward"]
 
 
 def load():
@@ -245,6 +248,19 @@ def load():
     lib.gft_pixel_loss_forward.argtypes = _kind_sizes + [C.c_float, C.c_void_p]
     lib.gft_pixel_loss_backward.restype = C.c_int
     lib.gft_pixel_loss_backward.argtypes = _kind_sizes + [C.c_void_p, C.c_float, C.c_void_p]
+    _flow_cams = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5           # stream, H, W, depth, K, w2v, K_tof, w2v_tof
+    lib.gft_flow_loss_blocks.restype = C.c_int64
+    lib.gft_flow_loss_blocks.argtypes = [C.c_int32, C.c_int32]
+    lib.gft_flow_loss_forward.restype = C.c_int
+    lib.gft_flow_loss_forward.argtypes = _flow_cams + [C.c_void_p] * 4 + [C.c_float, C.c_void_p]
+    lib.gft_flow_loss_backward.restype = C.c_int
+    lib.gft_flow_loss_backward.argtypes = _flow_cams + [C.c_void_p] * 6 + [C.c_float, C.c_void_p, C.c_void_p]
+    lib.gft_flow_points.restype = C.c_int
+    lib.gft_flow_points.argtypes = _flow_cams + [C.c_void_p, C.c_void_p]
+    lib.gft_flow_project.restype = C.c_int
+    lib.gft_flow_project.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6
+    lib.gft_flow_project_backward.restype = C.c_int
+    lib.gft_flow_project_backward.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6
     lib.gft_densify_stats.restype = C.c_int
     lib.gft_densify_stats.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8
     lib.gft_rows_rank_scratch_bytes.restype = C.c_size_t

@@ -1,0 +1,180 @@
+"""The F-ToRF scene-flow term of the training loss as one launch forward and one backward (``csrc/k_flow.hip``,
+``include/gftorf_flow.h``): ``train.py:243-261`` unprojects the rendered distance (``scene/torf_utils.py``
+``distance_to_points3d``), projects it into the ToF camera (``project_points``), adds each rendered 3-D flow and projects
+again (``project_flow``), and takes the mean of the squared difference to the ground-truth 2-D flow.  In eager PyTorch that
+is ~100 small launches forward and backward, and its ``torch.inverse`` of the view matrix synchronises with the host.  Here
+every camera matrix is read on the device (the inverse is formed inside each launch), nothing is read back to the host and
+nothing issues a memset, so ``flow_loss`` and its backward can be captured in a graph.
+
+The reference's semantics are kept as they are: the unprojection uses the colour camera's intrinsics and inverts
+``world_view_transform`` as stored, the projection uses ``K_tof`` and ``world_view_transform_tof.T``, the divide is
+``xy / (z + 1e-7)``.  Gradients flow to the 3-D flows only (the reference detaches the depth; the ground truth and the
+cameras are data).  There is no CPU path.
+"""
+import torch
+
+from . import _lib
+
+
+def _check(items):
+    """items: (tensor, name, shape, grad_ok); a None in `shape` is any size.  Shapes and gradients are checked before
+    devices, then every tensor must be on the first one's HIP device.  Returns the tensors as float32, contiguous."""
+    for t, name, shape, grad_ok in items:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("gftorf_amd.flow: %s must be a tensor, got %s" % (name, type(t).__name__))
+        if t.dim() != len(shape) or any(w is not None and int(n) != w for n, w in zip(t.shape, shape)):
+            want = "[%s]" % ", ".join("HW"[i - 1] if w is None else str(w) for i, w in enumerate(shape))      # [C, H, W]
+            raise RuntimeError("gftorf_amd.flow: %s must be %s, got %s" % (name, want, list(t.shape)))
+        if t.requires_grad and not grad_ok:
+            raise NotImplementedError("gftorf_amd.flow: gradients flow to the 3-D flows only; %s requires grad (detach it, "
+                                      "as train.py detaches the depth)" % name)
+    device = items[0][0].device
+    for t, name, _, _ in items:
+        if t.device.type != "cuda":
+            raise RuntimeError("gftorf_amd.flow: %s is on %s; the flow kernels run on a HIP device only, there is no CPU path"
+                               % (name, t.device))
+        if t.device != device:
+            raise RuntimeError("gftorf_amd.flow: %s is on %s, %s on %s" % (name, t.device, items[0][1], device))
+    return [t if t.dtype == torch.float32 and t.is_contiguous() else t.float().contiguous() for t, _, _, _ in items]
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _hw(t):
+    return (int(t.shape[-2]), int(t.shape[-1])) if isinstance(t, torch.Tensor) and t.dim() >= 2 else (None, None)
+
+
+class _SceneFlowL2(torch.autograd.Function):
+    """(forward_flow_l2, backward_flow_l2): one launch + one column sum forward, one launch backward."""
+
+    @staticmethod
+    def forward(ctx, depth, K, w2v, K_tof, w2v_tof, f_fwd, gt_fwd, f_bwd, gt_bwd):
+        lib = _lib.load()
+        H, W = int(depth.shape[1]), int(depth.shape[2])
+        blocks = int(lib.gft_flow_loss_blocks(H, W))
+        partials = torch.empty((blocks, 2), device=depth.device, dtype=torch.float32)
+        scale = 1.0 / (2.0 * H * W)
+        with _lib.on_device(depth.device):
+            _lib.check(lib.gft_flow_loss_forward(_lib.raw_stream(depth.device), H, W, depth.data_ptr(), K.data_ptr(),
+                                                 w2v.data_ptr(), K_tof.data_ptr(), w2v_tof.data_ptr(), _ptr(f_fwd), _ptr(gt_fwd),
+                                                 _ptr(f_bwd), _ptr(gt_bwd), scale, partials.data_ptr()))
+        sums = partials.sum(0)
+        ctx.sizes = (H, W, scale)
+        ctx.save_for_backward(depth, K, w2v, K_tof, w2v_tof, f_fwd, gt_fwd, f_bwd, gt_bwd)
+        ctx.set_materialize_grads(False)
+        return sums[0], sums[1]
+
+    @staticmethod
+    def backward(ctx, g_fwd, g_bwd):
+        lib = _lib.load()
+        depth, K, w2v, K_tof, w2v_tof, f_fwd, gt_fwd, f_bwd, gt_bwd = ctx.saved_tensors
+        H, W, scale = ctx.sizes
+        grad_fwd = torch.empty_like(f_fwd) if f_fwd is not None and ctx.needs_input_grad[5] else None
+        grad_bwd = torch.empty_like(f_bwd) if f_bwd is not None and ctx.needs_input_grad[7] else None
+        if grad_fwd is None and grad_bwd is None:
+            return (None,) * 9
+        up = lambda g: None if g is None else g.detach().float()        # a 0-dim gradient: one float at data_ptr()
+        gf, gb = up(g_fwd), up(g_bwd)
+        with _lib.on_device(depth.device):
+            _lib.check(lib.gft_flow_loss_backward(_lib.raw_stream(depth.device), H, W, depth.data_ptr(), K.data_ptr(),
+                                                  w2v.data_ptr(), K_tof.data_ptr(), w2v_tof.data_ptr(), _ptr(f_fwd),
+                                                  _ptr(gt_fwd), _ptr(f_bwd), _ptr(gt_bwd), _ptr(gf), _ptr(gb), scale,
+                                                  _ptr(grad_fwd), _ptr(grad_bwd)))
+        return None, None, None, None, None, grad_fwd, None, grad_bwd, None
+
+
+def scene_flow_l2(depth, K, w2v, K_tof, w2v_tof, flow3d_fwd=None, gt_fwd=None, flow3d_bwd=None, gt_bwd=None):
+    """``(forward_flow_l2, backward_flow_l2)`` of ``train.py:243-259`` from tensors alone, two 0-dim tensors of one autograd
+    node: ``mean((project_flow(p2, p3, flow3d) - gt) ** 2)`` per direction, with ``p3 = distance_to_points3d(depth)`` and
+    ``p2 = project_points(p3)``.  ``depth`` [1, H, W] (the rendered distance; no gradient), ``K`` / ``K_tof`` [3, 3],
+    ``w2v`` / ``w2v_tof`` [4, 4] (the cameras' ``world_view_transform`` / ``world_view_transform_tof`` as stored),
+    ``flow3d_*`` [3, H, W] (gradients flow here), ``gt_*`` [2, H, W].  A direction without its flow3d or its gt is 0.
+    Nothing is read back to the host: with static tensors the call and its backward can be captured in a graph."""
+    H, W = _hw(depth)
+    items = [(depth, "depth", (1, None, None), False), (K, "K", (3, 3), False), (w2v, "world_view_transform", (4, 4), False),
+             (K_tof, "K_tof", (3, 3), False), (w2v_tof, "world_view_transform_tof", (4, 4), False)]
+    present = []
+    for name, f, gt in (("forward", flow3d_fwd, gt_fwd), ("backward", flow3d_bwd, gt_bwd)):
+        present.append(f is not None and gt is not None)
+        if present[-1]:
+            items += [(f, "flow3d_" + name, (3, H, W), True), (gt, "gt_" + name, (2, H, W), False)]
+    t = iter(_check(items))
+    d, cams = next(t), [next(t) for _ in range(4)]
+    dirs = []
+    for p in present:
+        dirs += [next(t), next(t)] if p else [None, None]
+    return _SceneFlowL2.apply(d, *cams, *dirs)
+
+
+def flow_loss(depth, cam, flow3d_forward=None, flow3d_backward=None):
+    """``(forward_flow_l2, backward_flow_l2)`` exactly as ``train.py:236-259`` builds them, from one autograd node: the
+    caller writes ``loss += opt.lambda_flow * (f + b)`` and can still log each term.  ``depth`` is
+    ``render_pkg["render_depth"].detach()``; ``cam`` anything with the reference ``ToFCamera``'s ``K``, ``K_tof``,
+    ``world_view_transform``, ``world_view_transform_tof``, ``forward_flow`` and ``backward_flow``; ``flow3d_*`` the
+    ``render_flow`` outputs.  A direction whose flow3d or ground truth is None gives 0."""
+    return scene_flow_l2(depth, cam.K, cam.world_view_transform, cam.K_tof, cam.world_view_transform_tof,
+                         flow3d_forward, getattr(cam, "forward_flow", None), flow3d_backward, getattr(cam, "backward_flow", None))
+
+
+def distance_to_points3d(distance_map, viewpoint_cam):
+    """Drop-in for ``scene.torf_utils.distance_to_points3d`` (no gradient to the distance)."""
+    d, K, w2v = _check([(distance_map, "distance_map", (1, None, None), False), (viewpoint_cam.K, "K", (3, 3), False),
+                        (viewpoint_cam.world_view_transform, "world_view_transform", (4, 4), False)])
+    dev, (H, W) = d.device, _hw(d)
+    out = torch.empty((3, H, W), device=dev, dtype=torch.float32)
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        _lib.check(lib.gft_flow_points(_lib.raw_stream(dev), H, W, d.data_ptr(), K.data_ptr(), w2v.data_ptr(), None, None,
+                                       out.data_ptr(), None))
+    return out
+
+
+def project_points(points3d, viewpoint_cam):
+    """Drop-in for ``scene.torf_utils.project_points`` (no gradient to the points)."""
+    p3, K_tof, w2v_tof = _check([(points3d, "points3d", (3, None, None), False), (viewpoint_cam.K_tof, "K_tof", (3, 3), False),
+                                 (viewpoint_cam.world_view_transform_tof, "world_view_transform_tof", (4, 4), False)])
+    dev, (H, W) = p3.device, _hw(p3)
+    out = torch.empty((2, H, W), device=dev, dtype=torch.float32)
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        _lib.check(lib.gft_flow_project(_lib.raw_stream(dev), H, W, K_tof.data_ptr(), w2v_tof.data_ptr(), p3.data_ptr(), None,
+                                        None, out.data_ptr()))
+    return out
+
+
+class _ProjectFlow(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p2, p3, flow3d, K_tof, w2v_tof):
+        lib = _lib.load()
+        H, W = int(p3.shape[1]), int(p3.shape[2])
+        out = torch.empty((2, H, W), device=p3.device, dtype=torch.float32)
+        with _lib.on_device(p3.device):
+            _lib.check(lib.gft_flow_project(_lib.raw_stream(p3.device), H, W, K_tof.data_ptr(), w2v_tof.data_ptr(),
+                                            p3.data_ptr(), flow3d.data_ptr(), p2.data_ptr(), out.data_ptr()))
+        ctx.save_for_backward(p3, flow3d, K_tof, w2v_tof)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        p3, flow3d, K_tof, w2v_tof = ctx.saved_tensors
+        H, W = int(p3.shape[1]), int(p3.shape[2])
+        g = g.detach().float().contiguous()
+        grad = torch.empty_like(flow3d)
+        with _lib.on_device(p3.device):
+            _lib.check(lib.gft_flow_project_backward(_lib.raw_stream(p3.device), H, W, K_tof.data_ptr(), w2v_tof.data_ptr(),
+                                                     p3.data_ptr(), flow3d.data_ptr(), g.data_ptr(), grad.data_ptr()))
+        return None, None, grad, None, None
+
+
+def project_flow(points2d_curr, points3d_curr, flow3d, viewpoint_cam):
+    """Drop-in for ``scene.torf_utils.project_flow``: ``project_points(points3d_curr + flow3d) - points2d_curr``,
+    differentiable with respect to ``flow3d`` (the current points are data, as in ``train.py``)."""
+    H, W = _hw(points3d_curr)
+    p3, p2, f, K_tof, w2v_tof = _check([(points3d_curr, "points3d_curr", (3, None, None), False),
+                                        (points2d_curr, "points2d_curr", (2, H, W), False), (flow3d, "flow3d", (3, H, W), True),
+                                        (viewpoint_cam.K_tof, "K_tof", (3, 3), False),
+                                        (viewpoint_cam.world_view_transform_tof, "world_view_transform_tof", (4, 4), False)])
+    return _ProjectFlow.apply(p2, p3, f, K_tof, w2v_tof)
