@@ -150,6 +150,8 @@ EXPORTS = [
 # include/gftorf_flow.h (the scene-flow term; no struct, so the ABI version is unchanged)
 FLOW_EXPORTS = ["gft_flow_loss_blocks", "gft_flow_loss_forward", "gft_flow_loss_backward", "gft_flow_points", "gft_flow_project",
                 "gft_flow_project_backward"]
+# include/gftorf_features.h (the feature blend over a drawn frame; no struct, so the ABI version is unchanged)
+FEATURE_EXPORTS = ["gft_render_features", "gft_render_features_backward"]
 
 
 def load():
@@ -261,6 +263,11 @@ def load():
     lib.gft_flow_project.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6
     lib.gft_flow_project_backward.restype = C.c_int
     lib.gft_flow_project_backward.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6
+    _feat_frame = [C.c_void_p, C.POINTER(Config)] + [C.c_void_p] * 3 + [C.c_int64, C.c_int32]   # stream, cfg, scratch, R, C
+    lib.gft_render_features.restype = C.c_int
+    lib.gft_render_features.argtypes = _feat_frame + [C.c_void_p] * 3
+    lib.gft_render_features_backward.restype = C.c_int
+    lib.gft_render_features_backward.argtypes = _feat_frame + [C.c_void_p] * 3
     lib.gft_densify_stats.restype = C.c_int
     lib.gft_densify_stats.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8
     lib.gft_rows_rank_scratch_bytes.restype = C.c_size_t

@@ -15,14 +15,16 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libgftorf_rast.so")
-SOURCES = ["gft_api.hip", "k_preprocess.hip", "k_binning.hip", "k_pull.hip", "k_render.hip", "k_assemble.hip", "k_knn.hip", "k_adam.hip", "k_deform.hip", "k_densify.hip", "k_loss.hip", "k_flow.hip"]
+SOURCES = ["gft_api.hip", "k_preprocess.hip", "k_binning.hip", "k_pull.hip", "k_render.hip", "k_assemble.hip", "k_knn.hip", "k_adam.hip", "k_deform.hip", "k_densify.hip", "k_loss.hip", "k_flow.hip", "k_features.hip"]
 ARCH = "gfx950"
 # The SLP vectoriser packs the render kernels' scalar fp32 maths into v_pk_* ops that need extra
 # v_mov to pair registers: measured +12 us per render kernel on the metric frame.
 # (k_preprocess.hip: the vectoriser pairs scalar multiplies of the appearance maths into v_pk_mul_f32 behind four register moves
 # each: preprocess_fwd stage 57.3 -> 54.7 us on the metric frame, 129 -> 126 fog, 132.6 -> 130.1 at 5 M @ 1080p without it)
 # (k_pull.hip: it compiles the forward blend's walk too -- gft_render_walk.h -- and must do so exactly as k_render.hip does)
-FILE_FLAGS = {"k_render.hip": ["-fno-slp-vectorize"], "k_preprocess.hip": ["-fno-slp-vectorize"], "k_pull.hip": ["-fno-slp-vectorize"]}
+# (k_features.hip: it recomputes the forward blend's alpha, and must compile that arithmetic as k_render.hip does)
+FILE_FLAGS = {"k_render.hip": ["-fno-slp-vectorize"], "k_preprocess.hip": ["-fno-slp-vectorize"], "k_pull.hip": ["-fno-slp-vectorize"],
+              "k_features.hip": ["-fno-slp-vectorize"]}
 
 
 def hipcc():

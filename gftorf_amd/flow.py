@@ -10,7 +10,15 @@ The reference's semantics are kept as they are: the unprojection uses the colour
 ``world_view_transform`` as stored, the projection uses ``K_tof`` and ``world_view_transform_tof.T``, the divide is
 ``xy / (z + 1e-7)``.  Gradients flow to the 3-D flows only (the reference detaches the depth; the ground truth and the
 cameras are data).  There is no CPU path.
+
+The two ``render_flow`` calls that feed the term (``gaussian_renderer/__init__.py:141-204``) draw the same detached geometry
+from the same ToF camera with two ``colors_precomp``: ``render_flow_pair`` / ``render_flows`` draw the frame once, blend the
+second flow over it (``csrc/k_features.hip``, ``include/gftorf_features.h``) and return the gradient of both flows from one
+walk over the frame, with no host read.
 """
+import ctypes as C
+import math
+
 import torch
 
 from . import _lib
@@ -178,3 +186,148 @@ def project_flow(points2d_curr, points3d_curr, flow3d, viewpoint_cam):
                                         (viewpoint_cam.K_tof, "K_tof", (3, 3), False),
                                         (viewpoint_cam.world_view_transform_tof, "world_view_transform_tof", (4, 4), False)])
     return _ProjectFlow.apply(p2, p3, f, K_tof, w2v_tof)
+
+
+# ---- the two scene-flow renders (gaussian_renderer/__init__.py render_flow, train.py:249,256) ---------------------------
+
+class _RenderFlows(torch.autograd.Function):
+    """One rasterizer forward with ``colors_precomp = flow_a`` (its image is what that call returns), the second flow blended
+    over the same frame by ``k_feat_fwd<3>``; backward: one ``k_feat_bwd`` over both images (``include/gftorf_features.h``)."""
+
+    @staticmethod
+    def forward(ctx, s, means3D, opacities, scales, rotations, flow_a, flow_b):
+        from . import api
+        lib = _lib.load()
+        dev = means3D.device
+        P = int(means3D.shape[0])
+        H, W = int(s.image_height), int(s.image_width)
+        r = api.native_forward(s, means3D, None, None, flow_a, None, opacities, scales, rotations, None, 0.0, 0.0, False, False,
+                               nowait=True)
+        bg_c, bsc, bsy, bsx = r["bg"]
+        cfg = api._make_config(s, P, 0, 0, H, W, 0.0, 0.0, (bsc, bsy, bsx), False)
+        geom, img, binning = r["geom"], r["img"], r["binning"]
+        frame = (geom.data_ptr(), img.data_ptr(), binning.data_ptr() if binning.numel() else None, int(r["cap"]))
+        image_b = None
+        if flow_b is not None:
+            image_b = torch.empty((3, H, W), device=dev, dtype=torch.float32)
+            with _lib.on_device(dev):
+                _lib.check(lib.gft_render_features(_lib.raw_stream(dev), C.byref(cfg), *frame, 3, flow_b.data_ptr(),
+                                                   bg_c.data_ptr(), image_b.data_ptr()))
+        ctx.frame = (cfg, frame)
+        ctx.save_for_backward(geom, img, binning)
+        ctx.set_materialize_grads(False)
+        return r["outputs"][0], image_b
+
+    @staticmethod
+    def backward(ctx, g_a, g_b):
+        lib = _lib.load()
+        geom = ctx.saved_tensors[0]
+        cfg, frame = ctx.frame
+        want = [g is not None and ctx.needs_input_grad[5 + k] for k, g in enumerate((g_a, g_b))]
+        if not any(want):
+            return (None,) * 7
+        # one walk serves both flows: their weights alpha_i T_i are the same
+        g = torch.cat((g_a, g_b)) if all(want) else (g_a if want[0] else g_b)
+        g = g.detach().float().contiguous()
+        n = int(g.shape[0])
+        dev = geom.device
+        acc = torch.empty((cfg.P, 8), device=dev, dtype=torch.float32)
+        grad = torch.empty((cfg.P, n), device=dev, dtype=torch.float32)
+        with _lib.on_device(dev):
+            _lib.check(lib.gft_render_features_backward(_lib.raw_stream(dev), C.byref(cfg), *frame, n, g.data_ptr(),
+                                                        acc.data_ptr(), grad.data_ptr()))
+        if all(want):
+            return None, None, None, None, None, grad[:, :3], grad[:, 3:]
+        return (None, None, None, None, None) + ((grad, None) if want[0] else (None, grad))
+
+
+def render_flows(raster_settings, means3D, opacities, scales, rotations, flow_a, flow_b=None):
+    """``(image_a, image_b)``: the ``[3, H, W]`` images ``GaussianRasterizer(raster_settings)(colors_precomp=flow_a)`` and
+    ``(colors_precomp=flow_b)`` return on the same geometry, from one rasterizer forward (``image_a`` is its colour output)
+    and one blend of ``flow_b`` over the frame it drew; ``image_b`` is None without ``flow_b``.  Gradients flow to the flows
+    only -- one walk over the frame for both -- so the geometry (``means3D`` [P, 3], ``opacities`` [P, 1], ``scales`` [P, 3],
+    ``rotations`` [P, 4]) must not require grad.  Nothing is read back to the host once a frame of the shape has been drawn:
+    the binning buffer is sized from earlier frames, as with ``api.no_host_read``, so with static
+    tensors the call and its backward can be captured in a graph.  The price is that contract's: a frame with more
+    instances than that buffer holds is not drawn -- both images are undefined and so are the gradients -- and the next call
+    of the shape raises (and enlarges the buffer) instead of re-rendering as ``GaussianRasterizer`` does."""
+    t = means3D if isinstance(means3D, torch.Tensor) else None
+    P = int(t.shape[0]) if t is not None and t.dim() == 2 else None
+    op_shape = (P, 1) if isinstance(opacities, torch.Tensor) and opacities.dim() == 2 else (P,)
+    items = [(means3D, "means3D", (P, 3), False), (opacities, "opacities", op_shape, False), (scales, "scales", (P, 3), False),
+             (rotations, "rotations", (P, 4), False), (flow_a, "flow_a", (P, 3), True)]
+    if flow_b is not None:
+        items.append((flow_b, "flow_b", (P, 3), True))
+    checked = _check(items)
+    return _RenderFlows.apply(raster_settings, *checked[:5], checked[5] if flow_b is not None else None)
+
+
+def _gather(t, rank):
+    """[P, k]: row rank[i] of t in every row i, clamped to t's rows (any index is in bounds).  A t of no rows -- a model
+    without a dynamic Gaussian -- gives zeros, still connected to t so that its gradient is the empty one the reference's
+    empty masked assignment gives."""
+    rows = int(t.shape[0])
+    if rows == 0:
+        return t.sum(0, keepdim=True).expand(int(rank.shape[0]), *t.shape[1:])
+    return torch.index_select(t, 0, rank.clamp(0, rows - 1))
+
+
+def _assemble_flow_inputs(pc, d_xyz, d_rot, flows, render_regions):
+    """render_flow's masked assignments (gaussian_renderer/__init__.py:165-185) on the device, without their host reads: the
+    detached geometry and each flow [N_dynamic, 3] in its dynamic rows, with the same values bit for bit -- the dynamic rows'
+    arithmetic (xyz + d_xyz, rotation_activation(_rotation + d_rot)) runs on the same operands, only the copies are
+    gathers.  Row k of a d_* tensor belongs to the k-th True of the motion mask; the row counts are not checked against the
+    mask (the reference's assignment raises on a mismatch, which takes a host read)."""
+    mask = pc.get_motion_mask
+    P = int(mask.shape[0])
+    st, dy = "static" in render_regions, "dynamic" in render_regions
+    m = mask[:, None]
+    rank = torch.cumsum(mask, 0) - 1
+    pick = lambda s, d: torch.where(m, d if dy else 0.0, s if st else 0.0)
+    dyn = lambda t: _gather(t, rank) if isinstance(t, torch.Tensor) else t
+    with torch.no_grad():
+        xyz = pc.get_xyz
+        means3D = pick(xyz, xyz + dyn(d_xyz))
+        opacity = pick(pc.get_opacity, pc.get_opacity)
+        scales = pick(pc.get_scaling, pc.get_scaling)
+        if isinstance(d_rot, torch.Tensor):
+            # the dynamic rows' positions, so that rotation_activation sees the [N_dynamic, 4] rows the reference gives it
+            n = int(d_rot.shape[0])
+            pos = torch.zeros((n + 1,), device=mask.device, dtype=torch.int64)
+            pos.scatter_(0, torch.where(mask, rank.clamp(max=n), n), torch.arange(P, device=mask.device))
+            rot_dyn = dyn(pc.rotation_activation(torch.index_select(pc._rotation, 0, pos[:n]) + d_rot))
+        else:
+            rot_dyn = pc.rotation_activation(pc._rotation + d_rot)
+        rotations = pick(pc.get_rotation, rot_dyn)
+    full = [torch.where(m, dyn(f.float()), 0.0) if dy else torch.zeros((P, 3), device=mask.device) for f in flows]
+    return means3D, opacity, scales, rotations, full
+
+
+def render_flow_pair(viewpoint_cam, pc, d_xyz, d_rot, flow3d_forward, flow3d_backward, bg_color,
+                     render_regions=("static", "dynamic")):
+    """Drop-in for the two ``render_flow`` calls of an ftorf flow iteration (``gaussian_renderer/__init__.py:141-204``,
+    ``train.py:249,256``): ``(forward_image, backward_image)``, each what ``render_flow(viewpoint_cam, pc, d_xyz, d_rot,
+    flow3d, bg_color, render_regions)["render_flow"]`` returns for that flow, or None where the flow is None.  The ToF
+    camera's settings are built as there, the detached geometry is assembled on the device with render_flow's values bit for
+    bit, each flow ``[N_dynamic, 3]`` goes to its dynamic rows and its gradient comes back from them on the device: no host
+    read (a ``depth_range`` held in device memory is the one exception, as in the reference), and the call can be captured.
+    A model without dynamic Gaussians (``[0, k]`` deformations and flows) gives zero flow images, as the reference does.
+    The binning buffer is sized from earlier frames of the shape, with :func:`render_flows`' consequence: a frame that
+    outgrows it gives undefined images and the next call raises."""
+    from .api import GaussianRasterizationSettings
+    flows = [f for f in (flow3d_forward, flow3d_backward) if f is not None]
+    if not flows:
+        return None, None
+    dr = viewpoint_cam.depth_range
+    settings = GaussianRasterizationSettings(
+        image_height=int(viewpoint_cam.tof_image_height), image_width=int(viewpoint_cam.tof_image_width),
+        tanfovx=math.tan(viewpoint_cam.FoVx_tof * 0.5), tanfovy=math.tan(viewpoint_cam.FoVy_tof * 0.5), bg=bg_color,
+        scale_modifier=1.0, viewmatrix=viewpoint_cam.world_view_transform_tof, projmatrix=viewpoint_cam.full_proj_transform_tof,
+        sh_degree=pc.active_sh_degree, campos=viewpoint_cam.camera_center_tof, prefiltered=False, debug=False,
+        near_n=viewpoint_cam.znear, far_n=viewpoint_cam.zfar, depth_range=float(dr.item() if isinstance(dr, torch.Tensor) else dr),
+        use_view_dependent_phase=pc.use_view_dependent_phase, optimize_phase_offset=False, optimize_dc_offset=False)
+    means3D, opacity, scales, rotations, full = _assemble_flow_inputs(pc, d_xyz, d_rot, flows, render_regions)
+    image_a, image_b = render_flows(settings, means3D, opacity, scales, rotations, *full)
+    if flow3d_forward is None:
+        return None, image_a
+    return image_a, image_b
