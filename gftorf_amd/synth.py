@@ -27,6 +27,25 @@ def projection_matrix(znear, zfar, fovx, fovy):
     return P
 
 
+def projection_matrix_shift(znear, zfar, fx, fy, cx, cy, W, H, fovx, fovy):
+    """utils/graphics_utils.py:77-109 restated: the symmetric window of ``projection_matrix`` moved on the near plane by
+    the principal point's offset from the image centre, ``(cx - W / 2) / fx * znear`` (and the same in y)."""
+    t = math.tan(fovy / 2) * znear
+    r = math.tan(fovx / 2) * znear
+    ox = (cx - W / 2) / fx * znear
+    oy = (cy - H / 2) / fy * znear
+    left, right, bottom, top = ox - r, ox + r, oy - t, oy + t
+    P = np.zeros((4, 4), np.float32)
+    P[0, 0] = 2.0 * znear / (right - left)
+    P[1, 1] = 2.0 * znear / (top - bottom)
+    P[0, 2] = (right + left) / (right - left)
+    P[1, 2] = (top + bottom) / (top - bottom)
+    P[3, 2] = 1.0
+    P[2, 2] = zfar / (zfar - znear)
+    P[2, 3] = -(zfar * znear) / (zfar - znear)
+    return P
+
+
 def look_at_w2c(yaw=0.0, pitch=0.0, roll=0.0, t=(0.0, 0.0, 0.0)):
     """World-to-camera 4x4 (math convention) from Euler angles + translation."""
     cy, sy = math.cos(yaw), math.sin(yaw)
@@ -58,6 +77,25 @@ def make_camera(W, H, fovx_deg=60.0, znear=0.45, zfar=6.05, w2c=None):
     return dict(viewmatrix=view_t, projmatrix=full_t, campos=campos,
                 tanfovx=tanfovx, tanfovy=tanfovy, znear=znear, zfar=zfar,
                 image_width=W, image_height=H, w2c=w2c)
+
+
+def make_sensor_camera(W, H, fx, fy, cx, cy, znear=0.45, zfar=6.05, w2c=None):
+    """The camera the reference trains through: its own focal lengths and principal point in pixels
+    (scene/dataset_readers.py:360-375), ``tanfov = size / (2 focal)`` (dataset_readers.py:362-363) and the shifted
+    projection (scene/cameras.py:122-140).  Same dict as ``make_camera``, plus the intrinsics."""
+    tanfovx = W / (2.0 * fx)
+    tanfovy = H / (2.0 * fy)
+    fovx = 2 * math.atan(tanfovx)
+    fovy = 2 * math.atan(tanfovy)
+    if w2c is None:
+        w2c = np.eye(4, dtype=np.float32)
+    Pm = projection_matrix_shift(znear, zfar, fx, fy, cx, cy, W, H, fovx, fovy)
+    view_t = np.ascontiguousarray(w2c.T.astype(np.float32))           # world_view_transform
+    full_t = np.ascontiguousarray((view_t @ Pm.T).astype(np.float32))  # full_proj_transform
+    campos = np.linalg.inv(w2c.astype(np.float64))[:3, 3].astype(np.float32)
+    return dict(viewmatrix=view_t, projmatrix=full_t, campos=campos,
+                tanfovx=tanfovx, tanfovy=tanfovy, znear=znear, zfar=zfar,
+                image_width=W, image_height=H, w2c=w2c, fx=fx, fy=fy, cx=cx, cy=cy)
 
 
 def make_gaussians(P, cam, seed, sh_coeffs=16, scale_lo=0.002, scale_hi=0.02,

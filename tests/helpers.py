@@ -8,11 +8,51 @@ from gftorf_amd import synth
 GRAD_KEYS = ["color", "phasor", "depth", "acc", "depth_distortion"]
 
 
+# Sensor cameras (the reference hands every colour and ToF camera its own fx, fy, cx, cy: scene/dataset_readers.py:360-375,
+# and builds the projection with getProjectionMatrixShift: scene/cameras.py:122-140).  Focal lengths as fractions of
+# f0 = W / (2 tan 30 deg) (the centred camera's) or, where `of_size` is set, of the image size; the principal point as a
+# fraction of the image size: one entry works at every image size.  `z`: the depth range its scenes use when the caller
+# names none.
+CAMERAS = {
+    # tests/golden/camera.npz's shift_args: 320 x 240, fx 260, fy 262, cx 155.5, cy 118.25
+    "sensor": dict(fx=260.0 / 320.0, fy=262.0 / 240.0, of_size=True, cx=155.5 / 320.0, cy=118.25 / 240.0),
+    "shift_right": dict(fx=1.0, fy=1.0, cx=0.72, cy=0.5),
+    "shift_corner": dict(fx=1.0, fy=1.0, cx=0.25, cy=0.78),
+    "anisotropic": dict(fx=1.3, fy=0.8, cx=0.55, cy=0.45),
+    "tele": dict(fx=4.0, fy=4.0, cx=0.5, cy=0.6),
+    "wide": dict(fx=0.45, fy=0.45, cx=0.4, cy=0.5),
+    # ToFCamera's own defaults (scene/cameras.py): near 0.01, far 100, depth_range 100
+    "default_planes": dict(fx=1.0, fy=1.0, cx=0.52, cy=0.48, znear=0.01, zfar=100.0, depth_range=100.0, z=(0.02, 90.0)),
+}
+
+
+def sensor_camera(camera, W, H, w2c=None):
+    """synth.make_sensor_camera of an entry of CAMERAS (by name, or a dict of the same form) at the image size W x H."""
+    e = CAMERAS[camera] if isinstance(camera, str) else camera
+    f0 = W / (2.0 * np.tan(np.radians(30.0)))
+    fx = e["fx"] * (W if e.get("of_size") else f0)
+    fy = e["fy"] * (H if e.get("of_size") else f0)
+    return synth.make_sensor_camera(W, H, float(fx), float(fy), e["cx"] * W, e["cy"] * H, znear=e.get("znear", 0.45),
+                                    zfar=e.get("zfar", 6.05), w2c=w2c)
+
+
 def small_scene(P=400, W=80, H=48, seed=3, D=3, sh_coeffs=16, scale_lo=0.01, scale_hi=0.12,
-                w2c="tilted", spread=1.05, tof=True, opacity=None, z_lo=1.0, z_hi=5.5):
+                w2c="tilted", spread=1.05, tof=True, opacity=None, z_lo=None, z_hi=None, camera=None, depth_range=10.0):
+    """camera: None (synth.make_camera, the centred 60 degree one), a name from CAMERAS or a dict of that form; the
+    Gaussians are placed in that camera's frustum, and the entry's depth_range, where it has one, replaces the argument.
+    z_lo / z_hi default to 1.0 / 5.5, or to the camera entry's `z`."""
     if isinstance(w2c, str):
         w2c = synth.look_at_w2c(0.15, -0.1, 0.05, (0.1, -0.05, 0.2)) if w2c == "tilted" else None
-    cam = synth.make_camera(W, H, w2c=w2c)
+    zr = (1.0, 5.5)
+    if camera is None:
+        cam = synth.make_camera(W, H, w2c=w2c)
+    else:
+        e = CAMERAS[camera] if isinstance(camera, str) else camera
+        cam = sensor_camera(e, W, H, w2c=w2c)
+        depth_range = e.get("depth_range", depth_range)
+        zr = e.get("z", zr)
+    z_lo = zr[0] if z_lo is None else z_lo
+    z_hi = zr[1] if z_hi is None else z_hi
     g = synth.make_gaussians(P, cam, seed, sh_coeffs=sh_coeffs, scale_lo=scale_lo, scale_hi=scale_hi,
                              spread=spread, z_lo=z_lo, z_hi=z_hi)
     if not tof:
@@ -21,7 +61,90 @@ def small_scene(P=400, W=80, H=48, seed=3, D=3, sh_coeffs=16, scale_lo=0.01, sca
         g["opacities"] = np.full_like(g["opacities"], opacity)
     return dict(cfg=dict(P=P, W=W, H=H, D=D, sh_coeffs=sh_coeffs, tof=tof), cam=cam, gaussians=g,
                 bg=synth.make_background(W, H, seed), grads=synth.make_pixel_grads(W, H, seed),
-                depth_range=10.0, phase_offset=0.1, dc_offset=0.05, use_view_dependent_phase=True)
+                depth_range=depth_range, phase_offset=0.1, dc_offset=0.05, use_view_dependent_phase=True)
+
+
+PLANES = {"bench": (0.45, 6.05, 10.0), "tof_default": (0.01, 100.0, 100.0)}      # near, far, depth_range
+
+
+def plane_edge_scene(znear, zfar, depth_range, W=48, H=32, per_depth=4):
+    """Gaussians at `near`, `far` and the floats next to each on both sides, under the identity pose, where the view-space
+    z is the world z exactly.  The reference culls with `<` and `>` (auxiliary.h:169): one exactly on a plane is kept.
+    Returns (scene, kept): kept[i] says whether Gaussian i lies on or between the planes."""
+    zn, zf, inf = np.float32(znear), np.float32(zfar), np.float32(np.inf)
+    depths = [np.nextafter(zn, -inf), zn, np.nextafter(zn, inf), np.nextafter(zf, -inf), zf, np.nextafter(zf, inf)]
+    inside = [False, True, True, True, True, False]
+    P = len(depths) * per_depth
+    sc = small_scene(P=P, W=W, H=H, w2c=None, depth_range=depth_range)
+    cam = synth.make_camera(W, H, znear=znear, zfar=zfar)
+    z = np.repeat(np.array(depths, np.float32), per_depth)
+    rng = np.random.default_rng(77)
+    u, v = rng.uniform(-0.7, 0.7, P), rng.uniform(-0.7, 0.7, P)
+    g = dict(sc["gaussians"])
+    g["means3D"] = np.stack([u * z * cam["tanfovx"], v * z * cam["tanfovy"], z], 1).astype(np.float32)
+    g["means3D"][:, 2] = z
+    g["scales"] = (g["scales"] * (z[:, None] / np.float32(3.0))).astype(np.float32)     # the same size on screen at every depth
+    g["opacities"] = np.full_like(g["opacities"], 0.5)
+    return dict(sc, cam=cam, gaussians=g), np.repeat(np.array(inside), per_depth)
+
+
+def translated_pair(dx, dy, camera="anisotropic", **kw):
+    """Two scenes of the same Gaussians and pose whose principal points differ by (dx, dy) pixels: the second image is the first
+    one moved by (dx, dy).  With dx, dy multiples of the 16 pixel tile every tile-relative quantity moves with it.  Zero
+    background; the upstream gradients are zero outside the overlap and translated inside it."""
+    a = small_scene(camera=camera, **kw)
+    W, H = a["cfg"]["W"], a["cfg"]["H"]
+    e = dict(CAMERAS[camera] if isinstance(camera, str) else camera)
+    e["cx"], e["cy"] = e["cx"] + dx / W, e["cy"] + dy / H
+    cam_b = sensor_camera(e, W, H, w2c=a["cam"]["w2c"])
+    a["bg"] = np.zeros_like(a["bg"])
+    ga, gb = {}, {}
+    for k, v in a["grads"].items():
+        ga[k], gb[k] = np.zeros_like(v), np.zeros_like(v)
+        va, vb = overlap(ga[k], gb[k], dx, dy)
+        src, _ = overlap(v, v, dx, dy)
+        va[...] = src
+        vb[...] = src
+    a["grads"] = ga
+    return a, dict(a, cam=cam_b, grads=gb)
+
+
+def overlap(img_a, img_b, dx, dy):
+    """Views of the pixels that both images of translated_pair see: img_b[..., y + dy, x + dx] is img_a[..., y, x]."""
+    H, W = img_a.shape[-2:]
+    x0, x1, y0, y1 = max(0, -dx), min(W, W - dx), max(0, -dy), min(H, H - dy)
+    return img_a[..., y0:y1, x0:x1], img_b[..., y0 + dy:y1 + dy, x0 + dx:x1 + dx]
+
+
+def rect_inside_both(means2D, radii, W, H, dx, dy, margin=1.0):
+    """Gaussians (of the first scene of translated_pair) whose square of `radii` pixels lies inside both images, with a
+    margin: their tile rectangle is clipped by neither image."""
+    r = radii.astype(np.float64)
+    ok = radii > 0
+    for lo, hi, d, size in ((means2D[:, 0] - r, means2D[:, 0] + r, dx, W), (means2D[:, 1] - r, means2D[:, 1] + r, dy, H)):
+        ok &= (lo >= margin) & (hi <= size - 1 - margin) & (lo + d >= margin) & (hi + d <= size - 1 - margin)
+    return ok
+
+
+TRANSLATED = {
+    # scenes of the whole-tile translation property (translated_pair).  spread 1.6: the Gaussians cover both images
+    "base": dict(P=600, W=96, H=64, spread=1.6),
+    "opaque": dict(P=3000, W=96, H=64, spread=1.6, scale_lo=0.03, scale_hi=0.2, opacity=0.9, seed=7),
+    "small_sensor": dict(P=1500, W=80, H=48, spread=1.6, scale_lo=0.005, scale_hi=0.06, seed=11, camera="sensor"),
+}
+
+
+def beyond_the_clamp_on_screen(scene, f):
+    """Gaussians that are blended (`radii > 0`, `pixels > 0`), whose centre lies inside the image and whose view-space
+    t.x / t.z or t.y / t.z is beyond computeCov2D's 1.3 tanfov clamp (forward.cu computeCov2D: their Jacobian is taken at
+    the clamped point and x_grad_mul / y_grad_mul = 0).  Only a principal point away from the centre has any."""
+    cam, cfg = scene["cam"], scene["cfg"]
+    m = scene["gaussians"]["means3D"].astype(np.float64)
+    t = np.concatenate([m, np.ones((m.shape[0], 1))], 1) @ cam["viewmatrix"].astype(np.float64)
+    beyond = (np.abs(t[:, 0] / t[:, 2]) > 1.3 * cam["tanfovx"]) | (np.abs(t[:, 1] / t[:, 2]) > 1.3 * cam["tanfovy"])
+    m2 = f.geom["means2D"]
+    inside = (m2[:, 0] >= 0) & (m2[:, 0] <= cfg["W"] - 1) & (m2[:, 1] >= 0) & (m2[:, 1] <= cfg["H"] - 1)
+    return (f.radii > 0) & (f.pixels.reshape(-1) > 0) & inside & beyond
 
 
 def oracle_kwargs(scene, **over):
@@ -65,6 +188,11 @@ def gpu_settings(scene, dev, bg=None, debug=False, optimize_offsets=False, **ove
               optimize_phase_offset=optimize_offsets, optimize_dc_offset=optimize_offsets)
     kw.update(over)
     return GaussianRasterizationSettings(**kw)
+
+
+def gpu_rasterizer(scene, dev, **over):
+    from gftorf_amd import GaussianRasterizer
+    return GaussianRasterizer(raster_settings=gpu_settings(scene, dev, **over))
 
 
 OUT_NAMES = ["color", "phasor", "depth", "normal", "acc", "entropy", "depth_distortion",

@@ -16,7 +16,7 @@ import helpers as Hh
 
 def draw_case(rng):
     D, M = [(0, 16), (1, 16), (2, 16), (3, 16), (1, 4), (2, 9), (0, 1)][int(rng.integers(7))]
-    return dict(
+    case = dict(
         P=int(rng.choice([1, 7, 64, 300, 1200, 5000, 20000])),
         # (at least 2000 pixels: the tests allow 1e-3 of an image's elements to sit on a blend edge, and one pixel of a smaller
         # image is already more than that)
@@ -31,10 +31,16 @@ def draw_case(rng):
         grads=["fresh", "kept", "kept_full"][int(rng.integers(3))],
         dlpack=bool(rng.random() < 0.25),
         acc_kept=bool(rng.random() < 0.7))
+    # the camera (None: the centred one; or a sensor camera of helpers.CAMERAS), from a generator of its own: the sequence
+    # of cases is the same with and without it
+    names = [None] + list(Hh.CAMERAS)
+    case["camera"] = names[int(np.random.default_rng(case["seed"]).integers(len(names)))]
+    return case
 
 
-def run_case(case, dev, oracle, rng):
+def run_case(case, dev, oracle, rng, cameras=False):
     """One frame through the oracle and through the public API in the case's modes; raises AssertionError on a mismatch.
+    cameras: render through the case's camera (otherwise through the centred one, whatever the case names).
     Returns (pixel counts beyond the tests' band, frames with any pixel-count difference)."""
     import test_gpu_parity as T
     from gftorf_amd import _lib, api
@@ -42,7 +48,8 @@ def run_case(case, dev, oracle, rng):
     c = case
     P = c["P"]
     scene = Hh.small_scene(P=P, W=c["W"], H=c["H"], seed=c["seed"], D=c["D"], sh_coeffs=c["M"], scale_lo=0.01, scale_hi=c["scale_hi"],
-                           tof=c["tof"], opacity=c["opacity"], w2c="tilted" if c["tilted"] else None)
+                           tof=c["tof"], opacity=c["opacity"], w2c="tilted" if c["tilted"] else None,
+                           camera=c.get("camera") if cameras else None)
     keep = (api._TILE_HINTS, api._GRADS_REUSE, api._USE_COUNT_API, api._ACC_REUSE)
     keep_cam, api._TILE_HINTS_PER_CAMERA = api._TILE_HINTS_PER_CAMERA, False      # (a frame's camera tensors are new every case)
     # (the build of the pull kernel that honours the schedule, whenever the case hands one over; "keep": the operator's choice)
@@ -92,10 +99,12 @@ def run_case(case, dev, oracle, rng):
                 for e in pool:
                     e["dense_left"] = 2                 # the next backwards into these tensors write them in full
         f, b = Hh.run_oracle(oracle, scene)
+        # (planes under which the oracle's own depth_distortion sums cancel: that plane against float64, as the parity tests do)
+        dd_ref = T.float64_depth_distortion(scene, f) if T.needs_float64_depth_distortion(scene) else None
         if c["hints"] == "keep":
             # the schedule as the operator builds it: the frame once more, on the words its first rendering left
             out, grads, _ = Hh.run_gpu(scene, dev, optimize_offsets=c["tof"])
-            T.check_outputs(f, out) if not (out["pixels"] != f.pixels).any() else None
+            T.check_outputs(f, out, dd_ref=dd_ref) if not (out["pixels"] != f.pixels).any() else None
             del out, grads
         out, grads, _ = Hh.run_gpu(scene, dev, optimize_offsets=c["tof"])
         # the first-hit plane is not continuous in alpha: a pixel whose FIRST layer sits on the 1/255 edge shows another layer's
@@ -107,7 +116,7 @@ def run_case(case, dev, oracle, rng):
             if 0 < int(first_hit.sum()) <= n_pairs:
                 out["distribution"] = np.where(first_hit[None], f["distribution"], out["distribution"]).astype(out["distribution"].dtype)
         try:
-            T.check_outputs(f, out)
+            T.check_outputs(f, out, dd_ref=dd_ref)
         except AssertionError as e:
             # a pixel whose alpha sits on the 1/255 or T = 1e-4 edge may count for one more / one fewer Gaussian: with a few
             # hundred Gaussians one such Gaussian is already more than the tests' 2e-3 of them
@@ -153,18 +162,18 @@ def run_case(case, dev, oracle, rng):
     return edge_flips, flip_cases
 
 
-def run(dev, oracle, seed=77, cases=None, seconds=None):
+def run(dev, oracle, seed=77, cases=None, seconds=None, cameras=False):
     """Frames until `cases` are done or `seconds` have passed.  Returns the record; raises on the first mismatch with the
-    case in the message."""
+    case in the message.  cameras: every case through the camera it names (run_case)."""
     from gftorf_amd import api
     rng = np.random.default_rng(seed)
     t0 = time.time()
     n = edge = flips = deepest = 0
-    kinds = {}
+    kinds, by_camera = {}, {}
     while (cases is None or n < cases) and (seconds is None or time.time() - t0 < seconds):
         case = draw_case(rng)
         try:
-            e, fl = run_case(case, dev, oracle, rng)
+            e, fl = run_case(case, dev, oracle, rng, cameras=cameras)
         except AssertionError as ex:
             raise AssertionError("soak case %d failed: %s\ncase: %s" % (n, str(ex)[:400], json.dumps(case))) from ex
         edge += e
@@ -173,8 +182,10 @@ def run(dev, oracle, seed=77, cases=None, seconds=None):
         k = "bin%d_render%d_hints-%s_grads-%s%s%s" % (case["bin_mode"], case["render_mode"], case["hints"], case["grads"],
                                                      "_dlpack" if case["dlpack"] else "", "" if case["acc_kept"] else "_acc-cleared")
         kinds[k] = kinds.get(k, 0) + 1
+        if cameras:
+            by_camera[str(case["camera"])] = by_camera.get(str(case["camera"]), 0) + 1
         deepest = max(deepest, int(api.last_call_stats.get("max_tile_list", 0)))
-    return {"seconds": round(time.time() - t0, 1), "cases": n, "modes_met": len(kinds), "by_mode": kinds, "deepest_tile_list": deepest,
+    return {"seconds": round(time.time() - t0, 1), "cases": n, "modes_met": len(kinds), "by_mode": kinds, "by_camera": by_camera, "deepest_tile_list": deepest,
             "cases_beyond_the_tests_pixel_count_band": edge,
             "cases_with_a_pixel_count_difference (those Gaussians' gradient rows left out, 1e-2 for the frame's other rows)": flips,
             "checks": "tests/test_gpu_parity.py::check_outputs / check_grads (images L1 and max-norm, radii bit-exact, pixels, every gradient)"}

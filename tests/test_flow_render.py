@@ -193,6 +193,8 @@ CASES = {
     "culled": (dict(P=3000, W=96, H=64, seed=9, z_lo=-1.0), 7, False),
     "deep": (dict(P=30000, W=64, H=48, seed=13, opacity=0.01, scale_lo=0.02, scale_hi=0.08), 0, True),
     "ftorf": (dict(P=100_000, W=320, H=240, seed=21, scale_lo=0.004, scale_hi=0.03, opacity=0.1), 0, True),
+    # a sensor camera of helpers.CAMERAS: the principal point at 0.72 W
+    "sensor": (dict(P=3000, W=96, H=64, seed=9, camera="shift_right"), 7, False),
 }
 
 
@@ -309,8 +311,9 @@ def _tof_cam(scene, dev, gt=None):
     cam = scene["cam"]
     W, H = scene["cfg"]["W"], scene["cfg"]["H"]
     t = lambda a: torch.tensor(np.asarray(a), dtype=torch.float32, device=dev)
-    fx = W / (2 * cam["tanfovx"])
-    K = t([[fx, 0, W / 2], [0, fx, H / 2], [0, 0, 1]])
+    # the scene's own intrinsics (a sensor camera of helpers.CAMERAS), or the centred camera's
+    fx = cam.get("fx", W / (2 * cam["tanfovx"]))
+    K = t([[fx, 0, cam.get("cx", W / 2)], [0, cam.get("fy", fx), cam.get("cy", H / 2)], [0, 0, 1]])
     return types.SimpleNamespace(tof_image_height=H, tof_image_width=W, FoVx_tof=2 * math.atan(cam["tanfovx"]),
                                  FoVy_tof=2 * math.atan(cam["tanfovy"]), world_view_transform_tof=t(cam["viewmatrix"]),
                                  full_proj_transform_tof=t(cam["projmatrix"]), camera_center_tof=t(cam["campos"]),
@@ -381,8 +384,19 @@ def _flow_iteration(cam, pc, d, bg, fused, with_loss, depth=None):
 @pytest.mark.gpu
 @pytest.mark.parametrize("with_loss", [False, True])
 def test_render_flow_pair_is_a_drop_in(with_loss, gpu):
+    _drop_in(with_loss, None, gpu)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("with_loss", [False, True])
+def test_render_flow_pair_is_a_drop_in_through_a_sensor_camera(with_loss, gpu):
+    """... with K / K_tof from the camera's own fx, fy, cx, cy (helpers.CAMERAS `sensor`)."""
+    _drop_in(with_loss, "sensor", gpu)
+
+
+def _drop_in(with_loss, camera, gpu):
     W, H = 320, 240
-    scene = Hh.small_scene(P=20_000, W=W, H=H, seed=47, scale_lo=0.004, scale_hi=0.03, opacity=0.3)
+    scene = Hh.small_scene(P=20_000, W=W, H=H, seed=47, scale_lo=0.004, scale_hi=0.03, opacity=0.3, camera=camera)
     pc = _pc(scene, gpu)
     gen = torch.Generator().manual_seed(3)
     gt = [(2.0 * torch.randn((2, H, W), generator=gen)).to(gpu) for _ in range(2)]

@@ -140,6 +140,43 @@ SCENES = {
 }
 
 
+# The same scenes through the sensor cameras of helpers.CAMERAS ("scene@camera"): principal point off the centre (means2D from
+# projmatrix, the cov2D Jacobian and its clamp from tanfov), fx != fy, narrow and wide fields of view, and the ToF camera's
+# own planes 0.01 / 100 with depth_range 100 (k_pull derives its 4096 depth bins -- near_bits, bin_shift -- from the planes).
+for _cam in Hh.CAMERAS:
+    SCENES["base@" + _cam] = dict(camera=_cam)
+for _cam in ("sensor", "shift_right", "anisotropic", "wide"):
+    SCENES["odd_size@" + _cam] = dict(SCENES["odd_size"], camera=_cam)
+    SCENES["deep_lists@" + _cam] = dict(SCENES["deep_lists"], camera=_cam)
+for _cam in ("shift_right", "shift_corner"):
+    # Gaussians inside the image beyond the 1.3 tanfov clamp (x_grad_mul = 0 for a visible, blended Gaussian)
+    SCENES["wide_spread@" + _cam] = dict(spread=1.8, P=500, camera=_cam)
+for _name in ("deep_lists", "long_lists_lds128k", "scatter_direct"):
+    # (z stays 1 .. 5.5, a sliver of the planes' range, so that the lists stay as long as the scene's name says)
+    SCENES[_name + "@default_planes"] = dict(SCENES[_name], camera="default_planes", z_lo=1.0, z_hi=5.5)
+# ... and the two depth-bin scenes with their z ranges scaled to the planes: 0.02 .. 90, and 2 % of one depth
+SCENES["wide_depth_range@default_planes"] = dict(SCENES["wide_depth_range"], camera="default_planes", z_lo=0.02, z_hi=90.0)
+SCENES["crowded_depth_bins@default_planes"] = dict(SCENES["crowded_depth_bins"], camera="default_planes", z_lo=40.0, z_hi=40.8)
+
+
+def float64_depth_distortion(scene, f, **over):
+    """The depth_distortion plane of tests/torch_ref.py's float64 re-derivation (f: the oracle's forward, for the lists)."""
+    import torch_ref
+    dt = torch.float64
+    params = {k: torch.tensor(v, dtype=dt) for k, v in scene["gaussians"].items() if v is not None}
+    params["phase_offset"] = torch.tensor(scene["phase_offset"], dtype=dt)
+    params["dc_offset"] = torch.tensor(scene["dc_offset"], dtype=dt)
+    with torch.no_grad():
+        return torch_ref.render(params, f, Hh.oracle_kwargs(scene, **over), dd_only=True)["depth_distortion"].numpy()
+
+
+def needs_float64_depth_distortion(scene):
+    """Planes under which every d_ndc = far / (far - near) (1 - near / dist) is close to 1 (near 0.01: the ToF camera's
+    default): A D2 - D^2 cancels and the oracle's own reference-order fp32 sums are off float64 by 6e-6 .. 0.67 of the
+    plane's size in this file's scenes, so the oracle is no yardstick for that one plane."""
+    return scene["cam"]["znear"] < 0.05
+
+
 @pytest.mark.parametrize("mode", [1, 0], ids=["tile_pull", "whole_frame"])
 @pytest.mark.parametrize("name", list(SCENES))
 def test_preprocess_and_binning_bit_exact(name, mode, oracle, gpu):
@@ -249,12 +286,50 @@ def test_forward_backward_vs_oracle(name, oracle, gpu):
     scene = Hh.small_scene(**SCENES[name])
     f, b = Hh.run_oracle(oracle, scene)
     out, grads, _ = Hh.run_gpu(scene, gpu, optimize_offsets=True)
-    check_outputs(f, out)
+    dd_ref = float64_depth_distortion(scene, f) if needs_float64_depth_distortion(scene) else None
+    if "@" in name:
+        print("\n[camera] %s: %s" % (name, worst_errors(f, out, b, grads, scene, dd_ref)))
+    check_outputs(f, out, dd_ref=dd_ref)
     check_grads(b, grads, scene)
+    if "@shift" in name and "wide_spread" in name:
+        assert Hh.beyond_the_clamp_on_screen(scene, f).any(), "no blended Gaussian inside the image beyond the 1.3 tanfov clamp"
 
 
-def check_outputs(f, out):
+def worst_errors(f, out, b, grads, scene, dd_ref=None):
+    """For the record a test prints: the largest max-norm relative error over the compared image planes and over the
+    gradients (the figures IMG_MAX and GRAD_RTOL bound; a pixel on a blend edge shows in the first one)."""
+    img = max(Hh.rel_err(f[k], out[k])[0] for k in ["color", "phasor", "depth", "acc", "distribution"] + ([] if dd_ref is not None else ["depth_distortion"]))
+    names = dict(means3D="dL_dmeans3D", means2D="dL_dmeans2D", opacities="dL_dopacity", shs="dL_dsh", shs_p="dL_dsh_p", scales="dL_dscales",
+                 rotations="dL_drotations")
+    grad = max(Hh.rel_err(np.reshape(b[n], np.shape(grads[k])), grads[k])[0] for k, n in names.items() if grads.get(k) is not None and np.size(grads[k]))
+    txt = "images %.2g, gradients %.2g" % (img, grad)
+    if dd_ref is not None:
+        size = float(np.abs(dd_ref).max())
+        txt += ", depth_distortion vs float64 / size: device %.2g, oracle %.2g" % (
+            float(np.abs(out["depth_distortion"] - dd_ref).max()) / size, float(np.abs(f["depth_distortion"] - dd_ref).max()) / size)
+    return txt
+
+
+def check_depth_distortion_against_float64(oracle_dd, dev_dd, dd_ref):
+    """test_depth_distortion_in_a_narrow_depth_range's measure: as accurate as the oracle's reference-order fp32 sums,
+    relative to the plane's own size, and not negative beyond rounding."""
+    size = float(np.abs(dd_ref).max())
+    err_oracle = float(np.abs(oracle_dd - dd_ref).max())
+    err_dev = float(np.abs(dev_dd - dd_ref).max())
+    assert np.isfinite(dev_dd).all()
+    assert err_dev <= max(2.0 * err_oracle, 2e-3 * size), (err_dev, err_oracle, size)
+    assert float(dev_dd.min()) >= -1e-3 * size, (float(dev_dd.min()), size)
+
+
+def check_outputs(f, out, dd_ref=None):
+    """dd_ref: the float64 depth_distortion plane, for scenes where the oracle's own fp32 sums cancel
+    (needs_float64_depth_distortion).  That plane is then held to test_depth_distortion_in_a_narrow_depth_range's
+    measure -- as accurate as the oracle's reference-order sums, relative to the plane's own size, and not negative beyond
+    rounding -- and every other output is compared as always."""
     for k in ["color", "phasor", "depth", "acc", "depth_distortion", "distribution"]:
+        if k == "depth_distortion" and dd_ref is not None:
+            check_depth_distortion_against_float64(f[k], out[k], dd_ref)
+            continue
         l1 = np.abs(out[k].astype(np.float64) - f[k]).mean()
         scale = max(1.0, np.abs(f[k]).max())
         assert l1 < IMG_L1 * scale, "%s: L1 %.3g" % (k, l1)
@@ -953,11 +1028,26 @@ def test_scratch_buffers_may_start_as_anything(name, oracle, gpu):
         api._instance_hint.clear()
 
 
-@pytest.mark.parametrize("seed", list(range(12)))
+RANDOM_PLANES = [dict(znear=0.45, zfar=6.05, depth_range=10.0, z=(1.0, 5.5)), dict(znear=0.01, zfar=100.0, depth_range=100.0, z=(0.02, 90.0)),
+                 dict(znear=0.2, zfar=20.0, depth_range=7.0, z=(0.25, 18.0))]
+
+
+def random_camera(seed):
+    """A sensor camera in the form of helpers.CAMERAS, from a generator of its own (the draws of the scene stay what they
+    are without it): fx in 0.4 .. 4 f0, fy within a factor 1.4 of it (and inside 0.4 .. 4 f0), the principal point in
+    0.2 .. 0.8 of the image size, one of three plane sets."""
+    rng = np.random.default_rng(77000 + seed)
+    fx = float(10 ** rng.uniform(np.log10(0.4), np.log10(4.0)))
+    fy = float(np.clip(fx * 1.4 ** rng.uniform(-1.0, 1.0), 0.4, 4.0))
+    return dict(RANDOM_PLANES[int(rng.integers(0, 3))], fx=fx, fy=fy, cx=float(rng.uniform(0.2, 0.8)), cy=float(rng.uniform(0.2, 0.8)))
+
+
+@pytest.mark.parametrize("seed", list(range(24)))
 def test_random_configurations(seed, oracle, gpu):
     """Seeded sweep over frame shapes, densities, SH degrees, camera poses and scale modifiers:
-    images, counters and every gradient against the oracle."""
+    images, counters and every gradient against the oracle.  Seeds 12 .. 23 also draw the camera's intrinsics and planes."""
     rng = np.random.default_rng(1000 + seed)
+    camera = random_camera(seed) if seed >= 12 else None
     W = int(rng.integers(17, 130))
     H = int(rng.integers(9, 90))
     P = int(rng.integers(50, 6000))
@@ -968,14 +1058,18 @@ def test_random_configurations(seed, oracle, gpu):
     w2c = synth_pose(rng)
     scene = Hh.small_scene(P=P, W=W, H=H, seed=int(rng.integers(1 << 30)), D=D, sh_coeffs=M, scale_lo=lo, scale_hi=hi,
                            w2c=w2c, spread=float(rng.uniform(0.6, 1.8)),
-                           opacity=None if rng.random() < 0.6 else float(rng.uniform(0.02, 0.98)))
+                           opacity=None if rng.random() < 0.6 else float(rng.uniform(0.02, 0.98)), camera=camera)
     scene["use_view_dependent_phase"] = bool(rng.integers(0, 2))
     scene["phase_offset"] = float(rng.uniform(-0.5, 0.5))
     scene["dc_offset"] = float(rng.uniform(0.0, 0.2))
     over = dict(scale_modifier=float(rng.choice([1.0, 0.7, 1.3])))
     f, b = Hh.run_oracle(oracle, scene, **over)
     out, grads, _ = Hh.run_gpu(scene, gpu, optimize_offsets=True, **over)
-    check_outputs(f, out)
+    dd_ref = float64_depth_distortion(scene, f, **over) if needs_float64_depth_distortion(scene) else None
+    if camera is not None:
+        print("\n[camera] random configuration %d (fx %.2f f0, fy %.2f f0, c %.2f %.2f, near %g): %s" % (
+            seed, camera["fx"], camera["fy"], camera["cx"], camera["cy"], camera["znear"], worst_errors(f, out, b, grads, scene, dd_ref)))
+    check_outputs(f, out, dd_ref=dd_ref)
     check_grads(b, grads, scene)
 
 
@@ -983,6 +1077,76 @@ def synth_pose(rng):
     from gftorf_amd import synth
     return synth.look_at_w2c(float(rng.uniform(-0.3, 0.3)), float(rng.uniform(-0.2, 0.2)), float(rng.uniform(-0.2, 0.2)),
                              (float(rng.uniform(-0.2, 0.2)), float(rng.uniform(-0.2, 0.2)), float(rng.uniform(-0.1, 0.4))))
+
+
+@pytest.mark.parametrize("planes", list(Hh.PLANES))
+def test_plane_edges(planes, oracle, gpu):
+    """Gaussians at `near`, `far` and the floats next to each on both sides, identity pose (vz = pz exactly): the reference
+    culls with `<` and `>` (auxiliary.h:169), one exactly on a plane is kept.  radii, tile counts and R bit-exact against
+    the oracle in both binning modes, under the benchmark's planes and the ToF camera's defaults."""
+    scene, kept = Hh.plane_edge_scene(*Hh.PLANES[planes])
+    f, b = Hh.run_oracle(oracle, scene)
+    np.testing.assert_array_equal(f.radii > 0, kept)
+    for mode in (1, 0):
+        st = raw_forward(scene, gpu, mode=mode)
+        np.testing.assert_array_equal(st["radii"], f.geom["radii"])
+        np.testing.assert_array_equal(st["radii"] > 0, kept)
+        np.testing.assert_array_equal(st["tiles"], f.geom["tiles_touched"])
+        assert st["R"] == f.num_rendered == int(st["ctrl"][0])
+        np.testing.assert_array_equal(st["depth"][kept].view(np.uint32), f.geom["depths"][kept].view(np.uint32))
+    out, grads, _ = Hh.run_gpu(scene, gpu, optimize_offsets=True)
+    dd_ref = float64_depth_distortion(scene, f) if needs_float64_depth_distortion(scene) else None
+    print("\n[camera] plane edges %s: %s" % (planes, worst_errors(f, out, b, grads, scene, dd_ref)))
+    check_outputs(f, out, dd_ref=dd_ref)
+    check_grads(b, grads, scene)
+    for k in ("means3D", "scales", "rotations", "opacities", "shs", "shs_p"):
+        assert not grads[k][~kept].any(), k
+    vis = Hh.gpu_rasterizer(scene, gpu).markVisible(torch.tensor(scene["gaussians"]["means3D"], device=gpu))
+    np.testing.assert_array_equal(vis.cpu().numpy(), kept)
+
+
+@pytest.mark.parametrize("dx,dy", [(16, -16), (-32, 0)])
+@pytest.mark.parametrize("name", list(Hh.TRANSLATED))
+def test_principal_point_shift_by_whole_tiles_translates_the_image(name, dx, dy, gpu):
+    """Moving the principal point by whole tiles moves the image and nothing else (the operator against itself, no oracle:
+    test_oracle_properties.py has the same property on the oracle, where no element is left out).  Both binning modes, both
+    forward blend kernels: over the pixels both images see every plane agrees within IMG_MAX (1e-3 of the elements may be
+    alpha-edge flips); given upstream gradients that are zero outside the overlap and translated inside it, the Gaussians
+    that neither image clips get the same gradients within GRAD_RTOL."""
+    from gftorf_amd import api
+    a, b = Hh.translated_pair(dx, dy, **Hh.TRANSLATED[name])
+    W, H = a["cfg"]["W"], a["cfg"]["H"]
+    worst = {}
+    for bm in (1, 0):
+        for rm in (0, 1):
+            with binning_mode(bm), render_mode(rm):
+                api._instance_hint.clear()
+                oa, ga, _ = Hh.run_gpu(a, gpu)
+                ob, gb, _ = Hh.run_gpu(b, gpu)
+            for k in ["color", "phasor", "depth", "acc", "depth_distortion"]:
+                va, vb = Hh.overlap(oa[k], ob[k], dx, dy)
+                assert va.size >= W * H // 3 and np.abs(va).max() > 0
+                worst[k] = max(worst.get(k, 0.0), Hh.rel_err(va, vb)[0])
+                Hh.assert_close(k, va, vb, rtol_max=IMG_MAX, atol=1e-6, frac_bad=1e-3)
+            both = Hh.rect_inside_both(pixel_centres(a), oa["radii"], W, H, dx, dy)
+            assert both.sum() >= 20
+            np.testing.assert_array_equal(ob["radii"][both], oa["radii"][both])
+            for k in ga:
+                if ga[k] is not None:
+                    assert np.abs(ga[k][both]).max() > 0, k
+                    worst["d" + k] = max(worst.get("d" + k, 0.0), Hh.rel_err(ga[k][both], gb[k][both])[0])
+                    Hh.assert_close("d" + k, ga[k][both], gb[k][both], rtol_max=GRAD_RTOL)
+    print("\n[camera] translated %s (%d, %d): worst rel. err %s" % (name, dx, dy, ", ".join("%s %.2g" % kv for kv in worst.items())))
+
+
+def pixel_centres(scene):
+    """Pixel centres of the scene's Gaussians (float64 from the scene's own matrices; only used to say which Gaussians lie
+    well inside an image)."""
+    m = scene["gaussians"]["means3D"].astype(np.float64)
+    p = np.concatenate([m, np.ones((m.shape[0], 1))], 1) @ scene["cam"]["projmatrix"].astype(np.float64)
+    W, H = scene["cfg"]["W"], scene["cfg"]["H"]
+    w = p[:, 3] + 1e-7
+    return np.stack([((p[:, 0] / w + 1) * W - 1) / 2, ((p[:, 1] / w + 1) * H - 1) / 2], 1)
 
 
 @pytest.mark.gpu
@@ -1072,15 +1236,10 @@ def test_depth_distortion_in_a_narrow_depth_range(z_lo, z_hi, oracle, gpu):
     the kernels accumulate around the tile's nearest depth.  Against the float64 re-derivation (tests/torch_ref.py) the
     plane must be as accurate as the oracle's reference-order fp32 sums (relative to the plane's own size, not to 1),
     and not negative beyond rounding."""
-    import torch_ref
     sc = Hh.small_scene(P=1500, W=64, H=48, seed=5, scale_lo=0.03, scale_hi=0.15, z_lo=z_lo, z_hi=z_hi, w2c=None)
     f, _ = Hh.run_oracle(oracle, sc, backward=False)
     out, grads, _ = Hh.run_gpu(sc, gpu)
-    dt = torch.float64
-    params = {k: torch.tensor(v, dtype=dt, requires_grad=True) for k, v in sc["gaussians"].items() if v is not None}
-    params["phase_offset"] = torch.tensor(sc["phase_offset"], dtype=dt, requires_grad=True)
-    params["dc_offset"] = torch.tensor(sc["dc_offset"], dtype=dt, requires_grad=True)
-    ref = torch_ref.render(params, f, Hh.oracle_kwargs(sc))["depth_distortion"].detach().numpy()
+    ref = float64_depth_distortion(sc, f)
     size = float(np.abs(ref).max())
     err_oracle = float(np.abs(f["depth_distortion"] - ref).max())
     err_dev = float(np.abs(out["depth_distortion"] - ref).max())

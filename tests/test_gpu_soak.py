@@ -17,3 +17,17 @@ def test_seeded_slice_of_the_soak(oracle, gpu):
     assert rec["modes_met"] >= 60, rec["by_mode"]                         # of 2 x 2 x 4 x 3 x 2 x 2 = 192 combinations
     # pixels on the 1/255 or T = 1e-4 edge happen; frames beyond the tests' own count band must stay the exception
     assert rec["cases_beyond_the_tests_pixel_count_band"] <= CASES // 20, rec
+
+
+CAMERA_CASES = 100
+
+
+def test_seeded_slice_of_the_soak_through_sensor_cameras(oracle, gpu):
+    """The same generator, another seed, every frame through the camera its case names: the centred one or one of
+    helpers.CAMERAS (principal point off the centre, fx != fy, tele / wide, the ToF camera's default planes)."""
+    import helpers as Hh
+    rec = soak_cases.run(gpu, oracle, seed=20261016, cases=CAMERA_CASES, cameras=True)
+    print("soak through sensor cameras: %.1f s, %s, deepest tile list %d" % (rec["seconds"], rec["by_camera"], rec["deepest_tile_list"]))
+    assert rec["cases"] == CAMERA_CASES
+    assert set(rec["by_camera"]) == {str(c) for c in [None] + list(Hh.CAMERAS)}, rec["by_camera"]
+    assert rec["cases_beyond_the_tests_pixel_count_band"] <= CAMERA_CASES // 20, rec

@@ -115,6 +115,35 @@ def test_camera_convention_matches_reference_helpers():
     np.testing.assert_allclose(c2["campos"], np.linalg.inv(M)[:3, 3], atol=1e-6)
 
 
+def test_shifted_projection_matches_reference_helper():
+    """getProjectionMatrixShift (utils/graphics_utils.py:77-109), the projection every camera of the reference is built
+    with (scene/cameras.py:122-140), against the fixture captured from it; and synth.make_sensor_camera multiplies it
+    into `projmatrix` in the reference's transposed storage, with tanfov = size / (2 focal)."""
+    d = np.load(os.path.join(GOLD, "camera.npz"))
+    args = d["shift_args"]
+    np.testing.assert_allclose(synth.projection_matrix_shift(*args), d["shift_proj"], rtol=1e-6, atol=1e-7)
+    assert d["shift_proj"][0, 2] != 0 and d["shift_proj"][1, 2] != 0      # (the fixture does have a shift)
+    zn, zf, fx, fy, cx, cy, W, H, fovx, fovy = args
+    W, H = int(W), int(H)
+    # identity pose: full_proj_transform = P^T
+    cam = synth.make_sensor_camera(W, H, fx, fy, cx, cy, zn, zf, None)
+    np.testing.assert_allclose(cam["projmatrix"], d["shift_proj"].T, rtol=1e-6, atol=1e-7)
+    assert abs(cam["tanfovx"] - W / (2 * fx)) < 1e-12 and abs(cam["tanfovy"] - H / (2 * fy)) < 1e-12
+    assert abs(cam["tanfovx"] - math.tan(fovx / 2)) < 1e-12 and abs(cam["tanfovy"] - math.tan(fovy / 2)) < 1e-12
+    # a pose: world_view_transform = w2c^T, full_proj_transform = w2c^T P^T (scene/cameras.py:127-129)
+    cam = synth.make_sensor_camera(W, H, fx, fy, cx, cy, zn, zf, d["w2v"])
+    np.testing.assert_allclose(cam["viewmatrix"], d["w2v"].T, atol=0)
+    want = (d["shift_proj"].astype(np.float64) @ d["w2v"].astype(np.float64)).T
+    np.testing.assert_allclose(cam["projmatrix"], want, rtol=1e-6, atol=1e-6)
+    # a point on the optical axis lands on the principal point: pixel = ((ndc + 1) size - 1) / 2 = c - 0.5
+    p = np.array([0.0, 0.0, 2.0, 1.0]) @ synth.make_sensor_camera(W, H, fx, fy, cx, cy, zn, zf, None)["projmatrix"].astype(np.float64)
+    np.testing.assert_allclose([((p[0] / p[3] + 1) * W - 1) / 2, ((p[1] / p[3] + 1) * H - 1) / 2], [cx - 0.5, cy - 0.5], atol=1e-4)
+    # the table's `sensor` entry is this camera at the fixture's size
+    import helpers as Hh
+    c2 = Hh.sensor_camera("sensor", W, H)
+    np.testing.assert_allclose(c2["projmatrix"], d["shift_proj"].T, rtol=1e-6, atol=1e-7)
+
+
 def test_pa2sh_rgb2sh_recipe():
     d = np.load(os.path.join(GOLD, "sh_color.npz"))
     x = d["rgb2sh_in"]

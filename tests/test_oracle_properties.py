@@ -176,3 +176,50 @@ def test_kept_buffers_give_the_same_results(oracle):
                 np.testing.assert_allclose(v, g[k], rtol=1e-6, atol=1e-9, err_msg=k)   # (double sums in thread order)
     finally:
         oracle.reuse_buffers(False)
+
+
+@pytest.mark.parametrize("dx,dy", [(16, -16), (-32, 0)])
+@pytest.mark.parametrize("name", list(Hh.TRANSLATED))
+def test_principal_point_shift_by_whole_tiles_translates_the_image(name, dx, dy, oracle):
+    """Moving the principal point by whole tiles moves the image and nothing else: the view space, the covariances and
+    every tile-relative quantity stay.  Over the pixels both images see, every plane agrees within fp32 rounding of
+    means2D (IMG_MAX of test_gpu_parity.py, no element left out); the Gaussians that neither image clips keep their radius
+    and their tile count, one that leaves the image gets radius 0 there."""
+    IMG_MAX = 2e-4
+    a, b = Hh.translated_pair(dx, dy, **Hh.TRANSLATED[name])
+    fa, _ = Hh.run_oracle(oracle, a, backward=False)
+    fb, _ = Hh.run_oracle(oracle, b, backward=False)
+    W, H = a["cfg"]["W"], a["cfg"]["H"]
+    for k in ["color", "phasor", "depth", "acc", "depth_distortion"]:
+        va, vb = Hh.overlap(fa[k], fb[k], dx, dy)
+        assert va.size >= W * H // 3 and np.abs(va).max() > 0
+        err, den = Hh.rel_err(va, vb)
+        print("%s %s (%d, %d): rel. err %.3g of %.3g" % (name, k, dx, dy, err, den))
+        Hh.assert_close(k, va, vb, rtol_max=IMG_MAX, atol=1e-6)
+    m2, r = fa.geom["means2D"], fa.radii
+    both = Hh.rect_inside_both(m2, r, W, H, dx, dy)
+    assert both.sum() >= 20
+    np.testing.assert_array_equal(fb.radii[both], r[both])
+    np.testing.assert_array_equal(fb.geom["tiles_touched"][both], fa.geom["tiles_touched"][both])
+    np.testing.assert_allclose(fb.geom["means2D"][both], m2[both] + np.array([dx, dy], np.float32), atol=2e-4)
+    # wholly outside the second image (beyond the clipped tile grid): radius 0 there, whatever it was in the first
+    gx, gy = (W + 15) // 16 * 16, (H + 15) // 16 * 16
+    gone = (r > 0) & ((m2[:, 0] + dx + r < -1) | (m2[:, 0] + dx - r > gx + 1) | (m2[:, 1] + dy + r < -1) | (m2[:, 1] + dy - r > gy + 1))
+    assert gone.any() and not fb.radii[gone].any()
+    # ... and one that both images see has one radius: the cull is the tile rectangle's, nothing else depends on the principal point
+    seen = (fb.radii > 0) & (r > 0)
+    np.testing.assert_array_equal(fb.radii[seen], r[seen])
+
+
+@pytest.mark.parametrize("planes", list(Hh.PLANES))
+def test_plane_edges(planes, oracle):
+    """auxiliary.h:169 culls with `p_view.z < near || p_view.z > far`: a Gaussian exactly on a plane is kept, the next float
+    outside is not."""
+    sc, kept = Hh.plane_edge_scene(*Hh.PLANES[planes])
+    f, _ = Hh.run_oracle(oracle, sc, backward=False)
+    np.testing.assert_array_equal(f.geom["depths"][kept], sc["gaussians"]["means3D"][kept, 2])      # vz = pz exactly
+    np.testing.assert_array_equal(f.radii > 0, kept)
+    vis = oracle.mark_visible(sc["gaussians"]["means3D"], sc["cam"]["viewmatrix"], sc["cam"]["projmatrix"],
+                              sc["cam"]["znear"], sc["cam"]["zfar"])
+    np.testing.assert_array_equal(vis, kept)
+    assert (f.pixels[kept] > 0).any()

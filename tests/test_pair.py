@@ -10,8 +10,21 @@ from gftorf_amd import synth
 pytestmark = pytest.mark.gpu
 
 
-def _two_views(P=3000, W=96, H=64, seed=5, **kw):
-    """The same Gaussians seen by two cameras a small baseline apart (colour camera / ToF sensor)."""
+def _two_views(P=3000, W=96, H=64, seed=5, sensors=False, **kw):
+    """The same Gaussians seen by two cameras a small baseline apart (colour camera / ToF sensor).
+    sensors: as in the reference's scenes (scene/dataset_readers.py:360-375,396-401) the two cameras differ in size, field
+    of view, principal point and planes: view A 96 x 64 through `wide` (planes 0.45 / 6.05), view B 64 x 48 through `sensor`
+    with the ToF camera's default planes 0.01 / 100 and depth_range 100, and its own pose."""
+    if sensors:
+        a = Hh.small_scene(P=P, W=96, H=64, seed=seed, w2c=synth.look_at_w2c(0.10, -0.05, 0.02, (0.05, 0.0, 0.1)), camera="wide", **kw)
+        cam_b = dict(Hh.CAMERAS["sensor"], znear=0.01, zfar=100.0, depth_range=100.0)
+        b = Hh.small_scene(P=P, W=64, H=48, seed=seed, w2c=synth.look_at_w2c(0.13, -0.02, -0.03, (0.09, 0.03, 0.15)), camera=cam_b, **kw)
+        b["gaussians"] = a["gaussians"]
+        b["grads"] = synth.make_pixel_grads(64, 48, seed + 100)
+        b["bg"] = synth.make_background(64, 48, seed + 100)
+        b["phase_offset"], b["dc_offset"] = 0.25, 0.02
+        a["use_view_dependent_phase"] = False
+        return a, b
     a = Hh.small_scene(P=P, W=W, H=H, seed=seed, w2c=synth.look_at_w2c(0.10, -0.05, 0.02, (0.05, 0.0, 0.1)), **kw)
     b = Hh.small_scene(P=P, W=W, H=H, seed=seed, w2c=synth.look_at_w2c(0.12, -0.05, 0.02, (0.09, 0.0, 0.1)), **kw)
     b["gaussians"] = a["gaussians"]
@@ -82,7 +95,8 @@ def _same_grads(l1, m1, l2, m2, tol):
     assert not y[:, 2].any()
 
 
-@pytest.mark.parametrize("kw", [dict(), dict(P=20000, W=64, H=48, scale_lo=0.03, scale_hi=0.15)], ids=["base", "deep_lists"])
+@pytest.mark.parametrize("kw", [dict(), dict(P=20000, W=64, H=48, scale_lo=0.03, scale_hi=0.15), dict(sensors=True)],
+                         ids=["base", "deep_lists", "sensors"])
 def test_pair_equals_two_single_calls(kw, gpu):
     a, b = _two_views(**kw)
     for rep in range(3):         # first frames size their buffers after a blocking read, later ones from hints
@@ -95,13 +109,28 @@ def test_pair_equals_two_single_calls(kw, gpu):
 
 
 def test_pair_against_the_oracle(oracle, gpu):
-    a, b = _two_views()
+    _pair_against_the_oracle(False, oracle, gpu)
+
+
+def test_pair_against_the_oracle_sensors(oracle, gpu):
+    """... with two cameras that differ in size, field of view, principal point and planes (_two_views(sensors=True))."""
+    _pair_against_the_oracle(True, oracle, gpu)
+
+
+def _pair_against_the_oracle(sensors, oracle, gpu):
+    import test_gpu_parity as T
+    a, b = _two_views(sensors=sensors)
     (fa, ba), (fb, bb) = Hh.run_oracle(oracle, a), Hh.run_oracle(oracle, b)
     (oa, ob), leaf, m2, offs = _run_pair(a, b, gpu, offsets=True)
-    for f, o in ((fa, oa), (fb, ob)):
+    for sc, f, o in ((a, fa, oa), (b, fb, ob)):
         o = dict(zip(Hh.OUT_NAMES, o))
         np.testing.assert_array_equal(o["radii"].cpu().numpy(), f.radii)
+        assert (f.radii > 0).sum() > 500 and (f.pixels > 0).sum() > 500
         for k in ["color", "phasor", "depth", "acc", "depth_distortion"]:
+            if k == "depth_distortion" and T.needs_float64_depth_distortion(sc):
+                # (the ToF camera's default planes: the oracle's own sums cancel, the plane is held to float64)
+                T.check_depth_distortion_against_float64(f[k], o[k].detach().cpu().numpy(), T.float64_depth_distortion(sc, f))
+                continue
             Hh.assert_close(k, f[k], o[k].detach().cpu().numpy(), rtol_max=2e-4, atol=1e-6, frac_bad=1e-3)
     for key, name in [("means3D", "dL_dmeans3D"), ("shs", "dL_dsh"), ("shs_p", "dL_dsh_p"), ("scales", "dL_dscales"),
                       ("rotations", "dL_drotations")]:
@@ -109,6 +138,9 @@ def test_pair_against_the_oracle(oracle, gpu):
     Hh.assert_close("dL_dopacity", (ba["dL_dopacity"] + bb["dL_dopacity"]).reshape(-1), leaf["opacities"].grad.cpu().numpy().reshape(-1),
                     rtol_max=3e-4)
     Hh.assert_close("dL_dmeans2D", ba["dL_dmeans2D"] + bb["dL_dmeans2D"], m2.grad.cpu().numpy(), rtol_max=3e-4)
+    print("\n[camera] pair against the oracle (%s): means3D gradient %.2g, colour %.2g / %.2g" % (
+        "sensors" if sensors else "one camera", Hh.rel_err(ba["dL_dmeans3D"] + bb["dL_dmeans3D"], leaf["means3D"].grad.cpu().numpy())[0],
+        Hh.rel_err(fa["color"], oa[0].detach().cpu().numpy())[0], Hh.rel_err(fb["color"], ob[0].detach().cpu().numpy())[0]))
     # each view's own scalar offsets
     for v, bk in ((0, ba), (1, bb)):
         Hh.assert_close("dL_dphase_offset", bk["dL_dphase_offset"], offs[v][0].grad.cpu().numpy(), rtol_max=3e-4, atol=1e-5)

@@ -50,11 +50,49 @@ def sh_poly(deg, sh, dirs):
     return res
 
 
-def render(params, fwd, settings):
+def _depth_distortion_tile(ids, pix_x, pix_y, con_x, con_y, con_z, opac, d_ndc, pxf, pyf, chunk=256):
+    """The depth_distortion sums of render()'s walk over one tile's list, forward only, `chunk` list entries at a time: the
+    same float64 terms (transmittance as a running product, the exclusive sums A, D, D2 as running sums), so that a list
+    of thousands of entries takes milliseconds.  Stops, like the walk, once every pixel has terminated."""
+    n = pxf.numel()
+    dt = pxf.dtype
+    T = torch.ones(n, dtype=dt)
+    done = torch.zeros(n, dtype=torch.bool)
+    A, D1, D2, DD = (torch.zeros(n, dtype=dt) for _ in range(4))
+    for c0 in range(0, ids.numel(), chunk):
+        if bool(done.all()):
+            break
+        j = ids[c0:c0 + chunk]
+        dx = pix_x[j][:, None] - pxf[None]
+        dy = pix_y[j][:, None] - pyf[None]
+        power = -0.5 * (con_x[j][:, None] * dx * dx + con_z[j][:, None] * dy * dy) - con_y[j][:, None] * dx * dy
+        alpha = torch.clamp(opac[j][:, None] * torch.exp(power), max=0.99)
+        skip = (power > 0) | (alpha < 1.0 / 255.0)
+        a_eff = torch.where(skip, torch.zeros_like(alpha), alpha)
+        incl = T[None] * torch.cumprod(1 - a_eff, 0)                 # test_T at every entry
+        excl = torch.cat([T[None], incl[:-1]], 0)                    # T in front of it
+        stop = (~skip) & (incl < 1e-4)
+        stopped = torch.cumsum(stop.to(torch.int32), 0) > 0          # at or behind the entry that terminates the pixel
+        act = (~skip) & (~stopped) & (~done[None])
+        w = a_eff * excl * act.to(dt)
+        z = d_ndc[j][:, None]
+        wz, wzz = w * z, w * z * z
+        A_ex = A[None] + torch.cumsum(w, 0) - w
+        D1_ex = D1[None] + torch.cumsum(wz, 0) - wz
+        D2_ex = D2[None] + torch.cumsum(wzz, 0) - wzz
+        DD = DD + (w * (z * z * A_ex - 2 * z * D1_ex + D2_ex)).sum(0)
+        A, D1, D2 = A + w.sum(0), D1 + wz.sum(0), D2 + wzz.sum(0)
+        T = incl[-1]                                                  # (of no further use where the pixel has terminated)
+        done = done | stopped[-1]
+    return DD
+
+
+def render(params, fwd, settings, dd_only=False):
     """params: dict of float64 leaf tensors (means3D, opacities, shs|colors_precomp,
     shs_p|phasors_precomp, scales+rotations|cov3D_precomp, phase_offset, dc_offset).
     fwd: oracle ForwardResult (lists / masks).  settings: dict of scalars + matrices.
-    Returns dict of output images (float64) + 'ndc' (retain_grad leaf-like)."""
+    Returns dict of output images (float64) + 'ndc' (retain_grad leaf-like).
+    dd_only (forward only, call under torch.no_grad()): only the depth_distortion plane, by _depth_distortion_tile."""
     dt = torch.float64
     W, H = settings["image_width"], settings["image_height"]
     V = torch.tensor(np.asarray(settings["viewmatrix"]).reshape(4, 4), dtype=dt)  # transposed storage
@@ -76,7 +114,8 @@ def render(params, fwd, settings):
     p_hom = ph @ PV
     p_w = 1.0 / (p_hom[:, 3:4] + 1e-7)
     ndc = p_hom[:, :2] * p_w
-    ndc.retain_grad()
+    if ndc.requires_grad:          # (a forward-only call under torch.no_grad() has no graph)
+        ndc.retain_grad()
     pix_x = ((ndc[:, 0] + 1.0) * W - 1.0) * 0.5
     pix_y = ((ndc[:, 1] + 1.0) * H - 1.0) * 0.5
 
@@ -173,6 +212,9 @@ def render(params, fwd, settings):
         xs, ys = xs.reshape(-1), ys.reshape(-1)
         n = xs.numel()
         pxf, pyf = xs.to(dt), ys.to(dt)
+        if dd_only:
+            out_dd[0, ys, xs] = _depth_distortion_tile(plist[r0:r1], pix_x, pix_y, con_x, con_y, con_z, opac, d_ndc, pxf, pyf)
+            continue
         T = torch.ones(n, dtype=dt)
         done = torch.zeros(n, dtype=torch.bool)
         Cc = torch.zeros(n, 3, dtype=dt)
@@ -221,5 +263,7 @@ def render(params, fwd, settings):
         out_depth[0, ys, xs] = dd_
         out_acc[0, ys, xs] = aa
         out_dd[0, ys, xs] = ddd
+    if dd_only:
+        return dict(depth_distortion=out_dd)
     return dict(color=out_color, phasor=out_phasor, depth=out_depth, acc=out_acc,
                 depth_distortion=out_dd, ndc=ndc)
