@@ -82,6 +82,49 @@ class _CameraSchedule:
         self.sched_seen = False
         self.miss_streak = self.sched_off_until = self.hinted_tiles = self.frames = 0
 
+    def attach(self, io, lib, dev, W, H, capturing):
+        """Counts a frame and puts the camera's buffers into its gft_forward_io; returns gft_forward_hints.use_cell_sched."""
+        # (a buffer that does not exist yet is made here -- never during a capture: it would live in the graph's private
+        # pool, so a captured frame gets only what exists already)
+        self.frames += 1
+        n_tiles = ((W + 15) // 16) * ((H + 15) // 16)
+        if self.tile_hints is None:
+            if capturing:
+                return 0
+            self.tile_hints = torch.zeros((n_tiles,), device=dev, dtype=torch.int32)
+        io.tile_hints = self.tile_hints.data_ptr()
+        use_sched = 0
+        if _CELL_SCHED:
+            if self.cell_sched is None and not capturing:
+                words = int(lib.gft_cell_sched_words(W, H))
+                self.cell_sched = torch.zeros((words,), device=dev, dtype=torch.int32) if words else False
+            if self.cell_sched is not None and self.cell_sched is not False:
+                io.cell_sched = self.cell_sched.data_ptr()
+                use_sched = int(_force_cell_sched if _force_cell_sched is not None
+                                else (self.sched_seen and self.frames >= self.sched_off_until))
+        if _FWD_ORDER:
+            if self.tile_weights is None and not capturing:
+                self.tile_weights = torch.zeros((4 * n_tiles + 4,), device=dev, dtype=torch.int32)
+            io.tile_weights = _ptr(self.tile_weights)
+        return use_sched
+
+    def take_report(self, report, use_sched, fits):
+        """Takes what a hinted frame reported (gft_forward_report); ``fits``: its instances fitted the binning buffer."""
+        # (a camera whose lists keep outgrowing what its last frame left -- its tensors shared by scenes of different
+        # sizes, say -- pays the counted flow ON TOP of the failed attempt: after four misses in a row it counts again for 64
+        # frames, then tries anew.  A frame that did not fit the BINNING BUFFER either is re-rendered whatever the schedule
+        # said: not the schedule's miss.)
+        if use_sched and not report.sched_misses:
+            self.miss_streak = 0
+        elif use_sched:
+            last_call_stats["sched_misses"] = last_call_stats.get("sched_misses", 0) + 1
+            if fits:
+                self.miss_streak += 1
+                if self.miss_streak >= _SCHED_MISSES_OFF and _force_cell_sched is None:
+                    self.miss_streak = 0
+                    self.sched_off_until = self.frames + _SCHED_OFF_FRAMES
+        self.hinted_tiles = int(report.hinted_tiles)
+
 
 class _OperatorState:
     """Everything the operator keeps between calls, in one place (`gftorf_amd.api.state`; `state.reset()` drops all of it --
@@ -129,7 +172,8 @@ class _OperatorState:
 
 
 state = _OperatorState()
-_instance_hint = state.instance_hint          # (the same objects under the names the tests and bench.py have always used)
+# (the same objects under the names the tests and bench.py have always used; this file says `state.…`)
+_instance_hint, _status, _grad_pool, _acc_pool = state.instance_hint, state.status, state.grad_pool, state.acc_pool
 # GFT_BWD_DETERMINISTIC=1: the backward forms its per-Gaussian sums in a fixed order instead of with float atomics
 # (bit-reproducible gradients; several times slower: for tests)
 _DETERMINISTIC = _os.environ.get("GFT_BWD_DETERMINISTIC", "0") != "0"
@@ -161,20 +205,20 @@ def _whole_lists(cam, n_tiles):
 # it -- raises.  `enqueue_status()` returns the postings (after a graph replay, say).  Outside a capture, a shape that has
 # no size hint yet (the first frame of the process, a new P after densification) takes the blocking two-stage flow once.
 no_host_read = _os.environ.get("GFT_NO_HOST_READ", "0") != "0"
-_status = state.status    # hint key -> dict(dev=int32[16] on the device, host=its pinned copy, seen=overflows reported so far)
+# state.status: hint key -> dict(dev=int32[16] on the device, host=its pinned copy, seen=overflows reported so far)
 _ST_CAP, _ST_OVERFLOWS, _ST_MAX_R = 12, 13, 14      # include/gftorf_rast.h: GFT_STATUS_CAP / _OVERFLOWS / _MAX_R
 
 
 def _status_of(key, dev, create):
-    st = _status.get(key)
+    st = state.status.get(key)
     if st is None and create:
-        st = _status[key] = dict(dev=torch.zeros((16,), device=dev, dtype=torch.int32),
+        st = state.status[key] = dict(dev=torch.zeros((16,), device=dev, dtype=torch.int32),
                                  host=torch.zeros((16,), dtype=torch.int32).pin_memory(), seen=0, key=key)
         st["np"] = st["host"].numpy()
-        while len(_status) > state.MAX_SHAPES:       # (P changes with every densification step: the most recent shapes)
-            _status.popitem(last=False)
+        while len(state.status) > state.MAX_SHAPES:       # (P changes with every densification step: the most recent shapes)
+            state.status.popitem(last=False)
     elif st is not None:
-        _status.move_to_end(key)
+        state.status.move_to_end(key)
     return st
 
 
@@ -187,10 +231,10 @@ def enqueue_status(synchronize=True):
     frame has overwritten are in it)."""
     if synchronize and torch.cuda.is_available():
         torch.cuda.synchronize()
-        for st in _status.values():
+        for st in state.status.values():
             st["host"].copy_(st["dev"])
     out = []
-    for key, st in _status.items():
+    for key, st in state.status.items():
         a = st["np"]
         out.append(dict(key=key, posted=bool(a[3]), num_rendered=int(a[0]), binning_instances=int(a[_ST_CAP]),
                         overflow=bool(a[3]) and int(a[0]) > int(a[_ST_CAP]), overflows=int(a[_ST_OVERFLOWS]),
@@ -217,16 +261,9 @@ def enqueue_status(synchronize=True):
 # whole buffer) and raises if not.
 _GRADS_REUSE = _os.environ.get("GFT_GRADS_REUSE", "1") != "0"
 _GRADS_CHECK = _os.environ.get("GFT_GRADS_REUSE_CHECK", "0") != "0"
-# "Nobody aliases the buffer any more" is read from the storage's use count where torch has the (private) counter
-# CUDA-graph trees use.  Without it -- another torch version; GFT_GRADS_LIFETIME=dlpack forces it -- the public route:
-# the pool owns the memory and never hands it out; every forward gets an ALIAS of it through DLPack (torch.from_dlpack of a
-# capsule made here), whose deleter torch calls when the last tensor on that alias dies.  The version counter of an alias
-# dies with it, so on this route in-place writes are not seen afterwards; the one writer that is not the caller's doing --
-# autograd summing a second gradient INTO a tensor it took over as a leaf's `.grad` -- is kept out by holding a reference
-# to the handed-out tensors until the next forward of the shape: autograd then copies into `.grad` instead of taking them
-# (a copy per directly fed leaf: the price of the fallback), everything else is the contract above.
-_USE_COUNT_API = hasattr(torch._C, "_storage_Use_Count") and _os.environ.get("GFT_GRADS_LIFETIME", "") != "dlpack"
-_grad_pool = state.grad_pool       # (device, P, layout) -> list of {buf, dirty, version, base}
+# Without the private counter (another torch) the pool is not used at all: fresh tensors written in full, as with
+# GFT_GRADS_REUSE=0.
+_USE_COUNT_API = hasattr(torch._C, "_storage_Use_Count")
 _DENSE_SHARE = 0.3        # rows written by the last rows-only backward / P above which the tensors are written in full
 _DENSE_RUN = 15           # ... for this many backwards, before a rows-only one counts again
 _GRAD_POOL_DEPTH = 3      # rasterizer calls of one iteration whose gradient tensors are alive at the same time
@@ -254,55 +291,77 @@ def _storage_refs(t):
     return torch._C._storage_Use_Count(t.untyped_storage()._cdata)
 
 
-class _DLDevice(C.Structure):
-    _fields_ = [("device_type", C.c_int32), ("device_id", C.c_int32)]
+# One kept set of gradient tensors:
+#   buf      the one allocation all per-Gaussian gradients are slices of; `version` / `base`: its version counter and its
+#            storage's use count while the pool alone holds it.
+#   dirty    a mark per Gaussian + the 144 bytes behind them in which the rows backward counts.
+#   valid    the last backward into the buffer returned without error, so every row is defined -- zero or marked in `dirty`.
+#            A buffer that was handed to a forward whose backward never ran (a render under grad used only for logging, a
+#            loss skipped by a NaN guard) or failed holds rows nobody wrote: it may be taken again, but as a fresh one that
+#            the backward writes in full.
+#   report   pinned host word into which the rows backward stores the number of rows it wrote
+#            (gft_backward_io.rows_report), `report_np` its numpy view; `dense_left`, `probe`, `tick`: write_mode().
+class _GradEntry:
+    """An entry of state.grad_pool: (device, P, layout) -> list of at most _GRAD_POOL_DEPTH of these."""
+    __slots__ = ("buf", "dirty", "version", "base", "valid", "report", "report_np", "dense_left", "probe", "tick")
+
+    def __init__(self, total, P, dev):
+        self.buf = torch.empty((total,), device=dev, dtype=torch.float32)
+        self.report = _report_slot()
+        self.report_np = self.report.numpy()
+        self.dirty = torch.zeros(((P + 3) // 4 * 4 + 144,), device=dev, dtype=torch.uint8)
+        self.version = self.buf._version
+        self.base = _storage_refs(self.buf)
+        self.valid = self.probe = False
+        self.dense_left = self.tick = 0
+
+    def is_free(self):
+        return _storage_refs(self.buf) == self.base and self.buf._version == self.version
+
+    def is_spent(self):
+        """Somebody wrote to it through a tensor (autograd's in-place sum of two calls' gradients, clipping) and nobody
+        references it any more: never trusted again, the pool forgets it."""
+        return self.buf._version != self.version and _storage_refs(self.buf) == self.base
+
+    def write_mode(self, P):
+        """How the next backward writes a reused entry: (rows only, it reports its row count)."""
+        # A kept set is rewritten row by row only while few rows are written (a dense frame blends a few per cent of its
+        # Gaussians): the rows kernel stores its rows straight from the lanes, and from about a third of the Gaussians on the
+        # full write through LDS -- coalesced, zeros included -- is faster (C3-shaped frame, 96 % blended: 16 vs 54 us; fog:
+        # 140 vs 203 us).  The last rows backward has left its row count in pinned memory: above _DENSE_SHARE the next
+        # _DENSE_RUN backwards into these tensors write them in full (which marks every row), then one rows backward looks
+        # again.  (The report costs the rows kernel ~4 us: the first two, the one after a dense run, then every 16th call.)
+        if self.dense_left > 0:
+            self.dense_left -= 1
+            self.probe = self.dense_left == 0
+            return False, False
+        if int(self.report_np[0]) > _DENSE_SHARE * P:
+            self.dense_left = _DENSE_RUN
+            self.report_np[0] = 0
+            return False, False
+        self.tick += 1
+        sample = self.probe or self.tick <= 2 or self.tick % 16 == 0
+        self.probe = False
+        return True, sample
 
 
-class _DLDataType(C.Structure):
-    _fields_ = [("code", C.c_uint8), ("bits", C.c_uint8), ("lanes", C.c_uint16)]
-
-
-class _DLTensor(C.Structure):
-    _fields_ = [("data", C.c_void_p), ("device", _DLDevice), ("ndim", C.c_int32), ("dtype", _DLDataType),
-                ("shape", C.POINTER(C.c_int64)), ("strides", C.POINTER(C.c_int64)), ("byte_offset", C.c_uint64)]
-
-
-class _DLManagedTensor(C.Structure):
-    pass
-
-
-_DL_DELETER = C.CFUNCTYPE(None, C.POINTER(_DLManagedTensor))
-_DLManagedTensor._fields_ = [("dl_tensor", _DLTensor), ("manager_ctx", C.c_void_p), ("deleter", _DL_DELETER)]
-_dl_live = {}             # token -> (struct, shape array, callback, entry): alive until torch has called the deleter
-_dl_token = [0]
-
-
-def _dl_alias(entry):
-    """A float32 tensor on the memory of ``entry["mem"]`` with a storage of its own (DLPack, kDLROCM): when the last tensor
-    on that storage dies torch calls the capsule's deleter, which marks the entry free."""
-    mem = entry["mem"]
-    _dl_token[0] += 1
-    token = _dl_token[0]
-    m = _DLManagedTensor()
-    shape = (C.c_int64 * 1)(mem.numel())
-    m.dl_tensor.data = mem.data_ptr()
-    m.dl_tensor.device = _DLDevice(10 if mem.is_cuda else 1, mem.device.index or 0)      # kDLROCM / kDLCPU
-    m.dl_tensor.ndim = 1
-    m.dl_tensor.dtype = _DLDataType(2, 32, 1)                                               # kDLFloat, 32 bits
-    m.dl_tensor.shape = shape
-    m.dl_tensor.strides = None
-    m.dl_tensor.byte_offset = 0
-
-    def released(_ptr, token=token, entry=entry):
-        entry["free"] = True
-        _dl_live.pop(token, None)
-    cb = _DL_DELETER(released)
-    m.deleter = cb
-    _dl_live[token] = (m, shape, cb, entry)
-    entry["free"] = False
-    new = C.pythonapi.PyCapsule_New
-    new.restype, new.argtypes = C.py_object, [C.c_void_p, C.c_char_p, C.c_void_p]
-    return torch.from_dlpack(new(C.addressof(m), b"dltensor", None))
+def _take_grads(dev, P, total, layout_key):
+    """A free entry of the shape's pool -- a valid one if there is any -- or a new one: (entry, reused)."""
+    pool = state.grad_pool.setdefault((dev.index, P, layout_key), [])
+    pool[:] = [e for e in pool if not e.is_spent()]
+    free = [e for e in pool if e.is_free()]
+    entry = next((e for e in free if e.valid), None)
+    reused = entry is not None
+    if entry is None and free:
+        entry = free[0]
+    if entry is None:
+        entry = _GradEntry(total, P, dev)
+        pool.append(entry)
+        del pool[:-_GRAD_POOL_DEPTH]
+        if len(state.grad_pool) > 8:
+            state.grad_pool.pop(next(iter(state.grad_pool)))
+    entry.valid = False           # until the backward of this forward has returned (run_backward)
+    return entry, reused
 
 
 # The backward's accumulator (64 B per Gaussian) kept from one backward to the next.  The render backward adds to the rows
@@ -314,7 +373,7 @@ def _dl_alias(entry):
 # whose backward never ran (its clear or its predecessor's zeroing stands), or a backward that returned without error.
 # GFT_ACC_REUSE=0 switches it off (every forward then clears a fresh buffer, as before).
 _ACC_REUSE = _os.environ.get("GFT_ACC_REUSE", "1") != "0"
-_acc_pool = state.acc_pool         # (device, P) -> list of (buffer whose rows are zero, stream of its last kernels)
+# state.acc_pool: (device, P) -> list of (buffer whose rows are zero, stream of its last kernels)
 _ACC_POOL_DEPTH = 3
 
 
@@ -332,11 +391,11 @@ class _AccLease:
         buf, self.buf = self.buf, None
         if buf is None or not self.zero or not _ACC_REUSE or not self.pooled:
             return
-        pool = _acc_pool.setdefault(self.key, [])
+        pool = state.acc_pool.setdefault(self.key, [])
         pool.append((buf, self.stream))
         del pool[:-_ACC_POOL_DEPTH]
-        if len(_acc_pool) > 8:
-            _acc_pool.pop(next(iter(_acc_pool)))
+        if len(state.acc_pool) > 8:
+            state.acc_pool.pop(next(iter(state.acc_pool)))
 
     def __del__(self):
         # a forward whose backward never ran: the accumulator was not touched after the forward's clear
@@ -348,7 +407,7 @@ class _AccLease:
 
 def _take_acc(lib, dev, P, stream, any_stream=False, pooled=True, prezero=False):
     key = (dev.index, P)
-    pool = _acc_pool.get(key) if (_ACC_REUSE and pooled) else None
+    pool = state.acc_pool.get(key) if (_ACC_REUSE and pooled) else None
     if pool:
         for i, (buf, st) in enumerate(pool):
             if st == stream or any_stream:
@@ -495,6 +554,9 @@ def _guess_cap(hint, sched_cells=0):
 
 
 def _scratch(nbytes, dev):
+    # debug (GFT_POISON_SCRATCH=1): the scratch buffers start as 0x7f bytes (3.4e38 as a float, 2139062143 as an index) instead
+    # of whatever the allocator's block held -- usually the previous frame's plausible values --, so a kernel that reads a field
+    # no kernel of this frame wrote shows up in the parity tests
     t = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
     if _POISON:
         t.fill_(0x7f)
@@ -527,18 +589,177 @@ class _Settings(NamedTuple):
 
 
 _PLANE_SPLIT = (3, 7, 1, 3, 1, 1, 1, 1, 3)     # color, phasor, depth, normal, acc, entropy, depth_distortion, amp_distortion, distribution
-_PLANE_FIRST = (0, 3, 10, 11, 14, 15, 16, 17, 18)   # first plane of each output inside the [21, H, W] allocation
-_bw_plans = state.bw_plans
-_geom_bytes, _image_bytes = state.geom_bytes, state.image_bytes      # gft_geom_bytes(P), gft_image_bytes(W, H): one library call per size
 _FWD_FMT = "=%dQ" % len(_lib.ForwardIO._fields_)
 _BWD_FMT = "=%dQ" % len(_lib.BackwardIO._fields_)
 assert _struct.calcsize(_FWD_FMT) == C.sizeof(_lib.ForwardIO) and _struct.calcsize(_BWD_FMT) == C.sizeof(_lib.BackwardIO)
-_FWD_AT = {n: i for i, (n, _t) in enumerate(_lib.ForwardIO._fields_)}
-_BWD_AT = {n: i for i, (n, _t) in enumerate(_lib.BackwardIO._fields_)}
 
 
 def _p0(t):
     return 0 if t is None else t.data_ptr()
+
+
+def _save_snapshot(cpu_args, path, note):
+    """``raster_settings.debug``: the CPU copies of a failed call's arguments (taken before its launch), for whoever debugs it."""
+    if cpu_args is not None:
+        torch.save(cpu_args, path)
+        print(note)
+
+
+def _forward_inputs(s, means3D, sh, sh_p, colors_precomp, phasors_precomp, opacities, scales, rotations, cov3Ds_precomp, H, W):
+    """The arguments as the kernels read them (float32, contiguous, 16-byte aligned, on one device; absent: None):
+    (``inputs`` of native_forward's result, camera constants, background + strides)."""
+    dev = means3D.device
+    g = lambda t, n: _f32(t, dev, n) if _present(t) else None
+    means3D_c = _f32(means3D, dev, "means3D") if means3D.size(0) else means3D
+    sh_c, sh_p_c = g(sh, "shs"), g(sh_p, "shs_p")
+    colors_c, phasors_c = g(colors_precomp, "colors_precomp"), g(phasors_precomp, "phasors_precomp")
+    opac_c = g(opacities, "opacities")
+    scales_c, rot_c, cov_c = g(scales, "scales"), g(rotations, "rotations"), g(cov3Ds_precomp, "cov3D_precomp")
+    consts = (_f32(s.viewmatrix, dev, "viewmatrix"), _f32(s.projmatrix, dev, "projmatrix"), _f32(s.campos, dev, "campos"))
+    return ((means3D_c, opac_c, sh_c, sh_p_c, scales_c, rot_c, cov_c, colors_c, phasors_c), consts,
+            _bg_strides(s.bg, H, W, dev))
+
+
+def _forward_buffers(lib, dev, P, H, W):
+    """The outputs (nine images as planes of one allocation, radii, pixels) and the scratch buffers of known size."""
+    planes = torch.empty((21, H, W), device=dev, dtype=torch.float32)
+    radii = torch.empty((P,), device=dev, dtype=torch.int32)
+    pixels = torch.empty((P, 1), device=dev, dtype=torch.float32)
+    gb = state.geom_bytes.get(P)             # gft_geom_bytes(P), gft_image_bytes(W, H): one library call per size
+    if gb is None:
+        gb = state.geom_bytes[P] = int(lib.gft_geom_bytes(P))
+    ib = state.image_bytes.get((W, H))
+    if ib is None:
+        ib = state.image_bytes[(W, H)] = int(lib.gft_image_bytes(W, H))
+    return planes, radii, pixels, _scratch(gb, dev), _scratch(ib, dev)
+
+
+def _pack_forward_io(inputs, consts, bg_c, planes, pixels, radii, geom, img, off_dev):
+    """gft_forward_io in one pack (field order of the struct; the outputs' addresses from the one allocation they are
+    planes of): host time.  binning, acc and the camera's schedules are set by those who make them."""
+    means3D_c, opac_c, sh_c, sh_p_c, scales_c, rot_c, cov_c, colors_c, phasors_c = inputs
+    P = radii.size(0)
+    io = _lib.ForwardIO()
+    pl, hw4 = planes.data_ptr(), 4 * planes.size(1) * planes.size(2)
+    _struct.pack_into(_FWD_FMT, io, 0,
+                      _p0(bg_c), means3D_c.data_ptr() if P else 0, _p0(colors_c), _p0(phasors_c), _p0(opac_c), _p0(scales_c),
+                      _p0(rot_c), _p0(cov_c), consts[0].data_ptr(), consts[1].data_ptr(), consts[2].data_ptr(), _p0(sh_c),
+                      _p0(sh_p_c), geom.data_ptr(), img.data_ptr(), 0,
+                      pl, pl + 3 * hw4, pl + 10 * hw4, pl + 11 * hw4, pl + 14 * hw4, pl + 15 * hw4, pl + 16 * hw4, pl + 17 * hw4,
+                      pixels.data_ptr() if P else 0, pl + 18 * hw4, radii.data_ptr() if P else 0, 0, 0, 0, 0, 0, 0,
+                      *((0, 0) if off_dev is None else (_p0(off_dev[0]), _p0(off_dev[1]))))
+    return io
+
+
+def _update_hint(key, R, max_list=None, decay=0.95):
+    """state.instance_hint[key] as a slowly decaying maximum: alternating views of one scene (colour / ToF camera, random
+    training views) keep the larger count as the guess.  ``max_list`` None: the longest-list part is carried over."""
+    prev_r, prev_l = state.instance_hint.get(key, (0, 0))
+    r = max(R, int((prev_r or 0) * decay))
+    state.instance_hint[key] = (r, prev_l if max_list is None else max(max_list, int(prev_l * 0.95)))
+    if len(state.instance_hint) > state.MAX_SHAPES:
+        state.instance_hint.pop(next(iter(state.instance_hint)))
+    return r
+
+
+class _Launch:
+    """What the launch flows of one forward share."""
+    __slots__ = ("lib", "stream", "cfg", "io", "dev", "W", "H", "cam", "use_sched")
+
+    def __init__(self, lib, stream, cfg, io, dev, W, H, cam, use_sched):
+        self.lib, self.stream, self.cfg, self.io, self.dev, self.W, self.H = lib, stream, C.byref(cfg), io, dev, W, H
+        self.cam, self.use_sched = cam, use_sched
+
+    def alloc_binning(self, cap):
+        binning = _scratch(self.lib.gft_binning_bytes(cap, self.W, self.H), self.dev)
+        self.io.binning = binning.data_ptr()
+        return binning
+
+    def hints(self, cap, list_hint, use_sched=0):
+        n_tiles = ((self.W + 15) // 16) * ((self.H + 15) // 16)
+        return _lib.ForwardHints(binning_instances=cap, max_tile_list=int(list_hint * _LIST_HEADROOM) + 1,
+                                 whole_lists=_whole_lists(self.cam, n_tiles), use_cell_sched=use_sched)
+
+
+# The three launch flows: each returns (R, cap, binning, longest tile list, restarted).
+
+def _forward_no_host_read(fr, st, hint_key, hint, list_hint):
+    """gft_forward_enqueue: what earlier frames of the shape posted is read from pinned memory (``st``), not the device."""
+    a = st["np"]
+    if int(a[_ST_OVERFLOWS]) != st["seen"]:
+        # some earlier no-host-read frame of the shape did not fit its buffer (the device counts them in a word nothing
+        # clears: the posting of the frame itself may have been overwritten by a later frame's already)
+        n_over, st["seen"] = int(a[_ST_OVERFLOWS]) - st["seen"], int(a[_ST_OVERFLOWS])
+        worst = int(a[_ST_MAX_R])
+        _update_hint(hint_key, worst, decay=1)
+        raise RuntimeError("gftorf_amd: %d earlier no-host-read forward(s) of this shape had up to %d instances, "
+                           "more than their binning buffer held: their outputs were undefined (the buffer has "
+                           "been enlarged for the following frames)" % (n_over, worst))
+    if a[3]:
+        # the posting of an earlier no-host-read frame of the shape (whichever the copy in pinned memory holds)
+        prev_R = int(a[0])
+        a[3] = 0
+        if fr.cam is not None:
+            fr.cam.hinted_tiles = int(a[8])
+        if a[1] & 1:
+            raise RuntimeError("Point is filtered although prefiltered is set. This shouldn't happen!")
+        hint = _update_hint(hint_key, prev_R)
+    cap = _guess_cap(hint)
+    binning = fr.alloc_binning(cap)
+    hints = fr.hints(cap, list_hint)
+    _lib.check(fr.lib.gft_forward_enqueue(fr.stream, fr.cfg, C.byref(fr.io), C.byref(hints), st["dev"].data_ptr()))
+    st["host"].copy_(st["dev"], non_blocking=True)
+    return -1, cap, binning, 0, False          # (R is not known to the host)
+
+
+def _forward_first_frame(fr, hint_key):
+    """First frame of a shape: the buffer is sized after the one blocking read, like the reference's resize callback
+    (rasterize_points.cu:27-33, rasterizer_impl.cu:311-315)."""
+    _status_of(hint_key, fr.dev, create=True)      # (so that a later capture of this shape finds its status block)
+    num_rendered, max_list = C.c_int64(0), C.c_int64(0)
+    _lib.check(fr.lib.gft_forward_preprocess(fr.stream, fr.cfg, C.byref(fr.io), C.byref(num_rendered), C.byref(max_list)))
+    R = int(num_rendered.value)
+    cap = _canonical_cap(R)
+    binning = fr.alloc_binning(cap)
+    _lib.check(fr.lib.gft_forward_render(fr.stream, fr.cfg, C.byref(fr.io), cap, int(max_list.value)))
+    return R, cap, binning, int(max_list.value), False
+
+
+def _forward_hinted(fr, hint, list_hint):
+    """Later frames: the buffer is sized from the recent frames' instance counts, both stages are queued back to back;
+    a frame that needs more re-runs stage 2 with the exact size."""
+    cap = _guess_cap(hint, (fr.cam.cell_sched.numel() - 4) // 2 if fr.use_sched else 0)
+    binning = fr.alloc_binning(cap)
+    hints = fr.hints(cap, list_hint, fr.use_sched)
+    report = _lib.ForwardReport()
+    _lib.check(fr.lib.gft_forward(fr.stream, fr.cfg, C.byref(fr.io), C.byref(hints), C.byref(report)))
+    R, max_list = int(report.num_rendered), int(report.max_tile_list)
+    if fr.cam is not None:
+        fr.cam.take_report(report, fr.use_sched, R <= cap)
+    if R <= cap:
+        return R, cap, binning, max_list, False
+    cap = _canonical_cap(R)
+    binning = fr.alloc_binning(cap)
+    _lib.check(fr.lib.gft_forward_render(fr.stream, fr.cfg, C.byref(fr.io), cap, max_list))
+    return R, cap, binning, max_list, True
+
+
+def _launch_forward(fr, hint_key, capturing, nowait):
+    """Chooses the flow by what is known about the shape, and keeps the shape's size hint."""
+    hint, list_hint = state.instance_hint.get(hint_key, (None, 0))
+    st = _status_of(hint_key, fr.dev, create=not capturing) if (nowait and hint is not None) else None
+    if st is not None:
+        return _forward_no_host_read(fr, st, hint_key, hint, list_hint)
+    if nowait and capturing and hint is None:
+        raise RuntimeError("gftorf_amd: a forward captured in a graph sizes its binning buffer from earlier frames of the "
+                           "shape: render one frame of this shape (%d Gaussians, %dx%d) eagerly first" % hint_key[1:4])
+    if nowait and capturing:
+        raise RuntimeError("gftorf_amd: no status block for this shape: render one frame of it eagerly before capturing")
+    # (not capturing and nothing known about the shape yet -- the first frame of the process, a new P after a densification
+    # step -- takes the blocking two-stage flow once; it leaves the hint and the status block)
+    r = _forward_first_frame(fr, hint_key) if hint is None else _forward_hinted(fr, hint, list_hint)
+    _update_hint(hint_key, r[0], r[3])
+    return r
 
 
 def native_forward(s, means3D, sh, sh_p, colors_precomp, phasors_precomp, opacities, scales, rotations,
@@ -572,408 +793,202 @@ def native_forward(s, means3D, sh, sh_p, colors_precomp, phasors_precomp, opacit
     P = means3D.size(0)
     H, W = int(s.image_height), int(s.image_width)
 
-    g = lambda t, n: _f32(t, dev, n) if _present(t) else None
-    means3D_c = _f32(means3D, dev, "means3D") if P else means3D
-    sh_c, sh_p_c = g(sh, "shs"), g(sh_p, "shs_p")
-    colors_c, phasors_c = g(colors_precomp, "colors_precomp"), g(phasors_precomp, "phasors_precomp")
-    opac_c = g(opacities, "opacities")
-    scales_c, rot_c, cov_c = g(scales, "scales"), g(rotations, "rotations"), g(cov3Ds_precomp, "cov3D_precomp")
-    view_c = _f32(s.viewmatrix, dev, "viewmatrix")
-    proj_c = _f32(s.projmatrix, dev, "projmatrix")
-    campos_c = _f32(s.campos, dev, "campos")
-    bg_c, bsc, bsy, bsx = _bg_strides(s.bg, H, W, dev)
-    M = sh_c.size(1) if sh_c is not None else 0
-    M_p = sh_p_c.size(1) if sh_p_c is not None else 0
-
+    inputs, consts, bg = _forward_inputs(s, means3D, sh, sh_p, colors_precomp, phasors_precomp, opacities, scales, rotations,
+                                         cov3Ds_precomp, H, W)
+    means3D_c, opac_c, sh_c, sh_p_c, scales_c, rot_c, cov_c, colors_c, phasors_c = inputs
+    cpu_args = None
     if s.debug:
         cpu_args = cpu_deep_copy_tuple((s.bg, means3D, colors_precomp, phasors_precomp, opacities, scales,
                                         rotations, s.scale_modifier, cov3Ds_precomp, s.viewmatrix, s.projmatrix,
                                         s.tanfovx, s.tanfovy, s.image_height, s.image_width, sh, sh_p,
                                         s.sh_degree, s.campos, s.prefiltered, s.debug, s.near_n, s.far_n,
                                         s.depth_range, s.use_view_dependent_phase, ph_off, dc_off))
+    planes, radii, pixels, geom, img = _forward_buffers(lib, dev, P, H, W)
+    cfg = _make_config(s, P, sh_c.size(1) if sh_c is not None else 0, sh_p_c.size(1) if sh_p_c is not None else 0, H, W,
+                       ph_off, dc_off, bg[1:], want_bw)
+    io = _pack_forward_io(inputs, consts, bg[0], planes, pixels, radii, geom, img, off_dev)
 
-    f32 = dict(device=dev, dtype=torch.float32)
-    planes = torch.empty((21, H, W), **f32)
-    # (one split instead of nine slices: host time)
-    color, phasor, depth, normal, acc, entropy, depth_distortion, amp_distortion, distribution = planes.split(_PLANE_SPLIT)
-    radii = torch.empty((P,), device=dev, dtype=torch.int32)
-    pixels = torch.empty((P, 1), **f32)
-    gb = _geom_bytes.get(P)
-    if gb is None:
-        gb = _geom_bytes[P] = int(lib.gft_geom_bytes(P))
-    ib = _image_bytes.get((W, H))
-    if ib is None:
-        ib = _image_bytes[(W, H)] = int(lib.gft_image_bytes(W, H))
-    geom = torch.empty((gb,), device=dev, dtype=torch.uint8)
-    img = torch.empty((ib,), device=dev, dtype=torch.uint8)
-    if _POISON:
-        # debug (GFT_POISON_SCRATCH=1): the scratch buffers start as 0x7f bytes (3.4e38 as a float, 2139062143 as an index) instead
-        # of whatever the allocator's block held -- usually the previous frame's plausible values --, so a kernel that reads a field
-        # no kernel of this frame wrote shows up in the parity tests
-        geom.fill_(0x7f)
-        img.fill_(0x7f)
-
-    cfg = _make_config(s, P, M, M_p, H, W, ph_off, dc_off, (bsc, bsy, bsx), want_bw)
-    io = _lib.ForwardIO()
-    # (the argument block in one pack -- field order of gft_forward_io --, the outputs' addresses from the one allocation
-    # they are planes of: host time; binning, acc, grads_zero, tile_hints follow below)
-    pl, hw4 = planes.data_ptr(), 4 * H * W
-    _struct.pack_into(_FWD_FMT, io, 0,
-                      _p0(bg_c), means3D_c.data_ptr() if P else 0, _p0(colors_c), _p0(phasors_c), _p0(opac_c), _p0(scales_c),
-                      _p0(rot_c), _p0(cov_c), view_c.data_ptr(), proj_c.data_ptr(), campos_c.data_ptr(), _p0(sh_c), _p0(sh_p_c),
-                      geom.data_ptr(), img.data_ptr(), 0,
-                      pl, pl + 3 * hw4, pl + 10 * hw4, pl + 11 * hw4, pl + 14 * hw4, pl + 15 * hw4, pl + 16 * hw4, pl + 17 * hw4,
-                      pixels.data_ptr() if P else 0, pl + 18 * hw4, radii.data_ptr() if P else 0, 0, 0, 0, 0, 0, 0,
-                      *((0, 0) if off_dev is None else (_p0(off_dev[0]), _p0(off_dev[1]))))
-    # the backward's accumulator: cleared by the forward beside its binning kernels -- unless it comes from the pool of
-    # buffers that the last backward left zero (_AccLease)
-    lease = None
+    lease = prep = None
     if want_bw and with_acc and P:
+        # the backward's accumulator: cleared by the forward beside its binning kernels -- unless it comes from the pool of
+        # buffers that the last backward left zero (_AccLease) --, and the backward's gradient tensors and argument block,
+        # while the device is still busy with earlier work
         lease = _take_acc(lib, dev, P, stream if stream is not None else _lib.raw_stream(dev), acc_any_stream, pooled=not capturing,
                           prezero=nowait and not capturing)
+        if not lease.was_zero:
+            io.acc = lease.buf.data_ptr()
+        prep = prepare_backward(s, means3D_c, opac_c, sh_c, sh_p_c, scales_c, rot_c, cov_c, radii, geom, img, bg, consts,
+                                ph_off, dc_off, lease.buf, colors_c is not None, cov_c is not None, want_bw, pixels,
+                                share_grads=share_grads, acc_lease=lease, pooled=not capturing, off_dev=off_dev)
     acc_buf = lease.buf if lease is not None else None
-    io.acc = None if (lease is not None and lease.was_zero) else _ptr(acc_buf)
 
-    # the backward's gradient tensors and argument block, while the device is still busy with earlier work
-    prep = None
-    if want_bw and with_acc and P:
-        prep = prepare_backward(s, means3D_c, opac_c, sh_c, sh_p_c, scales_c, rot_c, cov_c, radii, geom, img,
-                                (bg_c, bsc, bsy, bsx), (view_c, proj_c, campos_c), ph_off, dc_off, acc_buf,
-                                colors_c is not None, cov_c is not None, want_bw, pixels,
-                                share_grads=share_grads, acc_lease=lease,
-                                pooled=not capturing, off_dev=off_dev)
-        if prep["zero_buf"] is not None:
-            io.grads_zero = prep["zero_buf"].data_ptr()
-            io.grads_zero_bytes = prep["zero_buf"].numel() * 4
-    R = cap = 0
-    restarted = False
-    max_list = C.c_int64(0)
     if P == 0:
-        # the reference skips every kernel and returns its zero-filled outputs
-        # (rasterize_points.cu:104)
+        # the reference skips every kernel and returns its zero-filled outputs (rasterize_points.cu:104)
         planes.zero_()
-        binning = torch.empty((0,), device=dev, dtype=torch.uint8)
+        R, cap, binning, max_list, restarted = 0, 0, torch.empty((0,), device=dev, dtype=torch.uint8), 0, False
     else:
         if stream is None:
             stream = _lib.raw_stream(dev)
         if pre_launch is not None:
             pre_launch()
-        num_rendered = C.c_int64(0)
         hint_key = (dev.index, P, W, H) if not hint_slot else (dev.index, P, W, H, hint_slot)
-        hint, list_hint = _instance_hint.get(hint_key, (None, 0))
-        # (a schedule buffer made during a capture would live in the graph's private pool: only one that exists already)
-        n_tiles = ((W + 15) // 16) * ((H + 15) // 16)
-        # (the schedules are about regions of the image as ONE CAMERA sees them -- which tiles hold the scene's silhouette
+        # The schedules are about regions of the image as ONE CAMERA sees them -- which tiles hold the scene's silhouette
         # differs from view to view: they are kept per image size and camera (_CameraSchedule), the camera being known by the
         # address of its view matrix (the reference's Camera objects keep theirs for the whole run, scene/cameras.py; a
         # caller that builds new matrices every call gets a fresh, empty schedule each time and evicts the oldest).  Not per
-        # number of Gaussians: they survive the densification steps, which change P every hundred iterations.)
+        # number of Gaussians: they survive the densification steps, which change P every hundred iterations.
         tiles_key = (dev.index, W, H, hint_slot, s.viewmatrix.data_ptr() if _TILE_HINTS_PER_CAMERA else 0)
-        # (a schedule buffer made during a capture would live in the graph's private pool: only what exists already)
         cam = state.camera(tiles_key, create=not capturing) if _TILE_HINTS else None
-        use_sched = 0
-        if cam is not None:
-            cam.frames += 1
-            if cam.tile_hints is None and not capturing:
-                cam.tile_hints = torch.zeros((n_tiles,), device=dev, dtype=torch.int32)
-            io.tile_hints = _ptr(cam.tile_hints)
-            if cam.tile_hints is not None and _CELL_SCHED:
-                if cam.cell_sched is None and not capturing:
-                    words = int(lib.gft_cell_sched_words(W, H))
-                    cam.cell_sched = torch.zeros((words,), device=dev, dtype=torch.int32) if words else False
-                if cam.cell_sched is not None and cam.cell_sched is not False:
-                    io.cell_sched = cam.cell_sched.data_ptr()
-                    use_sched = int(_force_cell_sched if _force_cell_sched is not None
-                                    else (cam.sched_seen and cam.frames >= cam.sched_off_until))
-            if cam.tile_hints is not None and _FWD_ORDER:
-                if cam.tile_weights is None and not capturing:
-                    cam.tile_weights = torch.zeros((4 * n_tiles + 4,), device=dev, dtype=torch.int32)
-                io.tile_weights = _ptr(cam.tile_weights)
+        use_sched = cam.attach(io, lib, dev, W, H, capturing) if cam is not None else 0
         try:
             with _lib.on_device(dev):
-                st = None
-                if nowait:
-                    st = _status_of(hint_key, dev, create=not capturing) if hint is not None else None
-                    if capturing and hint is None:
-                        raise RuntimeError("gftorf_amd: a forward captured in a graph sizes its binning buffer from earlier "
-                                           "frames of the shape: render one frame of this shape (%d Gaussians, %dx%d) eagerly "
-                                           "first" % (P, W, H))
-                    if capturing and st is None:
-                        raise RuntimeError("gftorf_amd: no status block for this shape: render one frame of it eagerly before "
-                                           "capturing")
-                    # (not capturing and nothing known about the shape yet -- the first frame of the process, a new P after a
-                    # densification step --: the blocking two-stage flow below, once; it leaves the hint and the status block)
-                if st is not None:
-                    a = st["np"]
-                    if int(a[_ST_OVERFLOWS]) != st["seen"]:
-                        # some earlier no-host-read frame of the shape did not fit its buffer (the device counts them in a word
-                        # nothing clears: the posting of the frame itself may have been overwritten by a later frame's already)
-                        n_over, st["seen"] = int(a[_ST_OVERFLOWS]) - st["seen"], int(a[_ST_OVERFLOWS])
-                        worst = int(a[_ST_MAX_R])
-                        prev_r, prev_l = _instance_hint.get(hint_key, (0, 0))
-                        _instance_hint[hint_key] = (max(worst, prev_r or 0), prev_l)
-                        raise RuntimeError("gftorf_amd: %d earlier no-host-read forward(s) of this shape had up to %d instances, "
-                                           "more than their binning buffer held: their outputs were undefined (the buffer has "
-                                           "been enlarged for the following frames)" % (n_over, worst))
-                    if a[3]:
-                        # the posting of an earlier no-host-read frame of the shape (whichever the copy in pinned memory holds)
-                        prev_R = int(a[0])
-                        a[3] = 0
-                        if cam is not None:
-                            cam.hinted_tiles = int(a[8])
-                        if a[1] & 1:
-                            raise RuntimeError("Point is filtered although prefiltered is set. This shouldn't happen!")
-                        prev_r, prev_l = _instance_hint.get(hint_key, (0, 0))
-                        _instance_hint[hint_key] = (max(prev_R, int((prev_r or 0) * 0.95)), prev_l)
-                        hint = _instance_hint[hint_key][0]
-                    cap = _guess_cap(hint)
-                    binning = _scratch(lib.gft_binning_bytes(cap, W, H), dev)
-                    io.binning = binning.data_ptr()
-                    hints = _lib.ForwardHints(binning_instances=cap, max_tile_list=int(list_hint * _LIST_HEADROOM) + 1,
-                                              whole_lists=_whole_lists(cam, n_tiles))
-                    _lib.check(lib.gft_forward_enqueue(stream, C.byref(cfg), C.byref(io), C.byref(hints), st["dev"].data_ptr()))
-                    st["host"].copy_(st["dev"], non_blocking=True)
-                    R = -1                     # (not known to the host)
-                elif hint is None:
-                    # first frame of this shape: size the buffer after the one blocking
-                    # read, like the reference's resize callback
-                    # (rasterize_points.cu:27-33, rasterizer_impl.cu:311-315)
-                    _status_of(hint_key, dev, create=True)      # (so that a later capture of this shape finds its status block)
-                    _lib.check(lib.gft_forward_preprocess(stream, C.byref(cfg), C.byref(io),
-                                                          C.byref(num_rendered), C.byref(max_list)))
-                    R = int(num_rendered.value)
-                    cap = _canonical_cap(R)
-                    binning = _scratch(lib.gft_binning_bytes(cap, W, H), dev)
-                    io.binning = binning.data_ptr()
-                    _lib.check(lib.gft_forward_render(stream, C.byref(cfg), C.byref(io), cap, int(max_list.value)))
-                else:
-                    # later frames: the buffer is sized from the recent frames' instance counts (the only thing taken
-                    # from earlier frames), both stages are queued back to back
-                    cap = _guess_cap(hint, (cam.cell_sched.numel() - 4) // 2 if (cam is not None and use_sched) else 0)
-                    binning = _scratch(lib.gft_binning_bytes(cap, W, H), dev)
-                    io.binning = binning.data_ptr()
-                    hints = _lib.ForwardHints(binning_instances=cap, max_tile_list=int(list_hint * _LIST_HEADROOM) + 1,
-                                              whole_lists=_whole_lists(cam, n_tiles), use_cell_sched=use_sched)
-                    report = _lib.ForwardReport()
-                    _lib.check(lib.gft_forward(stream, C.byref(cfg), C.byref(io), C.byref(hints), C.byref(report)))
-                    R = int(report.num_rendered)
-                    if use_sched:
-                        # (a camera whose lists keep outgrowing what its last frame left -- its tensors shared by scenes of
-                        # different sizes, say -- pays the counted flow ON TOP of the failed attempt: after four misses in a row
-                        # it counts again for 64 frames, then tries anew.  A frame that did not fit the BINNING BUFFER either is
-                        # re-rendered below whatever the schedule said: not the schedule's miss.)
-                        if report.sched_misses:
-                            last_call_stats["sched_misses"] = last_call_stats.get("sched_misses", 0) + 1
-                            if R <= cap:
-                                cam.miss_streak += 1
-                                if cam.miss_streak >= _SCHED_MISSES_OFF and _force_cell_sched is None:
-                                    cam.miss_streak = 0
-                                    cam.sched_off_until = cam.frames + _SCHED_OFF_FRAMES
-                        else:
-                            cam.miss_streak = 0
-                    if cam is not None:
-                        cam.hinted_tiles = int(report.hinted_tiles)
-                    max_list.value = int(report.max_tile_list)
-                    if R > cap:
-                        restarted = True
-                        cap = _canonical_cap(R)
-                        binning = _scratch(lib.gft_binning_bytes(cap, W, H), dev)
-                        io.binning = binning.data_ptr()
-                        _lib.check(lib.gft_forward_render(stream, C.byref(cfg), C.byref(io), cap, int(max_list.value)))
-                # slowly decaying maximum: alternating views of one scene (colour / ToF camera,
-                # random training views) keep the larger count as the guess
-                if st is None:
-                    prev_r, prev_l = _instance_hint.get(hint_key, (0, 0))
-                    _instance_hint[hint_key] = (max(R, int((prev_r or 0) * 0.95)), max(int(max_list.value), int(prev_l * 0.95)))
-                    if len(_instance_hint) > state.MAX_SHAPES:
-                        _instance_hint.pop(next(iter(_instance_hint)))
-        except Exception as ex:
-            if s.debug:
-                torch.save(cpu_args, "snapshot_fw.dump")
-                print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
-            raise ex
-    if P and io.cell_sched:
-        cam.sched_seen = True
+                R, cap, binning, max_list, restarted = _launch_forward(
+                    _Launch(lib, stream, cfg, io, dev, W, H, cam, use_sched), hint_key, capturing, nowait)
+        except Exception:
+            _save_snapshot(cpu_args, "snapshot_fw.dump",
+                           "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
+            raise
+        if io.cell_sched:
+            cam.sched_seen = True          # (a counted frame has written the camera's list schedule)
     if prep is not None:
-        prep["cap"] = cap
+        prep.cap = cap
     if lease is not None:
         lease.zero = True          # (cleared by this forward, or zero since its last backward)
 
-    last_call_stats.update(num_rendered=R, binning_instances=cap, restarted=restarted,
-                           max_tile_list=int(max_list.value) if P else 0)
-    if keep_last_buffers:
-        last_call_buffers.update(geom=geom, img=img, binning=binning, P=P, W=W, H=H, cap=cap)
+    last_call_stats.update(num_rendered=R, binning_instances=cap, restarted=restarted, max_tile_list=max_list)
     last_call_stats["forwards"] = last_call_stats.get("forwards", 0) + 1
     last_call_stats["restarts"] = last_call_stats.get("restarts", 0) + int(restarted)
+    if keep_last_buffers:
+        last_call_buffers.update(geom=geom, img=img, binning=binning, P=P, W=W, H=H, cap=cap)
+    # (one split instead of nine slices: host time)
+    color, phasor, depth, normal, acc, entropy, depth_distortion, amp_distortion, distribution = planes.split(_PLANE_SPLIT)
     return dict(R=R, cap=cap, outputs=(color, phasor, depth, normal, acc, entropy, depth_distortion, amp_distortion,
                                        pixels, distribution, radii),
-                geom=geom, binning=binning, img=img, acc=acc_buf, prep=prep, bg=(bg_c, bsc, bsy, bsx),
-                consts=(view_c, proj_c, campos_c),
-                inputs=(means3D_c, opac_c, sh_c, sh_p_c, scales_c, rot_c, cov_c, colors_c, phasors_c))
+                geom=geom, binning=binning, img=img, acc=acc_buf, prep=prep, bg=bg, consts=consts, inputs=inputs)
 
 
-def prepare_backward(s, means3D, opac, sh, sh_p, scales, rotations, cov3D, radii, geom, img, bg, consts, ph_off, dc_off,
-                     acc, want_colors, want_cov, want_bw_records=True, pixels=None, zero_fill=False, share_grads=None,
-                     acc_lease=None, pooled=True, off_dev=None):
-    """Everything of a backward that does not depend on the upstream gradients: the gradient tensors, the argument
-    block, the config.  The forward calls it BEFORE it queues its kernels, so that this host work overlaps the device's
-    previous work instead of sitting between the forward's last kernel and the backward's first one."""
-    lib = _lib.load()
-    dev = means3D.device
-    P = means3D.size(0)
-    H, W = int(s.image_height), int(s.image_width)
-    bg_c, bsc, bsy, bsx = bg
-    view_c, proj_c, campos_c = consts
-    has_sh, has_sh_p, has_scales, has_cov = sh is not None, sh_p is not None, scales is not None, cov3D is not None
-    M = sh.size(1) if has_sh else 0
-    M_p = sh_p.size(1) if has_sh_p else 0
-    f32 = dict(device=dev, dtype=torch.float32)
-    # (shapes, padded sizes and split of the gradient buffer: the same for every call of a training loop -- computed once)
+class _Prep:
+    """The hand-over from a forward to its backward: what :func:`prepare_backward` makes before the upstream gradients exist.
+    ``grads``: name -> gradient tensor or None; ``pool_entry``: the kept set this backward writes (second view of a pair:
+    adds to), None with fresh tensors; ``cap``: instances of the forward's binning buffer, None: read back from its size."""
+    __slots__ = ("grads", "cfg", "io", "acc", "acc_lease", "dev", "P", "H", "W", "pool_entry", "cap", "debug_args")
+
+    def __init__(self, grads, cfg, io, acc, acc_lease, dev, P, H, W, pool_entry, debug_args):
+        self.grads, self.cfg, self.io, self.acc, self.acc_lease = grads, cfg, io, acc, acc_lease
+        self.dev, self.P, self.H, self.W = dev, P, H, W
+        self.pool_entry, self.debug_args = pool_entry, debug_args
+        self.cap = None
+
+
+class _GradPlan(NamedTuple):
+    shapes: dict          # name -> shape of the gradient tensor, None: not asked for
+    sizes: dict           # name -> floats it takes in the one buffer (padded to 16 bytes), in the buffer's order
+    total: int            # floats of the buffer: the sizes + the two scalar offset gradients (padded)
+    split_sizes: list
+    layout_key: tuple
+    numels: list
+
+
+def _backward_plan(P, M, M_p, want_colors, want_cov, has_sh, has_sh_p, has_scales):
+    """Shapes, padded sizes and split of the gradient buffer: the same for every call of a training loop -- computed once."""
     plan_key = (P, M, M_p, want_colors, want_cov, has_sh, has_sh_p, has_scales)
-    plan = _bw_plans.get(plan_key)
+    plan = state.bw_plans.get(plan_key)
     if plan is None:
         shapes = dict(means3D=(P, 3), means2D=(P, 3), opacities=(P, 1), colors=(P, 3) if want_colors else None,
                       cov3D=(P, 6) if want_cov else None, sh=(P, M, 3) if has_sh else None,
                       sh_p=(P, M_p, 2) if has_sh_p else None, scales=(P, 3) if has_scales else None,
                       rotations=(P, 4) if has_scales else None)
         sizes = {k: (_prod(v) + 3) // 4 * 4 for k, v in shapes.items() if v is not None}
-        keys = [k for k, v in shapes.items() if v is not None]
-        if len(_bw_plans) > 64:
-            _bw_plans.clear()
-        plan = _bw_plans[plan_key] = (shapes, sizes, sum(sizes.values()) + 4, keys, [sizes[k] for k in keys] + [4],
-                                      tuple(sorted(sizes.items())), [_prod(shapes[k]) for k in keys])
-    shapes, sizes, total, keys, split_sizes, layout_key, numels = plan
-    zero_buf = None
-    entry, reused_grads = None, False
-    pool_entry = None              # the kept set of gradient tensors this backward writes (or, second view of a pair, adds to)
+        if len(state.bw_plans) > 64:
+            state.bw_plans.clear()
+        plan = state.bw_plans[plan_key] = _GradPlan(shapes, sizes, sum(sizes.values()) + 4, list(sizes.values()) + [4],
+                                                    tuple(sorted(sizes.items())), [_prod(shapes[k]) for k in sizes])
+    return plan
+
+
+def _grad_views(buf, plan):
+    """name -> gradient tensor, each a contiguous, 16-byte aligned slice of ``buf``, the two offset gradients at its end."""
+    # (one split into the padded pieces, then one view each: host time)
+    pieces = buf.split(plan.split_sizes)
+    g = dict.fromkeys(plan.shapes)
+    for (k, size), piece, n in zip(plan.sizes.items(), pieces, plan.numels):
+        g[k] = (piece if n == size else piece[:n]).view(plan.shapes[k])
+    g["offsets"] = pieces[-1][:2]
+    return g
+
+
+def _check_kept_rows(entry, g, P):
+    """GFT_GRADS_REUSE_CHECK=1: the rows of a kept set that its last backward did not mark must still be zero."""
+    clean = entry.dirty[:P] == 0
+    for k, t in g.items():
+        if t is not None and k != "offsets" and bool(t.reshape(P, -1)[clean].ne(0).any()):
+            raise RuntimeError("gftorf_amd: the kept gradient tensor '%s' holds non-zero rows the last backward did not "
+                               "write -- somebody wrote to it past the version counter (`.data`, a raw pointer); "
+                               "set GFT_GRADS_REUSE=0 for such a caller" % k)
+
+
+def prepare_backward(s, means3D, opac, sh, sh_p, scales, rotations, cov3D, radii, geom, img, bg, consts, ph_off, dc_off,
+                     acc, want_colors, want_cov, want_bw_records=True, pixels=None, share_grads=None,
+                     acc_lease=None, pooled=True, off_dev=None):
+    """Everything of a backward that does not depend on the upstream gradients: the gradient tensors, the argument
+    block, the config.  The forward calls it BEFORE it queues its kernels, so that this host work overlaps the device's
+    previous work instead of sitting between the forward's last kernel and the backward's first one."""
+    dev = means3D.device
+    P = means3D.size(0)
+    H, W = int(s.image_height), int(s.image_width)
+    has_sh, has_sh_p, has_scales, has_cov = sh is not None, sh_p is not None, scales is not None, cov3D is not None
+    M = sh.size(1) if has_sh else 0
+    M_p = sh_p.size(1) if has_sh_p else 0
+    plan = _backward_plan(P, M, M_p, want_colors, want_cov, has_sh, has_sh_p, has_scales)
+    entry, reused = None, False
     if share_grads is not None:
-        pool_entry = share_grads.get("pool_entry")
         # second view of a pair (gftorf_amd.pair): its backward adds to the first view's gradient tensors
-        # (cfg.grads_accumulate); only the two scalar offset gradients are its own
-        g = {k: v for k, v in share_grads["grads"].items() if k != "offsets"}
+        # (cfg.grads_accumulate) and marks its rows in the same array; only the two scalar offset gradients are its own
+        entry = share_grads.pool_entry
+        g = {k: v for k, v in share_grads.grads.items() if k != "offsets"}
+        g["offsets"] = torch.empty((2,), device=dev, dtype=torch.float32)
     else:
-        # One allocation for all per-Gaussian gradients (every tensor a contiguous slice, 16-byte aligned; the two scalar
-        # offset gradients at its end): ten torch.empty calls less per forward, which at the reference's scene size
-        # (100 k Gaussians, 0.1 ms of kernels per call) is host time the device waits for.  With the zero-fill switch
-        # the forward clears it beside its binning kernels and the backward writes only the rows of blended Gaussians.
-        entry = None
-        if _GRADS_REUSE and pooled and P and pixels is not None and want_bw_records and not zero_fill:
-            key = (dev.index, P, layout_key)
-            pool = _grad_pool.setdefault(key, [])
-            if _USE_COUNT_API:
-                # (a buffer somebody wrote to through a tensor -- autograd's in-place sum of two calls' gradients, clipping
-                # -- is never trusted again: forgotten as soon as nobody references it)
-                pool[:] = [e for e in pool if e["buf"]._version == e["version"] or _storage_refs(e["buf"]) != e["base"]]
-                free = [e for e in pool if _storage_refs(e["buf"]) == e["base"] and e["buf"]._version == e["version"]]
-            else:
-                # (DLPack route: the references that kept autograd from taking the tensors over are dropped now; an alias
-                # nobody else holds dies right here and its deleter marks the entry free.  An entry that is still waiting for
-                # its backward -- forward A, forward B, A.backward(), B.backward() -- loses that protection before autograd
-                # has seen its tensors: they may become a leaf's `.grad` and take the other call's gradient in place, which
-                # an alias's dead version counter cannot show.  Such an entry is never trusted to be zero outside its marked
-                # rows again: `spoiled` keeps `valid` off, so its next user writes it in full.)
-                for e in pool:
-                    if e["held"] is not None and not e["valid"]:
-                        e["spoiled"] = True
-                    e["held"] = None
-                free = [e for e in pool if e["free"]]
-            # `valid`: the last backward into this buffer returned without error, so every row is defined -- zero or marked
-            # in `dirty`.  A buffer that was handed to a forward whose backward never ran (a render under grad used only
-            # for logging, a loss skipped by a NaN guard) or failed holds rows nobody wrote: it may be taken again, but as
-            # a fresh one that the backward writes in full.
-            for e in free:
-                if e["valid"]:
-                    entry, reused_grads = e, True
-                    break
-            if entry is None and free:
-                entry = free[0]
-            if entry is None:
-                buf = torch.empty((total,), **f32)
-                # (`dirty`: a mark per Gaussian + the 144 bytes behind them in which the rows backward counts; `report`: pinned
-                # host word into which it stores the number of rows it wrote -- gft_backward_io.rows_report)
-                report = _report_slot()
-                entry = dict(buf=buf, dirty=torch.zeros(((P + 3) // 4 * 4 + 144,), device=dev, dtype=torch.uint8), version=buf._version,
-                             valid=False, report=report, report_np=report.numpy(), dense_left=0)
-                if _USE_COUNT_API:
-                    entry["base"] = _storage_refs(buf)
-                else:
-                    entry.update(mem=buf, buf=None, free=True, held=None)
-                pool.append(entry)
-                del pool[:-_GRAD_POOL_DEPTH]
-                if len(_grad_pool) > 8:
-                    _grad_pool.pop(next(iter(_grad_pool)))
-            entry["valid"] = False        # until the backward of this forward has returned (run_backward)
-            entry["spoiled"] = False
-            buf = entry["buf"] if _USE_COUNT_API else _dl_alias(entry)
-            pool_entry = entry
-        else:
-            buf = torch.empty((total,), **f32)
-        if zero_fill:
-            zero_buf = buf
-        # (one split into the padded pieces, then one view each: host time)
-        pieces = buf.split(split_sizes)
-        g = dict.fromkeys(shapes)
-        for k, piece, n in zip(keys, pieces, numels):
-            g[k] = (piece if n == sizes[k] else piece[:n]).view(shapes[k])
-        g["offsets"] = pieces[-1][:2]
-        if entry is not None and not _USE_COUNT_API:
-            entry["held"] = (buf, [t for t in g.values() if t is not None])
-        if reused_grads and _GRADS_CHECK:
-            clean = entry["dirty"][:P] == 0
-            for k, t in g.items():
-                if t is not None and k != "offsets" and bool(t.reshape(P, -1)[clean].ne(0).any()):
-                    raise RuntimeError("gftorf_amd: the kept gradient tensor '%s' holds non-zero rows the last backward did not "
-                                       "write -- somebody wrote to it past the version counter (`.data`, a raw pointer); "
-                                       "set GFT_GRADS_REUSE=0 for such a caller" % k)
-    if "offsets" not in g:
-        g["offsets"] = torch.empty((2,), **f32)
+        # One allocation for all per-Gaussian gradients: ten torch.empty calls less per forward, which at the reference's
+        # scene size (100 k Gaussians, 0.1 ms of kernels per call) is host time the device waits for.
+        if _GRADS_REUSE and _USE_COUNT_API and pooled and P and pixels is not None and want_bw_records:
+            entry, reused = _take_grads(dev, P, plan.total, plan.layout_key)
+        g = _grad_views(entry.buf if entry is not None else torch.empty((plan.total,), device=dev, dtype=torch.float32), plan)
+        if reused and _GRADS_CHECK:
+            _check_kept_rows(entry, g, P)
+    # (a reused set: the backward zeroes the rows the previous one wrote and this one does not, then writes its own
+    # -- cfg.grads_zeroed = 3 -- or writes everything, _GradEntry.write_mode; `sample`: it reports its row count)
+    rows_only, sample = entry.write_mode(P) if reused else (False, False)
     acc_zeroed = acc is not None
     if acc is None:            # second backward through the same forward (retain_graph), or the pybind-level route
-        acc = torch.empty((lib.gft_acc_bytes(P) // 4,), **f32)
-    cfg = _make_config(s, P, M, M_p, H, W, ph_off, dc_off, (bsc, bsy, bsx), want_bw_records)
+        acc = torch.empty((_lib.load().gft_acc_bytes(P) // 4,), device=dev, dtype=torch.float32)
+    cfg = _make_config(s, P, M, M_p, H, W, ph_off, dc_off, bg[1:], want_bw_records)
     # (2: the backward leaves the accumulator zero again -- the buffer goes back to the pool, _AccLease)
     cfg.acc_zeroed = 2 if (acc_zeroed and acc_lease is not None and _ACC_REUSE and acc_lease.pooled) else int(acc_zeroed)
-    # A kept set of gradient tensors is rewritten row by row only while few rows are written (a dense frame blends a few
-    # per cent of its Gaussians): the rows kernel stores its rows straight from the lanes, and from about a third of the
-    # Gaussians on the full write through LDS -- coalesced, zeros included -- is faster (C3-shaped frame, 96 % blended: 16 vs
-    # 54 us; fog: 140 vs 203 us).  The last rows backward has left its row count in pinned memory: above _DENSE_SHARE the
-    # next _DENSE_RUN backwards into these tensors write them in full (which marks every row), then one rows backward
-    # looks again.
-    rows_only = reused_grads
-    sample = False                 # this backward reports its row count (the report costs the rows kernel ~4 us: every 16th call)
-    if reused_grads and pool_entry is not None and "report_np" in pool_entry:
-        e = pool_entry
-        if e["dense_left"] > 0:
-            e["dense_left"] -= 1
-            rows_only = False
-            e["probe"] = e["dense_left"] == 0
-        elif int(e["report_np"][0]) > _DENSE_SHARE * P:
-            e["dense_left"] = _DENSE_RUN
-            e["report_np"][0] = 0
-            rows_only = False
-        else:
-            e["tick"] = e.get("tick", 0) + 1
-            sample = e.get("probe", False) or e["tick"] <= 2 or e["tick"] % 16 == 0
-            e["probe"] = False
-    cfg.grads_zeroed = 3 if rows_only else int(zero_buf is not None)
+    cfg.grads_zeroed = 3 if rows_only else 0
     cfg.grads_accumulate = int(share_grads is not None)
-    if share_grads is not None and share_grads.get("dirty") is not None:
-        # second view of a pair: its rows are added to the first view's tensors and marked in the same array
-        entry = dict(dirty=share_grads["dirty"])
-    io = _lib.BackwardIO()
+    io = _pack_backward_io(s, g, (means3D, opac, sh, sh_p, scales, rotations, cov3D), consts, bg[0], radii, pixels, geom, img, acc,
+                           entry.dirty.data_ptr() if entry is not None else 0, entry.report.data_ptr() if sample else 0, off_dev)
+    last_call_stats["grads_reused"] = reused
+    last_call_stats["grads_rows_only"] = rows_only
+    debug_args = (s.bg, means3D, radii, scales, rotations, s.scale_modifier, cov3D, s.viewmatrix, s.projmatrix,
+                  s.tanfovx, s.tanfovy, sh, sh_p, s.sh_degree, s.campos, s.debug, s.near_n, s.far_n, s.depth_range,
+                  s.use_view_dependent_phase, ph_off, dc_off) if s.debug else None
+    return _Prep(g, cfg, io, acc, acc_lease, dev, P, H, W, entry, debug_args)
+
+
+def _pack_backward_io(s, g, inputs, consts, bg_c, radii, pixels, geom, img, acc, dirty_ptr, report_ptr, off_dev):
+    """gft_backward_io in one pack; the upstream gradients, binning and det_partials follow in run_backward."""
+    means3D, opac, sh, sh_p, scales, rotations, cov3D = inputs
+    P = means3D.size(0)
     # the two scalar gradients cost a reduction launch: only when the caller optimises an offset (the reference returns
     # None for them otherwise, __init__.py:202-203); the pybind-level route always returns them
     want_off = getattr(s, "optimize_phase_offset", True) or getattr(s, "optimize_dc_offset", True)
     off_ptr = g["offsets"].data_ptr() if want_off else 0
-    # (cfg.grads_zeroed = 3: the backward zeroes the rows the previous one wrote and this one does not, then writes its own)
-    dirty_ptr = entry["dirty"].data_ptr() if entry is not None else 0
-    report_ptr = entry["report"].data_ptr() if (entry is not None and sample and entry.get("report") is not None) else 0
-    # (the argument block in one pack, field order of gft_backward_io; the upstream gradients, binning and det_partials follow
-    # in run_backward)
+    io = _lib.BackwardIO()
     _struct.pack_into(_BWD_FMT, io, 0,
                       _p0(bg_c), means3D.data_ptr() if P else 0, radii.data_ptr() if P else 0,
-                      _p0(scales) if has_scales else 0, _p0(rotations) if has_scales else 0, _p0(cov3D) if has_cov else 0,
-                      view_c.data_ptr(), proj_c.data_ptr(), campos_c.data_ptr(), _p0(sh) if has_sh else 0, _p0(sh_p) if has_sh_p else 0,
+                      _p0(scales), _p0(rotations) if scales is not None else 0, _p0(cov3D),
+                      consts[0].data_ptr(), consts[1].data_ptr(), consts[2].data_ptr(), _p0(sh), _p0(sh_p),
                       _p0(opac) if P else 0, _p0(pixels) if P else 0,
                       0, 0, 0, 0, 0,
                       geom.data_ptr(), img.data_ptr(), 0, acc.data_ptr() if P else 0,
@@ -981,20 +996,14 @@ def prepare_backward(s, means3D, opac, sh, sh_p, scales, rotations, cov3D, radii
                       g["opacities"].data_ptr() if P else 0, _p0(g["cov3D"]), _p0(g["sh"]), _p0(g["sh_p"]), _p0(g["scales"]),
                       _p0(g["rotations"]), off_ptr, off_ptr + 4 if off_ptr else 0, 0, dirty_ptr, report_ptr,
                       *((0, 0) if off_dev is None else (_p0(off_dev[0]), _p0(off_dev[1]))))
-    last_call_stats["grads_reused"] = bool(reused_grads)
-    last_call_stats["grads_rows_only"] = bool(rows_only)
-    return dict(grads=g, cfg=cfg, io=io, acc=acc, acc_lease=acc_lease, pixels=pixels, zero_buf=zero_buf, dev=dev, P=P, H=H, W=W,
-                dirty=entry["dirty"] if entry is not None else None, pool_entry=pool_entry,
-                debug_args=(s.bg, means3D, radii, scales, rotations, s.scale_modifier, cov3D, s.viewmatrix, s.projmatrix,
-                            s.tanfovx, s.tanfovy, sh, sh_p, s.sh_degree, s.campos, s.debug, s.near_n, s.far_n, s.depth_range,
-                            s.use_view_dependent_phase, ph_off, dc_off) if s.debug else None)
+    return io
 
 
 def run_backward(prep, grads_out, geom, binning, img, debug=False):
     """The rest of a backward: the upstream gradients (color, phasor, depth, acc, depth_distortion; None = zeros) and the
     launch (``RasterizeGaussiansBackwardCUDA``, rasterize_points.cu:167-281).  Returns the dict of gradient tensors."""
     lib = _lib.load()
-    dev, P, H, W, io = prep["dev"], prep["P"], prep["H"], prep["W"], prep["io"]
+    dev, P, H, W, io = prep.dev, prep.P, prep.H, prep.W, prep.io
 
     def gr(t, c, name):
         # gradients of normal / entropy / amp_distortion / pixels / distribution are
@@ -1011,7 +1020,7 @@ def run_backward(prep, grads_out, geom, binning, img, debug=False):
     io.dL_dout_depth, io.dL_dout_acc, io.dL_dout_depth_distortion = _ptr(keep[2]), _ptr(keep[3]), _ptr(keep[4])
     io.geom, io.img, io.binning = _ptr(geom), _ptr(img), _ptr(binning)
     det = None
-    cap = prep.get("cap")              # (known to the forward that made `prep`; else read back from the buffer's size)
+    cap = prep.cap                     # (known to the forward that made `prep`; else read back from the buffer's size)
     if cap is None:
         cap = binning_capacity(binning, W, H) if P else 0
     if _DETERMINISTIC and P and cap:
@@ -1021,31 +1030,25 @@ def run_backward(prep, grads_out, geom, binning, img, debug=False):
         # library clears with a kernel now, gft_api.hip gft_zero_async)
         det = torch.empty((lib.gft_det_partials_bytes(cap, W, H) // 4,), dtype=torch.float32, device=dev)
         io.det_partials = det.data_ptr()
-    if debug:
-        cpu_args = cpu_deep_copy_tuple(prep["debug_args"] + tuple(grads_out) + (geom, binning, img))
-    lease = prep.get("acc_lease")
+    cpu_args = cpu_deep_copy_tuple(prep.debug_args + tuple(grads_out) + (geom, binning, img)) if debug else None
+    lease, pool_entry = prep.acc_lease, prep.pool_entry
     if lease is not None:
         lease.zero = False             # the render backward writes to it; zero again only if the call below returns
-    pool_entry = prep.get("pool_entry")
     try:
         with _lib.on_device(dev):
             stream = _lib.raw_stream(dev)
-            _lib.check(lib.gft_backward(stream, C.byref(prep["cfg"]), C.byref(io), cap))
-        if pool_entry is not None and not prep["cfg"].grads_accumulate:
-            # every row of the kept gradient tensors is defined now (api._grad_pool) -- unless, on the DLPack route, another
-            # forward of the shape let go of them before this backward ran
-            pool_entry["valid"] = not pool_entry.get("spoiled", False)
-        if lease is not None and prep["cfg"].acc_zeroed == 2:
+            _lib.check(lib.gft_backward(stream, C.byref(prep.cfg), C.byref(io), cap))
+        if pool_entry is not None and not prep.cfg.grads_accumulate:
+            pool_entry.valid = True    # every row of the kept gradient tensors is defined now (_GradEntry)
+        if lease is not None and prep.cfg.acc_zeroed == 2:
             lease.zero, lease.stream = True, stream
             lease.give_back()
-    except Exception as ex:
+    except Exception:
         if pool_entry is not None:
-            pool_entry["valid"] = False
-        if debug:
-            torch.save(cpu_args, "snapshot_bw.dump")
-            print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
-        raise ex
-    return prep["grads"]
+            pool_entry.valid = False
+        _save_snapshot(cpu_args, "snapshot_bw.dump", "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
+        raise
+    return prep.grads
 
 
 def native_backward(s, means3D, opac, sh, sh_p, scales, rotations, cov3D, radii, geom, binning, img, bg, consts,

@@ -113,7 +113,7 @@ class _RasterizePair(torch.autograd.Function):
             prep = preps[v]
             if prep is not None:
                 # the second view adds to the first one's tensors -- unless it is the only one with a gradient
-                prep["cfg"].grads_accumulate = int(g is not None)
+                prep.cfg.grads_accumulate = int(g is not None)
                 res = run_backward(prep, go, geom, binning, img, bool(s.debug))
             else:                                     # second backward through the same forward (retain_graph)
                 res = native_backward(s, means3D, opac, sh if has_sh else None, sh_p if has_sh_p else None,

@@ -20,6 +20,6 @@ for it in range(40):
     o = rast(means3D=leaf["means3D"], means2D=m2, opacities=leaf["opacities"], shs=leaf["shs"], shs_p=leaf["shs_p"], scales=leaf["scales"], rotations=leaf["rotations"], phase_offset=sc["phase_offset"], dc_offset=sc["dc_offset"])
     torch.autograd.backward([o[0], o[1], o[2], o[4], o[6]], ups)
     pool = next(iter(api._grad_pool.values()))
-    log.append((api.last_call_stats["grads_reused"], api.last_call_stats["grads_rows_only"], [int(e["report_np"][0]) for e in pool], [e["dense_left"] for e in pool], len(pool)))
+    log.append((api.last_call_stats["grads_reused"], api.last_call_stats["grads_rows_only"], [int(e.report_np[0]) for e in pool], [e.dense_left for e in pool], len(pool)))
 torch.cuda.synchronize()
 for l in log: print(l)

@@ -3,7 +3,7 @@ of test_gpu_parity.py).  One generator for the builder's long soak (profiles/soa
 it that runs inside the GPU suite (tests/test_gpu_soak.py, ~200 frames): sizes, ragged image shapes, SH degrees, opacity
 regimes (saturating ... fog), splat sizes (deep lists, heads of 940 exceeded), ToF on / off -- and the mode product of the
 operator: both binning structures, both forward blend kernels, the per-tile schedule (none / as the frames leave it / all
-ones / random), gradient tensors fresh / kept (rows or full rewrite) on the use-count or the DLPack route, accumulator kept
+ones / random), gradient tensors fresh / kept (rows or full rewrite) with or without torch's storage use count, accumulator kept
 or cleared."""
 import json
 import time
@@ -29,7 +29,7 @@ def draw_case(rng):
         bin_mode=int(rng.integers(2)), render_mode=int(rng.integers(2)),
         hints=["off", "keep", "ones", "random"][int(rng.integers(4))],
         grads=["fresh", "kept", "kept_full"][int(rng.integers(3))],
-        dlpack=bool(rng.random() < 0.25),
+        no_use_count=bool(rng.random() < 0.25),     # torch without the private counter: nothing is kept
         acc_kept=bool(rng.random() < 0.7))
     # the camera (None: the centred one; or a sensor camera of helpers.CAMERAS), from a generator of its own: the sequence
     # of cases is the same with and without it
@@ -61,10 +61,7 @@ def run_case(case, dev, oracle, rng, cameras=False):
         api._TILE_HINTS = c["hints"] != "off"
         api._GRADS_REUSE = c["grads"] != "fresh"
         api._ACC_REUSE = c["acc_kept"]
-        want_use_count = keep[2] and not c["dlpack"]
-        if api._USE_COUNT_API != want_use_count:
-            api._grad_pool.clear()                      # (an entry belongs to the route that made it)
-            api._USE_COUNT_API = want_use_count
+        api._USE_COUNT_API = keep[2] and not c["no_use_count"]
         if c["hints"] in ("ones", "random"):
             # (the schedule of the image size: a frame's camera tensors are new every case, so the per-camera key is off)
             T_ = ((c["W"] + 15) // 16) * ((c["H"] + 15) // 16)
@@ -97,7 +94,7 @@ def run_case(case, dev, oracle, rng, cameras=False):
         if c["grads"] == "kept_full":
             for pool in api._grad_pool.values():
                 for e in pool:
-                    e["dense_left"] = 2                 # the next backwards into these tensors write them in full
+                    e.dense_left = 2                    # the next backwards into these tensors write them in full
         f, b = Hh.run_oracle(oracle, scene)
         # (planes under which the oracle's own depth_distortion sums cancel: that plane against float64, as the parity tests do)
         dd_ref = T.float64_depth_distortion(scene, f) if T.needs_float64_depth_distortion(scene) else None
@@ -153,8 +150,6 @@ def run_case(case, dev, oracle, rng, cameras=False):
     finally:
         lib.gft_set_binning_mode(-1)
         lib.gft_set_render_mode(-1)
-        if api._USE_COUNT_API != keep[2]:
-            api._grad_pool.clear()
         api._TILE_HINTS, api._GRADS_REUSE, api._USE_COUNT_API, api._ACC_REUSE = keep
         api._force_whole_lists = None
         api._force_cell_sched = None
@@ -180,7 +175,7 @@ def run(dev, oracle, seed=77, cases=None, seconds=None, cameras=False):
         flips += fl
         n += 1
         k = "bin%d_render%d_hints-%s_grads-%s%s%s" % (case["bin_mode"], case["render_mode"], case["hints"], case["grads"],
-                                                     "_dlpack" if case["dlpack"] else "", "" if case["acc_kept"] else "_acc-cleared")
+                                                     "_no-use-count" if case["no_use_count"] else "", "" if case["acc_kept"] else "_acc-cleared")
         kinds[k] = kinds.get(k, 0) + 1
         if cameras:
             by_camera[str(case["camera"])] = by_camera.get(str(case["camera"]), 0) + 1

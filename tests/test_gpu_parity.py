@@ -1286,12 +1286,12 @@ def test_gradient_tensors_are_reused_only_when_nobody_holds_or_modified_them(ora
     t["leaf"]["shs"].grad.mul_(0.5)
     del t, grads, out
     pool = api._grad_pool[next(iter(api._grad_pool))]
-    edited = [e["buf"].data_ptr() for e in pool if e["buf"]._version != e["version"]]
+    edited = [e.buf.data_ptr() for e in pool if e.buf._version != e.version]
     assert len(edited) == 1                                   # the edit is visible in the buffer's version counter ...
     out, grads, t = Hh.run_gpu(b, gpu)
     check_grads(bb, grads, b)
     pool = api._grad_pool[next(iter(api._grad_pool))]
-    assert edited[0] not in [e["buf"].data_ptr() for e in pool]     # ... and that buffer is forgotten, not reused
+    assert edited[0] not in [e.buf.data_ptr() for e in pool]     # ... and that buffer is forgotten, not reused
     del out, grads, t
     # a forward under grad whose backward never runs (a render for logging, a loss skipped by a NaN guard) takes a set of
     # tensors that nobody ever writes: the next call may take the same buffer, but must write it in full
@@ -1306,9 +1306,9 @@ def test_gradient_tensors_are_reused_only_when_nobody_holds_or_modified_them(ora
                 scales=kw.get("scales"), rotations=kw.get("rotations"), cov3D_precomp=kw.get("cov3D_precomp"),
                 phase_offset=a["phase_offset"], dc_offset=a["dc_offset"])
     pool = api._grad_pool[next(iter(api._grad_pool))]
-    assert len(pool) == 1 and pool[0]["valid"] is False
-    pool[0]["buf"].fill_(float("nan"))          # what uninitialised memory may hold (through the pool's own alias: the
-    pool[0]["version"] = pool[0]["buf"]._version   # version counter is the test's doing, not a caller's edit)
+    assert len(pool) == 1 and pool[0].valid is False
+    pool[0].buf.fill_(float("nan"))             # what uninitialised memory may hold (through the pool's own alias: the
+    pool[0].version = pool[0].buf._version      # version counter is the test's doing, not a caller's edit)
     del outs, leaf
     import gc
     gc.collect()
@@ -1334,12 +1334,10 @@ def test_gradient_tensors_are_reused_only_when_nobody_holds_or_modified_them(ora
 
 
 def test_gradient_tensors_are_reused_without_the_private_use_count(oracle, gpu):
-    """`torch._C._storage_Use_Count` is a private counter.  Without it (another torch version; GFT_GRADS_LIFETIME=dlpack)
-    the pool hands out DLPack aliases of its memory, whose deleter tells when nobody references them any more (public
-    API), and keeps autograd from taking the tensors over as `.grad` by holding them until the next forward.  Reuse works
-    the same: alternating scenes against the oracle with reuse from the second call on; a gradient the caller keeps
-    stays intact (it is autograd's copy on this route); a forward whose backward never ran leaves a buffer that is
-    written in full next time."""
+    """`torch._C._storage_Use_Count` is a private counter.  Without it (another torch version) the operator cannot tell
+    whether somebody still holds a gradient tensor, so nothing is kept: every backward gets fresh tensors and writes them
+    in full, as with GFT_GRADS_REUSE=0.  Alternating scenes against the oracle, no reuse in any call, a gradient the
+    caller keeps stays intact, and the pool stays empty."""
     from gftorf_amd import api
     if not api._GRADS_REUSE:
         pytest.skip("gradient-tensor reuse is off")
@@ -1361,39 +1359,19 @@ def test_gradient_tensors_are_reused_without_the_private_use_count(oracle, gpu):
                 held = t["leaf"]["means3D"].grad
                 snapshot = held.clone()
             del t, grads, out
-        assert reused[0] is False and all(reused[1:]), reused
+        assert reused == [False] * 6, reused
         assert torch.equal(held, snapshot)
-        pool = api._grad_pool[next(iter(api._grad_pool))]
-        assert len(pool) == 1 and "mem" in pool[0]                         # one buffer went round, on the DLPack route
-        # a forward under grad whose backward never runs
-        api._grad_pool.clear()
-        from gftorf_amd import GaussianRasterizer
-        ga = dict(a["gaussians"])
-        leaf = torch.tensor(ga["means3D"], dtype=torch.float32, device=gpu, requires_grad=True)
-        kw = {k: (torch.tensor(v, dtype=torch.float32, device=gpu) if v is not None else None) for k, v in ga.items() if k != "means3D"}
-        outs = GaussianRasterizer(raster_settings=Hh.gpu_settings(a, gpu))(
-            means3D=leaf, means2D=torch.zeros((3000, 3), device=gpu), opacities=kw["opacities"], shs=kw.get("shs"), shs_p=kw.get("shs_p"),
-            scales=kw.get("scales"), rotations=kw.get("rotations"), phase_offset=a["phase_offset"], dc_offset=a["dc_offset"])
-        pool = api._grad_pool[next(iter(api._grad_pool))]
-        pool[0]["mem"].fill_(float("nan"))
-        del outs, leaf
-        import gc
-        gc.collect()
-        for sc, bw in ((b, bb), (a, ba)):
-            out, grads, t = Hh.run_gpu(sc, gpu)
-            check_grads(bw, grads, sc)
-            del out, grads, t
-        assert api.last_call_stats["grads_reused"] is True
+        assert not api.state.grad_pool                                     # nothing was kept
     finally:
         api._USE_COUNT_API = keep
         api._grad_pool.clear()
 
 
-def test_two_pending_backwards_on_the_dlpack_route(oracle, gpu):
-    """DLPack route (no private use count): forward A, forward B of one shape, then A.backward(), B.backward() into the SAME
-    leaves.  The second forward lets go of A's gradient tensors before autograd has seen them, so they become the leaves'
-    `.grad` and B's gradient is added into A's pool buffer in place -- rows A's marks do not cover.  The entry must not be
-    taken as "zero but for its marked rows" afterwards: the next renders' gradients are the oracle's."""
+def test_two_pending_backwards_into_the_same_leaves(oracle, gpu):
+    """Forward A, forward B of one shape, then A.backward(), B.backward() into the SAME leaves: A's gradient tensors become
+    the leaves' `.grad` and autograd adds B's gradient into A's pool buffer in place -- rows A's marks do not cover.  The
+    entry must not be taken as "zero but for its marked rows" afterwards (its version counter has moved: it is forgotten):
+    the sum is the oracle's, and so are the next renders' gradients."""
     from gftorf_amd import api, GaussianRasterizer
     if not api._GRADS_REUSE:
         pytest.skip("gradient-tensor reuse is off")
@@ -1403,8 +1381,6 @@ def test_two_pending_backwards_on_the_dlpack_route(oracle, gpu):
     fa, ba = Hh.run_oracle(oracle, a)
     fb, bb = Hh.run_oracle(oracle, b)
     fc, bc = Hh.run_oracle(oracle, c)
-    keep = api._USE_COUNT_API
-    api._USE_COUNT_API = False
     api._grad_pool.clear()
     try:
         # shared leaves: the Gaussians of scene a rendered from the cameras of a and b
@@ -1436,7 +1412,6 @@ def test_two_pending_backwards_on_the_dlpack_route(oracle, gpu):
             check_grads(bw, grads, sc)
             del out, grads, t
     finally:
-        api._USE_COUNT_API = keep
         api._grad_pool.clear()
 
 

@@ -1,6 +1,6 @@
 """A seeded slice of the randomised soak (profiles/soak_raster.py runs the same generator for minutes) inside the GPU
 suite: ~200 random frames through the mode product of the operator -- binning structure x forward blend kernel x per-tile
-schedule x gradient-tensor route (fresh / kept rows / kept full, use count / DLPack) x accumulator kept or cleared -- against
+schedule x gradient-tensor route (fresh / kept rows / kept full, with / without torch's use count) x accumulator kept or cleared -- against
 the C oracle with the parity tests' checks."""
 import pytest
 
