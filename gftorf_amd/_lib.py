@@ -143,6 +143,7 @@ EXPORTS = [
     "gft_knn_scratch_bytes", "gft_knn_mean_dist2", "gft_adam_step", "gft_adam_step_multi", "gft_adam_step_rows", "gft_adam_step_multi_dev",
     "gft_deform_inputs", "gft_deform_packed_bytes", "gft_deform_saved_bytes", "gft_deform_scratch_bytes", "gft_deform_pack",
     "gft_deform_forward", "gft_deform_backward", "gft_deform_compact", "gft_deform_rows_work_bytes", "gft_deform_backward_rows",
+    "gft_deform_dw_splits", "gft_deform_rows_splits_capacity",
     "gft_ssim_blocks", "gft_ssim_l2_forward", "gft_ssim_l2_backward",
     "gft_image_loss_forward", "gft_image_loss_backward", "gft_pixel_loss_blocks", "gft_pixel_loss_forward", "gft_pixel_loss_backward",
     "gft_densify_stats", "gft_rows_rank_scratch_bytes", "gft_rows_rank", "gft_rows_rank_dev", "gft_rows_gather", "gft_rows_any_nonzero",
@@ -227,6 +228,10 @@ def load():
     lib.gft_deform_compact.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 9
     lib.gft_deform_rows_work_bytes.restype = C.c_size_t
     lib.gft_deform_rows_work_bytes.argtypes = [C.c_int64]
+    lib.gft_deform_dw_splits.restype = C.c_int
+    lib.gft_deform_dw_splits.argtypes = [C.c_int64]
+    lib.gft_deform_rows_splits_capacity.restype = C.c_int
+    lib.gft_deform_rows_splits_capacity.argtypes = [C.c_int64]
     lib.gft_deform_backward_rows.restype = C.c_int
     lib.gft_deform_backward_rows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.POINTER(DeformParams), C.c_void_p]

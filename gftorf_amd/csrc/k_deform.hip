@@ -1867,6 +1867,7 @@ __global__ __launch_bounds__(256) void k_deform_dw_bf(DwArgs a)
     if (a.plan) {      // counts the device keeps (DevPlan): the launch is the capacity's, surplus workgroups return below
         a.splits = a.plan->splits; a.tiles_per_split = a.plan->tiles_per_split; a.n_ext = a.plan->n_ext;
         if (a.first_block) a.first_block = 7 * a.splits;      // (the light jobs' launch: behind the heavy jobs of THESE splits)
+        else if ((int)blockIdx.x >= 7 * a.splits) return;      // (the heavy jobs' launch: its surplus is no light job)
     }
     const int wg = (int)blockIdx.x + a.first_block;
     if (wg < 7 * a.splits) {
@@ -1949,6 +1950,24 @@ __host__ __device__ int dw_splits(int64_t n_pad, int* tiles_per_split)
     const int64_t tps = (tiles + splits - 1) / splits;
     *tiles_per_split = (int)tps;
     return (int)((tiles + tps - 1) / tps);
+}
+
+// The splits a launch under a plan is sized for (grids, partial sums): dw_splits() is not monotone -- 129 tiles give
+// 26 splits, 108 tiles 27 --, so the capacity's own count does not bound the count of fewer rows.  dw_splits() never
+// returns more than the count it aims at, min(73, max(1, tiles / 4)), and that grows with the tiles: it holds for every
+// row count up to the capacity.
+__host__ int rows_splits_capacity(int64_t n_pad)
+{
+    int64_t splits = n_pad / DF_DW_TILE / 4;
+    if (splits < 1) splits = 1;
+    if (splits > 73) splits = 73;
+    return (int)splits;
+}
+
+// dz | dzh | the splits' partial sums | the points' largest |dz| per layer | the range flag of k_deform_dw_h
+size_t scratch_bytes(int64_t n_pad, int splits)
+{
+    return ((size_t)n_pad * (DF_D * DF_W + DF_HEAD) + (size_t)splits * DW_PART_FLOATS + (size_t)n_pad * DF_D + 4) * sizeof(float);
 }
 
 // GFT_DEFORM_FP16X2=0: the forward walk on three bf16 planes (six multiplies per product) instead of two fp16 planes (three)
@@ -2063,9 +2082,17 @@ extern "C" size_t gft_deform_scratch_bytes(int64_t n)
     const int64_t n_pad = pad_points(n);
     int tps;
     const int splits = dw_splits(n_pad, &tps);
-    // dz | dzh | the splits' partial sums | the points' largest |dz| per layer | the range flag of k_deform_dw_h
-    return ((size_t)n_pad * (DF_D * DF_W + DF_HEAD) + (size_t)splits * DW_PART_FLOATS + (size_t)n_pad * DF_D + 4) * sizeof(float);
+    return scratch_bytes(n_pad, splits);
 }
+
+extern "C" int gft_deform_dw_splits(int64_t n)
+{
+    if (n <= 0) return 0;
+    int tps;
+    return dw_splits(pad_points(n), &tps);
+}
+
+extern "C" int gft_deform_rows_splits_capacity(int64_t n) { return n <= 0 ? 0 : rows_splits_capacity(pad_points(n)); }
 
 extern "C" int gft_deform_pack(void* hip_stream, int xyz_multires, int t_multires, const gft_deform_params* p, void* packed)
 {
@@ -2191,7 +2218,9 @@ static int deform_backward_impl(void* hip_stream, int xyz_multires, int t_multir
     float* dzh = dz + n_pad * DF_D * DF_W;
     float* part = dzh + n_pad * DF_HEAD;
     int tps;
-    const int splits = dw_splits(n_pad, &tps);
+    int splits = dw_splits(n_pad, &tps);
+    // under a plan the kernels take their splits from it: grids and partial sums for the most any row count can have
+    if (plan) splits = rows_splits_capacity(n_pad);
     float* rowmax = part + (int64_t)splits * DW_PART_FLOATS;
     uint32_t* xflag = reinterpret_cast<uint32_t*>(rowmax + n_pad * DF_D);
     const bool h_planes = fp16_backward();
@@ -2344,7 +2373,7 @@ RowsWork rows_work(int64_t n)
     w.dx = take((size_t)n * 12);
     w.ds = take((size_t)n * 192);
     w.saved = take(gft_deform_saved_bytes(n));
-    w.scratch = take(gft_deform_scratch_bytes(n));
+    w.scratch = take(scratch_bytes(pad_points(n), rows_splits_capacity(pad_points(n))));
     w.total = o;
     return w;
 }

@@ -48,34 +48,46 @@ class FusedAdam(torch.optim.Adam):
                 step=torch.zeros((self._SLOTS,), device=dev, dtype=torch.float32),
                 lr=torch.zeros((self._SLOTS,), device=dev, dtype=torch.float64),
                 lr_host=torch.zeros((self._SLOTS,), dtype=torch.float64).pin_memory(),
-                factors=torch.zeros((2 * self._SLOTS,), device=dev, dtype=torch.float32), used=0, slot_of={})
+                factors=torch.zeros((2 * self._SLOTS,), device=dev, dtype=torch.float32), used=0)
             b["lr_np"] = b["lr_host"].numpy()
         return b
 
+    def _slot_of(self, b, st):
+        """The slot whose count ``st`` (a ``state["step"]``) views, or None.  The state itself is the record: the reference's
+        densification code replaces a parameter and hands the SAME state dict to the new tensor
+        (scene/gaussian_model.py:456-540), so nothing keyed by the parameter object survives it."""
+        base = b["step"].data_ptr()
+        if (isinstance(st, torch.Tensor) and st.device == b["step"].device and st.dtype == torch.float32
+                and base <= st.data_ptr() < base + 4 * self._SLOTS):
+            return (st.data_ptr() - base) // 4
+        return None
+
     def _slot(self, p, state):
         """The parameter's slot in the device buffers; its ``state["step"]`` becomes (or stays) the 0-dim view of the slot's
-        count.  A count that came from elsewhere -- a state_dict, steps taken before the mode was switched on, the
-        reference's densification code re-keying the state (scene/gaussian_model.py:456-540 keeps the dict) -- is copied in."""
+        count.  A count that came from elsewhere -- a state_dict, steps taken before the mode was switched on -- is copied in."""
         b = self._buffers(p.device)
         st = state.get("step")
-        base, end = b["step"].data_ptr(), b["step"].data_ptr() + 4 * self._SLOTS
-        if isinstance(st, torch.Tensor) and st.is_cuda and base <= st.data_ptr() < end and st.dtype == torch.float32:
-            return (st.data_ptr() - base) // 4, b
+        slot = self._slot_of(b, st)
+        if slot is not None:
+            return slot, b
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("gftorf_amd.FusedAdam(capturable=True): take one eager step() before capturing (the optimizer "
                                "state of a parameter is created, or adopted, outside the graph)")
         if b["used"] >= self._SLOTS:
-            # (slots of parameters that no longer exist -- densification replaces the tensors -- are reclaimed)
-            alive = {id(q) for g in self.param_groups for q in g["params"]}
-            b["slot_of"] = {k: v for k, v in b["slot_of"].items() if k in alive}
-            free = sorted(set(range(self._SLOTS)) - set(b["slot_of"].values()))
+            # (slots of parameters that no longer exist are reclaimed: a slot is taken while the state of a parameter of
+            # some group views it)
+            taken = set()
+            for g in self.param_groups:
+                for q in g["params"]:
+                    if q.device == p.device and q in self.state:
+                        taken.add(self._slot_of(b, self.state[q].get("step")))
+            free = sorted(set(range(self._SLOTS)) - taken)
             if not free:
                 raise RuntimeError("gftorf_amd.FusedAdam(capturable=True): more than %d parameter tensors" % self._SLOTS)
             slot = free[0]
         else:
             slot = b["used"]
             b["used"] += 1
-        b["slot_of"][id(p)] = slot
         view = b["step"][slot]
         view.fill_(float(st) if st is not None else 0.0)
         state["step"] = view
@@ -88,8 +100,8 @@ class FusedAdam(torch.optim.Adam):
             lr = float(group["lr"])
             for p in group["params"]:
                 b = self._gft_dev.get(p.device)
-                if b is not None:
-                    slot = b["slot_of"].get(id(p))
+                if b is not None and p in self.state:
+                    slot = self._slot_of(b, self.state[p].get("step"))
                     if slot is not None:
                         b["lr_np"][slot] = lr
 

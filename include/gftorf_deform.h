@@ -132,8 +132,14 @@ int gft_deform_compact(void* hip_stream, int64_t n, int64_t k, const uint8_t* ma
  * them.  Gradients equal gft_deform_compact + gft_deform_backward over the same rows bit for bit (the same kernels on
  * the same compacted rows; only the buffers' plane stride differs), i.e. the dense backward's up to summation order.
  * work: gft_deform_rows_work_bytes(n) bytes, 256-byte aligned, contents irrelevant before and after.
- * rows_out: device uint32 that receives the number of rows processed (may be NULL). */
+ * rows_out: device uint32 that receives the number of rows processed (may be NULL).
+ * The weight gradients are sums over point splits.  gft_deform_dw_splits(k) is the number of splits the backward of k
+ * points sums over (what the plan computes for k rows); it does NOT grow monotonically with k.  The launches and the
+ * work buffer of capacity n therefore hold gft_deform_rows_splits_capacity(n) splits, which is non-decreasing and at
+ * least gft_deform_dw_splits(k) for every k <= n.  Both are host-only queries (0 for n <= 0). */
 size_t gft_deform_rows_work_bytes(int64_t n);
+int gft_deform_dw_splits(int64_t n);
+int gft_deform_rows_splits_capacity(int64_t n);
 int gft_deform_backward_rows(void* hip_stream, int xyz_multires, int t_multires, int64_t n, const void* packed,
                              const float* xyz, const float* t, int64_t t_stride, const float* g_d_xyz, const float* g_d_sh,
                              void* work, const gft_deform_grads* grads, uint32_t* rows_out);

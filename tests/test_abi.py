@@ -193,3 +193,50 @@ def test_deform_size_queries_and_argument_errors(lib):
     assert lib.gft_deform_forward(None, 10, 10, 5, None, None, 1, None, None, None, None) != 0
     assert lib.gft_deform_forward(None, 11, 16, 0, None, None, 1, None, None, None, None) != 0      # 102 inputs
     assert lib.gft_deform_backward(None, 10, 10, 5, None, None, None, None, None, None) != 0
+
+
+def test_deform_rows_launches_hold_the_splits_of_every_row_count(lib):
+    """gft_deform_backward_rows sizes its weight-gradient grids and partial sums on the host, for the capacity, while the
+    plan kernel picks the splits of the row count it finds on the device.  gft_deform_dw_splits is not monotone, so the
+    capacity's own count is no bound: gft_deform_rows_splits_capacity has to hold the splits of EVERY row count up to
+    the capacity, and the work buffer has to hold that many partial sums."""
+    import numpy as np
+    PAD = 192
+    classes = np.arange(1, 400_000 // PAD + 2, dtype=np.int64)               # padded sizes 192 .. 400 128
+    dw = np.array([lib.gft_deform_dw_splits(int(c) * PAD) for c in classes], dtype=np.int64)
+    cap = np.array([lib.gft_deform_rows_splits_capacity(int(c) * PAD) for c in classes], dtype=np.int64)
+    assert lib.gft_deform_dw_splits(0) == 0 and lib.gft_deform_rows_splits_capacity(0) == 0
+    # a count belongs to its padding class: the first and the last size of a class give the class's answer
+    assert [lib.gft_deform_dw_splits(int(c) * PAD - PAD + 1) for c in classes[:300]] == dw[:300].tolist()
+    assert [lib.gft_deform_rows_splits_capacity(int(c) * PAD - PAD + 1) for c in classes[:300]] == cap[:300].tolist()
+    assert dw.min() >= 1 and dw.max() == 73
+    # every k <= n in steps of the padding: the largest count up to a capacity is within what that capacity launches
+    most = np.maximum.accumulate(dw)
+    assert (most <= cap).all(), classes[most > cap][:5] * PAD
+    assert (np.diff(cap) >= 0).all()
+    # the work buffer grows with n and holds a partial sum per split of the capacity beside everything else
+    # (a split's partial sums: dW of layer 0 [256,96], layers 1..7 [256,256], encoding rows of layer 5 [256,96], heads
+    # [64,256], biases [8,256] + [64])
+    part_bytes = (2 * 256 * 96 + 7 * 256 * 256 + 64 * 256 + 8 * 256 + 64) * 4
+    r256 = lambda b: (b + 255) // 256 * 256
+    sizes = sorted({int(c) * PAD + d for c in classes[::7].tolist() + [42, 43, 64, 65, 104, 105] for d in (-1, 0, 1)} | {1, 8195, 12345})
+    work = [lib.gft_deform_rows_work_bytes(n) for n in sizes]
+    assert all(a <= b for a, b in zip(work, work[1:]))
+    for n, w in zip(sizes, work):
+        n_pad = (n + PAD - 1) // PAD * PAD
+        # the dense scratch without its partial sums = dz, dzh, row maxima, range flag
+        dense_rest = lib.gft_deform_scratch_bytes(n) - lib.gft_deform_dw_splits(n) * part_bytes
+        assert dense_rest == (n_pad * (8 * 256 + 64) + n_pad * 8 + 4) * 4
+        rest = (2 * 256 + r256(lib.gft_rows_rank_scratch_bytes(n)) + r256(n) + 2 * r256(4 * n) + 3 * r256(12 * n) + 2 * r256(192 * n)
+                + r256(lib.gft_deform_saved_bytes(n)) + dense_rest)
+        assert w - rest >= lib.gft_deform_rows_splits_capacity(n) * part_bytes, n
+    # the guard on this test: dw_splits is NOT monotone, so "the capacity's own count" fails the bound above -- at the
+    # smallest size the Python module sends down this path, at the test sizes and at the config-3 point count
+    for n, k_pads in ((8195, (6912, 7680)), (12345, (10752, 11520, 12288)), (20000, (16896, 17664, 18432)), (40000, (18432,)),
+                      (100000, (23232,))):
+        own = lib.gft_deform_dw_splits(n)
+        for k in k_pads:
+            assert k <= n and lib.gft_deform_dw_splits(k) > own, (n, k)
+            assert lib.gft_deform_dw_splits(k) <= lib.gft_deform_rows_splits_capacity(n)
+    assert [lib.gft_deform_dw_splits(n) for n in (8195, 12345, 20000, 40000, 100000)] == [26, 39, 63, 70, 72]
+    assert int((dw[:40128 // PAD] > 70).sum()) == 27 and int((dw[:100032 // PAD] > 72).sum()) == 68

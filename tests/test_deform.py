@@ -1,5 +1,7 @@
 """Deformation network: oracle vs the reference's golden vectors (CPU),
 HIP path vs oracle (GPU, through the C ABI in include/gftorf_deform.h)."""
+import contextlib
+import functools
 import os
 
 import numpy as np
@@ -330,12 +332,15 @@ def test_full_size_properties():
 @pytest.mark.gpu
 def test_bf16_backward_walk_still_matches():
     """GFT_DEFORM_BWD_FP16=0 keeps the backward walk on three bf16 planes (six MFMAs per product; the default since round 6
-    multiplies two fp16 planes, three MFMAs): it is also what runs when a weight does not fit the fp16 planes."""
+    multiplies two fp16 planes, three MFMAs): it is also what runs when a weight does not fit the fp16 planes.  The sweep over
+    the padded row counts of a capacity runs here too: under a plan the bf16 weight-gradient kernel finds its jobs by the same
+    launch arithmetic (heavy launch, then the light jobs behind `first_block`)."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_deform.py"), "-q", "-m", "gpu", "-x",
-                        "-k", "backward_against_oracle or backward_matches_reference or gradient_only"],
+                        "-k", "backward_against_oracle or backward_matches_reference or gradient_only or "
+                              "(every_padded_row_count and n8195)"],
                        env=dict(os.environ, GFT_DEFORM_BWD_FP16="0"), cwd=root, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert " passed" in r.stdout
@@ -548,6 +553,203 @@ def test_activations_on_demand_give_the_saved_forwards_gradients():
         D.lazy_save, D.device_row_count = old, old_dev
 
 
+@contextlib.contextmanager
+def _deform_modes(**modes):
+    """Module switches of gftorf_amd.deform set for a block."""
+    from gftorf_amd import deform as D
+    old = {k: getattr(D, k) for k in modes}
+    try:
+        for k, v in modes.items():
+            setattr(D, k, v)
+        yield D
+    finally:
+        for k, v in old.items():
+            setattr(D, k, v)
+
+
+# the blocking selection on exactly the rows with a gradient (with `_save_state = {"fraction": 0.0}`: a forward that keeps
+# nothing, a host read of the count, buffers and launches of exactly that size): the reference of every rows test
+_BLOCKING = dict(device_row_count=False, lazy_save=True, _SPARSE_MAX_FRACTION=2.0)
+
+
+class _RowsCase:
+    """One network, one set of inputs and upstream gradients for n points; the parameter gradients for the rows of a mask
+    by the blocking selection and by the rows counted on the device (gft_deform_backward_rows)."""
+
+    def __init__(self, n, shared_t):
+        self.dev = dev = torch.device("cuda:0")
+        self.n = n
+        x, t = _inputs(n, 8, shared_t=shared_t)
+        self.x, self.t = torch.tensor(x, device=dev), torch.tensor(t, device=dev)
+        if shared_t:
+            self.t = self.t[:1].expand(n, -1)                     # one time for all points (stride 0)
+        g = torch.Generator().manual_seed(5)
+        self.g_dxyz = torch.randn((n, 3), generator=g).to(dev)
+        self.g_dsh = torch.randn((n, 16, 3), generator=g).to(dev)
+        self.perm = torch.randperm(n, generator=g).to(dev)
+        self.ref_net, _ = _net(12, dev)
+        self.net, _ = _net(12, dev)
+
+    def mask(self, k):
+        """exactly k rows, scattered"""
+        m = torch.zeros((self.n,), dtype=torch.bool, device=self.dev)
+        m[self.perm[:k]] = True
+        return m
+
+    def _step(self, net, m):
+        net.zero_grad(set_to_none=True)
+        d_xyz, _, d_sh, _ = net(self.x, self.t)
+        torch.autograd.backward([d_xyz, d_sh], [self.g_dxyz * m[:, None], self.g_dsh * m[:, None, None]])
+        return {k: p.grad for k, p in net.named_parameters() if p.grad is not None}
+
+    def blocking(self, m):
+        with _deform_modes(**_BLOCKING) as D:
+            self.ref_net._save_state = {"fraction": 0.0}
+            grads = self._step(self.ref_net, m)
+            st = dict(D.last_backward_stats)
+        assert st["recomputed"] and st["points_processed"] == int(m.sum())
+        return grads
+
+    def on_device(self, m, mode=True, fraction=None):
+        """(gradients, the row count left on the device); mode "auto" with the share of rows the loop would have learnt"""
+        with _deform_modes(device_row_count=mode, lazy_save=True) as D:
+            if fraction is not None:
+                self.net._save_state = {"fraction": fraction, "pending": None, "pin": None}
+            grads = self._step(self.net, m)
+            st = dict(D.last_backward_stats)
+        assert st["recomputed"] and st["points_processed"] is None
+        return grads, int(st["rows_on_device"].item())
+
+    def mismatches(self, k, mode=True, fraction=None):
+        """what differs from the blocking selection with exactly k rows: [] when all 24 gradients are the same bits and the
+        count is k"""
+        m = self.mask(k)
+        ref = self.blocking(m)
+        got, rows = self.on_device(m, mode, fraction)
+        assert len(got) == len(ref) == 24
+        names = sorted(ref)
+        bad = [(k, "rows", rows)] if rows != k else []
+        if not torch.equal(torch.cat([got[q].reshape(-1) for q in names]), torch.cat([ref[q].reshape(-1) for q in names])):
+            bad += [(k, q) for q in names if not torch.equal(got[q], ref[q])]
+        return bad
+
+
+@functools.lru_cache(maxsize=1)
+def _rows_case(n, shared_t):
+    return _RowsCase(n, shared_t)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,shared_t", [pytest.param(8_195, False, id="n8195"), pytest.param(12_345, True, id="n12345")])
+def test_every_padded_row_count_of_a_capacity(n, shared_t):
+    """The launches of gft_deform_backward_rows are the capacity's, the splits of the weight-gradient sums are those of the
+    row count found on the device -- and fewer rows can have MORE splits (8195 points: 26, 7680 rows: 30).  Every padding
+    class of the capacity, with a count inside it; both ends of the classes that have at least the capacity's splits."""
+    from gftorf_amd import _lib
+    lib = _lib.load()
+    case = _rows_case(n, shared_t)
+    classes = (n + 191) // 192
+    assert classes == {8_195: 43, 12_345: 65}[n]
+    own = lib.gft_deform_dw_splits(n)
+    ks, more = [], 0
+    for c in range(1, classes + 1):
+        ks.append(min(n, 192 * c - 5))
+        if lib.gft_deform_dw_splits(192 * c) >= own:
+            ks += [k for k in (192 * (c - 1) + 1, 192 * c) if k <= n]
+            more += lib.gft_deform_dw_splits(192 * c) > own
+    assert more == {8_195: 2, 12_345: 3}[n]                       # (7680 and 6912; 10752, 11520 and 12288)
+    bad = []
+    for k in ks:
+        bad += case.mismatches(k)
+    assert not bad, bad[:24]
+
+
+def _classes_of_the_73_split_regime(lib, n):
+    classes = (n + 191) // 192
+    own = lib.gft_deform_dw_splits(n)
+    over = [c for c in range(1, classes + 1) if lib.gft_deform_dw_splits(192 * c) > own]
+    chosen = set(range(16, classes + 1, 16))
+    for c in over:
+        chosen |= {c - 1, c, c + 1}
+    return sorted(c for c in chosen if 1 <= c <= classes), over
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,k", [pytest.param(40_000, None, id="n40000"), (100_000, 23_200), (100_000, 28_000)])
+def test_rows_where_fewer_points_have_the_most_splits(n, k):
+    """Capacities whose own split count is below the 73 that a smaller row count reaches (40 000 points: 70, from 18 432 rows
+    up 27 classes have more; 100 000 points, the config-3 size: 72, a seventh of the classes from 23 % of the rows up have
+    73).  The classes come from the library's own query: all with more splits than the capacity, their neighbours, every
+    16th otherwise.  Shares of at most 0.6 run as the loop runs them (device_row_count = "auto" with that share learnt)."""
+    from gftorf_amd import _lib
+    lib = _lib.load()
+    case = _rows_case(n, True)
+    if k is None:
+        classes, over = _classes_of_the_73_split_regime(lib, n)
+        assert lib.gft_deform_dw_splits(n) == 70 and len(over) == 27 and over[0] == 18_432 // 192
+        ks = [min(n, 192 * c - 5) for c in classes]
+    else:
+        assert lib.gft_deform_dw_splits(k) == 73 > lib.gft_deform_dw_splits(n) == 72
+        ks = [k]
+    bad = []
+    for k in ks:
+        bad += case.mismatches(k, "auto", k / n) if k <= 0.6 * n else case.mismatches(k)
+    assert not bad, bad[:24]
+
+
+@functools.lru_cache(maxsize=1)
+def _points_far_from_a_relu_edge(n):
+    params = deform_ref.random_params(12)
+    x, t = _inputs(n + n // 8, 200 + n, False)
+    margin = deform_ref.relu_margin(params, x, t)
+    keep = np.sort(np.argsort(-margin)[:n])
+    assert margin[keep].min() > 1e-6
+    return x[keep], t[keep]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", [7_675, 6_907])
+def test_rows_counted_on_the_device_against_the_float64_oracle(k):
+    """8195 points with 7675 and 6907 rows carrying a gradient (30 and 27 splits against the capacity's 26): the gradients
+    of the rows counted on the device against deform_ref in float64 over those rows, within BWD_TOL -- and, so that a miss
+    can be attributed, the dense backward over the same rows as a batch of their own first."""
+    from gftorf_amd import _lib
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    n = 8_195
+    assert lib.gft_deform_dw_splits(k) > lib.gft_deform_dw_splits(n) and lib.gft_deform_dw_splits(k) in (27, 30)
+    x, t = _points_far_from_a_relu_edge(n)
+    net, params = _net(12, dev)
+    rng = np.random.default_rng(k)
+    sel = np.sort(rng.permutation(n)[:k])
+    g_dxyz, g_dsh = np.zeros((n, 3), np.float32), np.zeros((n, 16, 3), np.float32)
+    g_dxyz[sel], g_dsh[sel] = rng.normal(size=(k, 3)), rng.normal(size=(k, 16, 3))
+    ref = deform_ref.backward(params, x[sel], t[sel], g_dxyz[sel], g_dsh[sel], dtype=np.float64)
+
+    def grads(xs, ts, gx, gs):
+        net.zero_grad(set_to_none=True)
+        d_xyz, _, d_sh, _ = net(torch.tensor(xs, device=dev), torch.tensor(ts, device=dev))
+        torch.autograd.backward([d_xyz, d_sh], [torch.tensor(gx, device=dev), torch.tensor(gs, device=dev)])
+        return {q: p.grad.cpu().numpy() for q, p in net.named_parameters() if p.grad is not None}
+
+    with _deform_modes(device_row_count=False, lazy_save=True) as D:
+        dense = grads(x[sel], t[sel], g_dxyz[sel], g_dsh[sel])    # (below the row selection's 8192 points: the dense backward)
+        assert D.last_backward_stats == {"points": k, "points_processed": k, "recomputed": False}
+    with _deform_modes(device_row_count=True, lazy_save=True) as D:
+        rows = grads(x, t, g_dxyz, g_dsh)
+        assert D.backward_stats() == {"points": n, "points_processed": k, "recomputed": True}
+    assert sorted(dense) == sorted(rows) == sorted(q for q, v in ref.items() if v is not None) and len(rows) == 24
+    err_dense = {q: _rel(dense[q], ref[q]) for q in dense}
+    err_rows = {q: _rel(rows[q], ref[q]) for q in rows}
+    worst = max(err_rows, key=err_rows.get)
+    print("k = %d: dense backward %.3g, rows counted on the device %.3g (%s) of the max-norm against float64"
+          % (k, max(err_dense.values()), err_rows[worst], worst))
+    for q in dense:
+        assert err_dense[q] < BWD_TOL, ("dense", q, err_dense[q])
+    for q in rows:
+        assert err_rows[q] < BWD_TOL, ("rows", q, err_rows[q])
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("frac,n,shared_t", [(0.07, 20_000, True), (0.5, 12_345, False), (0.0, 9_000, True), (1.0, 10_000, True)])
 def test_rows_counted_on_the_device_give_the_blocking_selections_gradients(frac, n, shared_t):
@@ -596,28 +798,29 @@ def test_rows_counted_on_the_device_give_the_blocking_selections_gradients(frac,
         D.device_row_count, D.lazy_save, D._SPARSE_MAX_FRACTION = old
 
 
-@pytest.mark.gpu
-def test_a_captured_backward_follows_the_rows_of_every_replay():
-    """Forward + backward captured in a HIP graph once (the row count stays on the device), replayed on upstream gradients
-    with other rows set: every replay's gradients are those of an eager call on the same gradients, bit for bit, and the
-    row count it leaves is that replay's."""
+def _captured_replays_follow_the_blocking_selection(n, masks):
+    """Forward + backward of n points captured once, replayed on upstream gradients with the rows of every mask: each replay
+    against the blocking selection run eagerly on the same upstream gradients, bit for bit, and the row count it leaves."""
     from gftorf_amd import deform as D
     dev = torch.device("cuda:0")
-    n = 16_000
     x, t = _inputs(n, 8, shared_t=True)
     xt, tt = torch.tensor(x, device=dev), torch.tensor(t, device=dev)
     g = torch.Generator().manual_seed(11)
     full_xyz, full_sh = torch.randn((n, 3), generator=g).to(dev), torch.randn((n, 16, 3), generator=g).to(dev)
-    masks = [(torch.rand((n,), generator=g) < f).to(dev) for f in (0.3, 0.05, 0.0, 0.8)]
+    made = {}
+    for m in masks:                                               # (a mask listed twice is the same rows again)
+        if m not in made:
+            made[m] = m(g).to(dev)
+    masks = [made[m] for m in masks]
     s_xyz, s_sh = torch.zeros_like(full_xyz), torch.zeros_like(full_sh)
     if os.environ.get("GFT_DEFORM_DEVICE_ROWS", "") in ("", "auto"):
         assert D.device_row_count == "auto"                       # (the default: under capture always)
     net, _ = _net(12, dev)
-    params = [p for p in net.parameters()]
+    ref_net, _ = _net(12, dev)
 
-    def run():
+    def run(net):
         d_xyz, _, d_sh, _ = net(xt, tt)
-        return torch.autograd.grad([d_xyz, d_sh], [p for p in params if p.requires_grad], [s_xyz, s_sh], allow_unused=True)
+        return torch.autograd.grad([d_xyz, d_sh], [p for p in net.parameters() if p.requires_grad], [s_xyz, s_sh], allow_unused=True)
 
     def set_mask(m):
         s_xyz.copy_(full_xyz * m[:, None])
@@ -626,29 +829,56 @@ def test_a_captured_backward_follows_the_rows_of_every_replay():
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
-        run()                                                     # (warm-up outside the capture: allocations, LDS opt-ins)
+        run(net)                                                  # (warm-up outside the capture: allocations, LDS opt-ins)
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
-        captured = run()
+        captured = run(net)
         rows = D.last_backward_stats["rows_on_device"]
-    old = D.device_row_count
-    try:
-        for m in masks + [masks[0]]:
-            set_mask(m)
-            graph.replay()
-            got = [None if c is None else c.clone() for c in captured]
-            assert int(rows.item()) == int(m.sum())
-            D.device_row_count = True
-            ref = run()
-            D.device_row_count = old
-            for a, b in zip(got, ref):
-                assert (a is None) == (b is None)
-                if a is not None:
-                    assert torch.equal(a, b)
-    finally:
-        D.device_row_count = old
+    for m in masks:
+        set_mask(m)
+        graph.replay()
+        got = [None if c is None else c.clone() for c in captured]
+        assert int(rows.item()) == int(m.sum())
+        with _deform_modes(**_BLOCKING):
+            ref_net._save_state = {"fraction": 0.0}
+            ref = run(ref_net)
+            assert D.last_backward_stats["recomputed"] and D.last_backward_stats["points_processed"] == int(m.sum())
+        assert len(got) == len(ref) and sum(a is not None for a in got) == 24
+        for a, b in zip(got, ref):
+            assert (a is None) == (b is None)
+            if a is not None:
+                assert torch.equal(a, b), int(m.sum())
+
+
+@pytest.mark.gpu
+def test_a_captured_backward_follows_the_rows_of_every_replay():
+    """Forward + backward captured in a HIP graph once (the row count stays on the device), replayed on upstream gradients
+    with other rows set: every replay's gradients are those of the blocking selection run eagerly on the same gradients, bit
+    for bit, and the row count it leaves is that replay's."""
+    n = 16_000
+    masks = [lambda g, f=f: torch.rand((n,), generator=g) < f for f in (0.3, 0.05, 0.0, 0.8)]
+    _captured_replays_follow_the_blocking_selection(n, masks + [masks[0]])
+
+
+@pytest.mark.gpu
+def test_a_captured_backward_follows_row_counts_with_more_splits_than_its_capacity():
+    """One graph at 20 000 points (63 weight-gradient splits of its own) replayed with 16 890 and 18 430 rows -- 66 and 72
+    splits: more than the capacity's --, then few, none and 16 890 again."""
+    n = 20_000
+
+    def exactly(k):
+        def mask(g):
+            m = torch.zeros((n,), dtype=torch.bool)
+            m[torch.randperm(n, generator=g)[:k]] = True
+            return m
+        return mask
+    from gftorf_amd import _lib
+    lib = _lib.load()
+    assert [lib.gft_deform_dw_splits(k) for k in (n, 16_890, 18_430)] == [63, 66, 72]
+    first = exactly(16_890)
+    _captured_replays_follow_the_blocking_selection(n, [first] + [exactly(k) for k in (18_430, 1_400, 0)] + [first])
 
 
 @pytest.mark.gpu

@@ -206,3 +206,191 @@ def test_capturable_adam_equals_the_eager_one_and_replays(gpu):
         assert float(eager.state[pe]["step"]) == float(cap.state[pc]["step"]) == 6.0
         assert torch.equal(pe, pc), ge["name"]
         assert torch.equal(eager.state[pe]["exp_avg_sq"], cap.state[pc]["exp_avg_sq"])
+
+
+# ---- densification re-keys the parameters: the reference replaces each nn.Parameter and hands the SAME state dict to the new
+# tensor (scene/gaussian_model.py:456-540; gftorf_amd.densify does the same) --------------------------------------------------
+PER_GAUSSIAN = [str(i) for i in range(6)]      # groups() names of the six [1001, ...] tensors; "6" is the odd one
+
+
+def _new_rows(seed=21, rows=37):
+    g = torch.Generator().manual_seed(seed)
+    shapes = [(3,), (1, 3), (15, 3), (1,), (3,), (4,)]
+    ext = {name: torch.randn((rows,) + s, generator=g) for name, s in zip(PER_GAUSSIAN, shapes)}
+    keep = torch.rand(1001 + rows, generator=g) < 0.8
+    return ext, keep
+
+
+def _densify(opt, dev, ext, keep):
+    """37 rows appended, then a seeded mask of rows kept: every per-Gaussian parameter is replaced twice."""
+    from gftorf_amd import densify
+    densify.cat_tensors_to_optimizer(opt, {k: v.to(dev) for k, v in ext.items()}, skip=("6",))
+    densify.prune_optimizer(opt, keep.to(dev), skip=("6",))
+
+
+def _densify_by_hand(opt, ext, keep):
+    """The same surgery on a torch.optim.Adam, written out (gaussian_model.py:473-492 and 516-537)."""
+    for group in opt.param_groups:
+        if group["name"] not in ext:
+            continue
+        p = group["params"][0]
+        state = opt.state.pop(p)
+        new_p = torch.nn.Parameter(torch.cat((p.detach(), ext[group["name"]]), dim=0)[keep].clone())
+        for k in ("exp_avg", "exp_avg_sq"):
+            state[k] = torch.cat((state[k], torch.zeros_like(ext[group["name"]])), dim=0)[keep].clone()
+        group["params"][0] = new_p
+        opt.state[new_p] = state
+
+
+def _rekey(opt, group):
+    """A parameter replaced the way the densification replaces it: new tensor, same state dict."""
+    p = group["params"][0]
+    new_p = torch.nn.Parameter(p.detach().clone())
+    state = opt.state.pop(p)
+    group["params"][0] = new_p
+    opt.state[new_p] = state
+    return new_p
+
+
+@pytest.mark.gpu
+def test_capturable_adam_follows_the_schedule_after_densification(gpu):
+    """Two eager steps, the densification's surgery on the optimizer, one eager step, the step captured, five replays under
+    a moving learning rate: the capturable optimizer equals the eager one bit for bit and torch.optim.Adam (CPU, the same
+    surgery by hand) to rounding.  The re-keyed parameters keep their state dict, so their slot in the device buffers has to
+    be known from the state: refresh_lr() must reach them."""
+    from gftorf_amd import FusedAdam
+    ext, keep = _new_rows()
+    gen = torch.Generator().manual_seed(7)
+
+    def make(cls, dev, **kw):
+        opt = cls(groups(dev, seed=3), lr=0.0, eps=1e-15, **kw)
+        for g in opt.param_groups:
+            g["base_lr"] = g["lr"]
+        return opt
+    # eager, captured, eager with the learning rate held at its capture-time value (the guard), torch on the CPU
+    eager, cap, held = make(FusedAdam, gpu), make(FusedAdam, gpu, capturable=True), make(FusedAdam, gpu)
+    cpu = make(torch.optim.Adam, "cpu")
+    opts = [(eager, gpu), (cap, gpu), (held, gpu), (cpu, "cpu")]
+
+    def draw():
+        return [torch.randn(g["params"][0].shape, generator=gen) for g in eager.param_groups]
+
+    def load(opt, dev, grads, lr_of):
+        for g, gr in zip(opt.param_groups, grads):
+            p = g["params"][0]
+            if p.grad is None:
+                p.grad = torch.zeros_like(p)            # (static gradient tensors: the graph reads these)
+            p.grad.copy_(gr.to(dev))
+            g["lr"] = lr_of(g["base_lr"])
+    for _ in range(2):
+        grads = draw()
+        for opt, dev in opts:
+            load(opt, dev, grads, lambda base: base)
+            opt.step()
+    for opt, dev in opts[:3]:
+        _densify(opt, dev, ext, keep)
+    _densify_by_hand(cpu, ext, keep)
+    rows = int(keep.sum())
+    assert all(g["params"][0].shape[0] == (rows if g["name"] != "6" else 7) for opt, _ in opts for g in opt.param_groups)
+    grads = draw()
+    for opt, dev in opts:
+        load(opt, dev, grads, lambda base: base)
+        opt.step()                                       # adopts the state outside the graph
+    graph = torch.cuda.CUDAGraph()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        torch.cuda.synchronize()
+        with torch.cuda.graph(graph, stream=side):
+            cap.step()
+    torch.cuda.current_stream().wait_stream(side)
+    for it in range(1, 6):
+        grads = draw()
+        for opt, dev in ((eager, gpu), (cpu, "cpu")):
+            load(opt, dev, grads, lambda base: base * 0.9 ** it)
+            opt.step()
+        load(held, gpu, grads, lambda base: base)
+        held.step()
+        load(cap, gpu, grads, lambda base: base * 0.9 ** it)
+        cap.refresh_lr()
+        graph.replay()
+    torch.cuda.synchronize()
+    for ge, gc, gh, gt in zip(eager.param_groups, cap.param_groups, held.param_groups, cpu.param_groups):
+        pe, pc, ph, pt = (g["params"][0] for g in (ge, gc, gh, gt))
+        se, sc, st = eager.state[pe], cap.state[pc], cpu.state[pt]
+        assert float(se["step"]) == float(sc["step"]) == float(st["step"]) == 8.0, ge["name"]
+        for name, a, b, t in (("param", pe, pc, pt), ("exp_avg", se["exp_avg"], sc["exp_avg"], st["exp_avg"]),
+                              ("exp_avg_sq", se["exp_avg_sq"], sc["exp_avg_sq"], st["exp_avg_sq"])):
+            assert torch.equal(a, b), "%s of group %s" % (name, ge["name"])
+            ref_np = t.detach().numpy()
+            np.testing.assert_allclose(b.detach().cpu().numpy(), ref_np, rtol=3e-6, atol=3e-7 * float(np.abs(ref_np).max()),
+                                       err_msg="%s of group %s" % (name, ge["name"]))
+        # the guard: the schedule moved the result (a replay that kept the capture-time rate would equal `held`)
+        if ge["base_lr"] > 0:
+            assert not torch.equal(ph, pc), ge["name"]
+            assert float((ph.detach() - pc.detach()).abs().max()) > 1e-3 * ge["base_lr"], ge["name"]
+
+
+@pytest.mark.gpu
+def test_capturable_adam_never_hands_out_the_slot_of_a_rekeyed_parameter(gpu):
+    """Eight slots.  Seven tensors step and all are re-keyed (they keep their state, so their slots); the odd one then leaves
+    the optimizer -- its slot is the only dead one -- and two groups are added: the ninth tensor to ask for a slot forces the
+    reclaim, which must find that dead slot and none of the re-keyed parameters'.  One more tensor does not fit."""
+    from gftorf_amd import FusedAdam, densify
+    opt = FusedAdam(groups(gpu), lr=1e-3, eps=1e-15, capturable=True)
+    opt._SLOTS = 8
+    ext, keep = _new_rows()
+
+    def step():
+        for g in opt.param_groups:
+            p = g["params"][0]
+            p.grad = torch.ones_like(p)
+        opt.step()
+    step()
+    _densify(opt, gpu, ext, keep)
+    _rekey(opt, opt.param_groups[6])
+    buf = opt._buffers(gpu)
+    assert buf["step"].numel() == 8 and buf["used"] == 7
+    gone = opt.param_groups.pop(6)["params"][0]
+    gone_ptr = opt.state.pop(gone)["step"].data_ptr()
+    taken = {}
+    for i in range(2):
+        opt.add_param_group({"params": [torch.nn.Parameter(torch.zeros(5 + i, device=gpu))], "lr": 1e-3, "name": "new%d" % i})
+    for _ in range(3):
+        step()
+    for g in opt.param_groups:
+        st = opt.state[g["params"][0]]["step"]
+        assert st.data_ptr() not in taken, (g["name"], taken[st.data_ptr()])
+        taken[st.data_ptr()] = g["name"]
+        assert float(st) == (3.0 if g["name"].startswith("new") else 4.0), g["name"]
+    assert len(taken) == 8 and taken[gone_ptr] == "new1"
+    opt.add_param_group({"params": [torch.nn.Parameter(torch.zeros(3, device=gpu))], "lr": 1e-3, "name": "one too many"})
+    with pytest.raises(RuntimeError, match="more than 8 parameter tensors"):
+        step()
+
+
+@pytest.mark.gpu
+def test_refresh_lr_reaches_exactly_the_slot_of_a_rekeyed_parameter(gpu):
+    """After the densification re-keyed the parameters, a changed learning rate of one group changes that parameter's entry of
+    the pinned buffer a captured step copies from, and no other (read on the host: no replay needed)."""
+    from gftorf_amd import FusedAdam
+    opt = FusedAdam(groups(gpu), lr=0.0, eps=1e-15, capturable=True)
+    for g in opt.param_groups:
+        p = g["params"][0]
+        p.grad = torch.ones_like(p)
+    opt.step()
+    ext, keep = _new_rows()
+    _densify(opt, gpu, ext, keep)
+    _rekey(opt, opt.param_groups[6])
+    buf = opt._buffers(gpu)
+    lr_host = buf["lr_host"]
+    opt.refresh_lr()
+    assert lr_host[:7].tolist() == [g["lr"] for g in opt.param_groups] and not lr_host[7:].any()
+    for i, g in enumerate(opt.param_groups):
+        slot = (opt.state[g["params"][0]]["step"].data_ptr() - buf["step"].data_ptr()) // 4
+        assert slot == i                                  # (slots were given out in this order by the first step)
+        before = lr_host.clone()
+        g["lr"] = 0.125 + i
+        opt.refresh_lr()
+        assert torch.nonzero(lr_host != before)[:, 0].tolist() == [slot], g["name"]
+        assert float(lr_host[slot]) == 0.125 + i
