@@ -12,7 +12,9 @@ warm_up 2000) and keeps the reference loop's SHAPE, statement for statement (tra
     planes (train.py:209-231; lambda_color is 0 in torf.json) -> backward -> densification statistics
     (train.py:441-449) -> Adam on the Gaussians and, after warm_up, on the network (train.py:467-474).
 
-Densification / pruning / opacity reset, logging, checkpoints and the debug image dumps are left out.
+Densification / pruning / opacity reset, logging, checkpoints and the debug image dumps are left out,
+and so is the gradient-norm clip of the network (train.py:468; ``opt_net.step(max_grad_norm=1.0)`` is its fused form,
+INTEGRATION section F).
 Everything between the statements is this package (assemble_inputs, GaussianRasterizer, DeformNetwork, densify,
 FusedAdam); the losses and activations are stock torch, as in the reference.
 """

@@ -10,11 +10,11 @@ from .api import (GaussianRasterizationSettings, GaussianRasterizer, rasterize_g
 from .pair import GaussianRasterizerPair, render_pair  # noqa: F401
 from .assemble import assemble_inputs, assemble_parameters  # noqa: F401
 from .knn import distCUDA2  # noqa: F401
-from .optim import FusedAdam  # noqa: F401
+from .optim import FusedAdam, clip_grad_norm_  # noqa: F401
 from .deform import DeformNetwork, REFERENCE_ARCH, reference_network  # noqa: F401
 from . import densify  # noqa: F401
 from . import loss  # noqa: F401
 from . import flow  # noqa: F401
 
-__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "GaussianRasterizerPair", "render_pair", "assemble_inputs", "assemble_parameters", "distCUDA2", "FusedAdam",
+__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "GaussianRasterizerPair", "render_pair", "assemble_inputs", "assemble_parameters", "distCUDA2", "FusedAdam", "clip_grad_norm_",
            "DeformNetwork", "REFERENCE_ARCH", "reference_network", "densify"]

@@ -146,6 +146,8 @@ EXPORTS = [
     "gft_deform_dw_splits", "gft_deform_rows_splits_capacity",
     "gft_ssim_blocks", "gft_ssim_l2_forward", "gft_ssim_l2_backward",
     "gft_image_loss_forward", "gft_image_loss_backward", "gft_pixel_loss_blocks", "gft_pixel_loss_forward", "gft_pixel_loss_backward",
+    "gft_grad_norm_scratch_bytes", "gft_grad_norm", "gft_grad_scale", "gft_adam_step_multi_clip", "gft_adam_step_rows_clip",
+    "gft_adam_step_multi_dev_clip", "gft_adam_step_rows_dev",
     "gft_densify_stats", "gft_rows_rank_scratch_bytes", "gft_rows_rank", "gft_rows_rank_dev", "gft_rows_gather", "gft_rows_any_nonzero",
 ]
 # include/gftorf_flow.h (the scene-flow term; no struct, so the ABI version is unchanged)
@@ -208,6 +210,22 @@ def load():
     lib.gft_adam_step_rows.restype = C.c_int
     lib.gft_adam_step_rows.argtypes = [C.c_void_p, C.c_int32, C.POINTER(AdamTensor), C.c_int64, C.c_void_p, C.c_double, C.c_double,
                                        C.c_double, C.c_double]
+    _ptrs = C.POINTER(C.c_void_p)
+    lib.gft_adam_step_multi_clip.restype = C.c_int
+    lib.gft_adam_step_multi_clip.argtypes = lib.gft_adam_step_multi.argtypes + [C.c_void_p]
+    lib.gft_adam_step_rows_clip.restype = C.c_int
+    lib.gft_adam_step_rows_clip.argtypes = lib.gft_adam_step_rows.argtypes + [C.c_void_p]
+    lib.gft_adam_step_multi_dev_clip.restype = C.c_int
+    lib.gft_adam_step_multi_dev_clip.argtypes = lib.gft_adam_step_multi_dev.argtypes + [C.c_void_p]
+    lib.gft_adam_step_rows_dev.restype = C.c_int
+    lib.gft_adam_step_rows_dev.argtypes = [C.c_void_p, C.c_int32, C.POINTER(AdamTensor), C.c_int64, C.c_void_p, _ptrs, _ptrs, C.c_void_p,
+                                           C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]
+    lib.gft_grad_norm_scratch_bytes.restype = C.c_size_t
+    lib.gft_grad_norm_scratch_bytes.argtypes = [C.c_int64, C.c_int32]
+    lib.gft_grad_norm.restype = C.c_int
+    lib.gft_grad_norm.argtypes = [C.c_void_p, C.c_int32, _ptrs, C.POINTER(C.c_int64), C.c_double, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.gft_grad_scale.restype = C.c_int
+    lib.gft_grad_scale.argtypes = [C.c_void_p, C.c_int32, _ptrs, C.POINTER(C.c_int64), C.c_void_p]
     lib.gft_deform_packed_bytes.restype = C.c_size_t
     lib.gft_deform_packed_bytes.argtypes = []
     lib.gft_deform_saved_bytes.restype = C.c_size_t

@@ -15,11 +15,13 @@ struct AdamArgs {
     int64_t n;
     float* p; const float* g; float* m; float* v;
     float one_m_beta1, beta2, one_m_beta2, step_size, bias2_sqrt, eps, weight_decay;
+    float grad_scale;     // the clip coefficient (gft_grad_norm's out[1]); 1 when the caller gave none: g * 1 is g, bit for bit
 };
 
 __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, const AdamArgs& a)
 {
 #pragma clang fp contract(off)
+    g = g * a.grad_scale;                                     // clip_grad_norm_: grad.mul_(clip_coef_clamped), rounded on its own
     if (a.weight_decay != 0.f) g = g + a.weight_decay * p;
     m = m + a.one_m_beta1 * (g - m);                          // exp_avg.lerp_(grad, 1 - beta1)
     v = v * a.beta2 + (a.one_m_beta2 * g) * g;                // mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
@@ -87,7 +89,8 @@ __global__ __launch_bounds__(64) void k_adam_tick(AdamTickArgs a)
 }
 
 template <bool DEV>
-__global__ __launch_bounds__(ADAM_BLOCK) void k_adam_multi(AdamMultiArgs a, const float* __restrict__ factors)
+__global__ __launch_bounds__(ADAM_BLOCK) void k_adam_multi(AdamMultiArgs a, const float* __restrict__ factors,
+                                                           const float* __restrict__ grad_scale)
 {
     int k = 0;
 #pragma unroll 1
@@ -97,6 +100,7 @@ __global__ __launch_bounds__(ADAM_BLOCK) void k_adam_multi(AdamMultiArgs a, cons
     s.n = a.t[k].n; s.p = a.t[k].p; s.g = a.t[k].g; s.m = a.t[k].m; s.v = a.t[k].v;
     s.one_m_beta1 = a.one_m_beta1; s.beta2 = a.beta2; s.one_m_beta2 = a.one_m_beta2; s.step_size = a.t[k].step_size;
     s.bias2_sqrt = a.t[k].bias2_sqrt; s.eps = a.eps; s.weight_decay = a.weight_decay;
+    s.grad_scale = grad_scale ? *grad_scale : 1.f;
     if (DEV) {          // (t[k].pad: the tensor's index in the caller's table = its slot in `factors`)
         s.step_size = factors[2 * a.t[k].pad];
         s.bias2_sqrt = factors[2 * a.t[k].pad + 1];
@@ -148,7 +152,9 @@ struct AdamRowsArgs {
     uint32_t row_floats[GFT_ADAM_MAX_TENSORS];
 };
 
-__global__ __launch_bounds__(ADAM_BLOCK) void k_adam_rows(AdamRowsArgs a)
+template <bool DEV>
+__global__ __launch_bounds__(ADAM_BLOCK) void k_adam_rows(AdamRowsArgs a, const float* __restrict__ factors,
+                                                          const float* __restrict__ grad_scale)
 {
     int k = 0;
 #pragma unroll 1
@@ -158,6 +164,11 @@ __global__ __launch_bounds__(ADAM_BLOCK) void k_adam_rows(AdamRowsArgs a)
     s.n = a.m.t[k].n; s.p = a.m.t[k].p; s.g = a.m.t[k].g; s.m = a.m.t[k].m; s.v = a.m.t[k].v;
     s.one_m_beta1 = a.m.one_m_beta1; s.beta2 = a.m.beta2; s.one_m_beta2 = a.m.one_m_beta2; s.step_size = a.m.t[k].step_size;
     s.bias2_sqrt = a.m.t[k].bias2_sqrt; s.eps = a.m.eps; s.weight_decay = a.m.weight_decay;
+    s.grad_scale = grad_scale ? *grad_scale : 1.f;
+    if (DEV) {          // as k_adam_multi<true>: the factors k_adam_tick left for this tensor
+        s.step_size = factors[2 * a.m.t[k].pad];
+        s.bias2_sqrt = factors[2 * a.m.t[k].pad + 1];
+    }
     const uint32_t rf = a.row_floats[k];
     const uint32_t blk = blockIdx.x - a.m.t[k].first_block;
     const int64_t n4 = s.n >> 2;
@@ -202,7 +213,205 @@ __global__ __launch_bounds__(ADAM_BLOCK) void k_adam_rows(AdamRowsArgs a)
     }
 }
 
+// ---- gradient-norm clipping (torch.nn.utils.clip_grad_norm_, reference train.py:468) --------------------------------------
+// The global L2 norm of a set of gradient tensors, and the coefficient torch scales them by, left on the device for the Adam
+// kernels above (or for k_grad_scale).  One launch per GFT_ADAM_MAX_TENSORS spans, table in the kernel arguments as in
+// k_adam_multi; a span may start on any 4-byte boundary (the network's gradients are consecutive views of one buffer):
+// up to three scalars in front of the first 16-byte boundary, 16-byte groups, up to three scalars behind them.
+// No atomics and no counters: every workgroup stores ONE partial sum, a double, and a one-workgroup kernel adds the partials
+// in a fixed order -- the same bits every call, and every word that is read was written by the same call.
+#define NORM_BLOCK 256
+#define NORM_ITEMS 4      // 16-byte groups per thread, all loaded before the arithmetic: 16 KB per workgroup
+
+struct GradSpanArgs {
+    int count;
+    uint32_t first_partial;     // (norm) this launch's workgroup b writes partials[first_partial + b]
+    struct T { float* g; int64_t n; uint32_t first_block; uint32_t head; } t[GFT_ADAM_MAX_TENSORS];
+};
+
+// sum of one double per thread over the workgroup, in a fixed order; the result is valid in thread 0
+__device__ __forceinline__ double norm_block_sum(double d, double* lds)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) d += __shfl_down(d, o, 64);
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = d;
+    __syncthreads();
+    return lds[0] + lds[1] + lds[2] + lds[3];
+}
+
+__global__ __launch_bounds__(NORM_BLOCK) void k_grad_norm_partial(GradSpanArgs a, double* __restrict__ partials)
+{
+    __shared__ double lds[NORM_BLOCK / 64];
+    int k = 0;
+#pragma unroll 1
+    for (int q = 1; q < a.count; q++)
+        if (blockIdx.x >= a.t[q].first_block) k = q;
+    const float* g = a.t[k].g;
+    const int64_t n = a.t[k].n;
+    const uint32_t head = a.t[k].head;
+    const uint32_t blk = blockIdx.x - a.t[k].first_block;
+    const float4* body = reinterpret_cast<const float4*>(g + head);
+    const int64_t n4 = (n - head) >> 2;
+    float4 x[NORM_ITEMS];
+    int64_t idx[NORM_ITEMS];
+#pragma unroll
+    for (int u = 0; u < NORM_ITEMS; u++) {
+        idx[u] = ((int64_t)blk * NORM_ITEMS + u) * NORM_BLOCK + threadIdx.x;
+        if (n4 > 0) x[u] = body[idx[u] < n4 ? idx[u] : n4 - 1];
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int u = 0; u < NORM_ITEMS; u++)
+        if (idx[u] < n4) s += x[u].x * x[u].x + x[u].y * x[u].y + x[u].z * x[u].z + x[u].w * x[u].w;
+    if (blk == 0) {         // the scalars in front of and behind the 16-byte groups: at most three each
+        const uint32_t tail = (uint32_t)((n - head) & 3);
+        if (threadIdx.x < head) { const float e = g[threadIdx.x]; s += e * e; }
+        else if (threadIdx.x < head + tail) { const float e = g[(n4 << 2) + threadIdx.x]; s += e * e; }
+    }
+    const double d = norm_block_sum((double)s, lds);
+    if (threadIdx.x == 0) partials[a.first_partial + blockIdx.x] = d;
+}
+
+__global__ __launch_bounds__(NORM_BLOCK) void k_grad_norm_final(const double* __restrict__ partials, uint32_t count, float max_norm,
+                                                                float* __restrict__ out)
+{
+#pragma clang fp contract(off)
+    __shared__ double lds[NORM_BLOCK / 64];
+    double d = 0.0;
+    for (uint32_t i = threadIdx.x; i < count; i += NORM_BLOCK) d += partials[i];
+    d = norm_block_sum(d, lds);
+    if (threadIdx.x == 0) {
+        const float norm = (float)sqrt(d);
+        // torch/nn/utils/clip_grad.py: clip_coef = max_norm / (total_norm + 1e-6) -- which Tensor.__rtruediv__ forms as
+        // reciprocal() * max_norm, two fp32 roundings -- then clamp(max=1.0), which lets a NaN through
+        float c = (1.0f / (norm + 1e-6f)) * max_norm;
+        c = c > 1.0f ? 1.0f : c;
+        out[0] = norm;
+        out[1] = c;
+    }
+}
+
+__global__ __launch_bounds__(NORM_BLOCK) void k_grad_scale(GradSpanArgs a, const float* __restrict__ coef)
+{
+    const float c = *coef;
+    if (c == 1.0f) return;          // g * 1 is g: nothing to store
+    int k = 0;
+#pragma unroll 1
+    for (int q = 1; q < a.count; q++)
+        if (blockIdx.x >= a.t[q].first_block) k = q;
+    float* g = a.t[k].g;
+    const int64_t n = a.t[k].n;
+    const uint32_t head = a.t[k].head;
+    const uint32_t blk = blockIdx.x - a.t[k].first_block;
+    float4* body = reinterpret_cast<float4*>(g + head);
+    const int64_t n4 = (n - head) >> 2;
+    float4 x[NORM_ITEMS];
+    int64_t idx[NORM_ITEMS];
+#pragma unroll
+    for (int u = 0; u < NORM_ITEMS; u++) {
+        idx[u] = ((int64_t)blk * NORM_ITEMS + u) * NORM_BLOCK + threadIdx.x;
+        if (n4 > 0) x[u] = body[idx[u] < n4 ? idx[u] : n4 - 1];
+    }
+#pragma unroll
+    for (int u = 0; u < NORM_ITEMS; u++)
+        if (idx[u] < n4) body[idx[u]] = make_float4(x[u].x * c, x[u].y * c, x[u].z * c, x[u].w * c);
+    if (blk == 0) {
+        const uint32_t tail = (uint32_t)((n - head) & 3);
+        if (threadIdx.x < head) g[threadIdx.x] *= c;
+        else if (threadIdx.x < head + tail) g[(n4 << 2) + threadIdx.x] *= c;
+    }
+}
+
 }  // namespace
+
+// fills the span table of a launch from spans [c0 ...]; returns the number of entries (< 0: error)
+static int span_table(GradSpanArgs& a, float* const* grads, const int64_t* n, int32_t c0, int32_t count, uint64_t* blocks_out,
+                      const char* who)
+{
+    int k = 0;
+    uint64_t blocks = 0;
+    for (int32_t c = c0; c < count && c < c0 + GFT_ADAM_MAX_TENSORS; c++) {
+        if (n[c] < 0) { gft_fail("%s: span %d has n < 0", who, c); return -1; }
+        if (n[c] == 0) continue;
+        if (!grads[c]) { gft_fail("%s: span %d has a NULL pointer", who, c); return -1; }
+        if (((uintptr_t)grads[c] & 3) != 0) { gft_fail("%s: span %d is not 4-byte aligned", who, c); return -1; }
+        int64_t head = (int64_t)(((16 - ((uintptr_t)grads[c] & 15)) & 15) >> 2);
+        if (head > n[c]) head = n[c];
+        a.t[k].g = grads[c]; a.t[k].n = n[c]; a.t[k].head = (uint32_t)head; a.t[k].first_block = (uint32_t)blocks;
+        const int64_t n4 = (n[c] - head) >> 2;
+        const int64_t per_block = (int64_t)NORM_BLOCK * NORM_ITEMS;
+        blocks += n4 > 0 ? (uint64_t)((n4 + per_block - 1) / per_block) : 1;
+        k++;
+    }
+    if (blocks > 0x7fffffffull) { gft_fail("%s: too many elements for one launch", who); return -1; }
+    a.count = k;
+    *blocks_out = blocks;
+    return k;
+}
+
+extern "C" size_t gft_grad_norm_scratch_bytes(int64_t total_elements, int32_t count)
+{
+    if (total_elements < 0 || count < 0) return 0;
+    // a span of n elements takes at most n / (4 * NORM_BLOCK * NORM_ITEMS) + 1 workgroups, each with one double
+    return sizeof(double) * (size_t)(total_elements / (4 * NORM_BLOCK * NORM_ITEMS) + count + 1);
+}
+
+extern "C" int gft_grad_norm(void* hip_stream, int32_t count, const float* const* grads, const int64_t* n, double max_norm,
+                             void* scratch, size_t scratch_bytes, float* out)
+{
+    if (count < 0) return gft_fail("gft_grad_norm: count < 0");
+    if (count == 0 && !out) return 0;
+    if (count > 0 && (!grads || !n)) return gft_fail("gft_grad_norm: the span table is NULL");
+    if (!out) return gft_fail("gft_grad_norm: out is NULL");
+    uint64_t partials = 0;
+    // (a first pass over the tables: nothing is launched unless the whole call fits the scratch buffer)
+    for (int pass = 0; pass < 2; pass++) {
+        partials = 0;
+        for (int32_t c0 = 0; c0 < count; c0 += GFT_ADAM_MAX_TENSORS) {
+            GradSpanArgs a;
+            uint64_t blocks = 0;
+            const int k = span_table(a, const_cast<float* const*>(grads), n, c0, count, &blocks, "gft_grad_norm");
+            if (k < 0) return 1;
+            if (k == 0) continue;
+            if (pass == 1) {
+                a.first_partial = (uint32_t)partials;
+                hipLaunchKernelGGL(k_grad_norm_partial, dim3((unsigned)blocks), dim3(NORM_BLOCK), 0, (hipStream_t)hip_stream, a, (double*)scratch);
+            }
+            partials += blocks;
+        }
+        if (pass == 0 && partials > 0) {
+            if (partials > 0x7fffffffull) return gft_fail("gft_grad_norm: too many elements");
+            if (!scratch || ((uintptr_t)scratch & 7) != 0 || partials * sizeof(double) > scratch_bytes)
+                return gft_fail("gft_grad_norm: scratch is NULL, not 8-byte aligned or smaller than %llu bytes (gft_grad_norm_scratch_bytes)",
+                                (unsigned long long)(partials * sizeof(double)));
+        }
+    }
+    hipLaunchKernelGGL(k_grad_norm_final, dim3(1), dim3(NORM_BLOCK), 0, (hipStream_t)hip_stream, (const double*)scratch, (uint32_t)partials,
+                       (float)max_norm, out);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return gft_fail("gft_grad_norm: %s", hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int gft_grad_scale(void* hip_stream, int32_t count, float* const* grads, const int64_t* n, const float* coef)
+{
+    if (count < 0) return gft_fail("gft_grad_scale: count < 0");
+    if (count == 0) return 0;
+    if (!grads || !n) return gft_fail("gft_grad_scale: the span table is NULL");
+    if (!coef) return gft_fail("gft_grad_scale: coef is NULL");
+    for (int32_t c0 = 0; c0 < count; c0 += GFT_ADAM_MAX_TENSORS) {
+        GradSpanArgs a;
+        a.first_partial = 0;
+        uint64_t blocks = 0;
+        const int k = span_table(a, grads, n, c0, count, &blocks, "gft_grad_scale");
+        if (k < 0) return 1;
+        if (k == 0) continue;
+        hipLaunchKernelGGL(k_grad_scale, dim3((unsigned)blocks), dim3(NORM_BLOCK), 0, (hipStream_t)hip_stream, a, coef);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return gft_fail("gft_grad_scale: %s", hipGetErrorString(e));
+    }
+    return 0;
+}
 
 // fills the per-tensor table of a launch from tensors[c0 ...]; returns the number of entries (< 0: error)
 static int adam_table(AdamMultiArgs& a, const gft_adam_tensor* tensors, int32_t c0, int32_t count, double beta1, double beta2,
@@ -245,24 +454,108 @@ static int adam_table(AdamMultiArgs& a, const gft_adam_tensor* tensors, int32_t 
     return k;
 }
 
+// the tick of the device-side variants: the counts of tensors [c0, c1) advance, their factors are left in factors[2 c ...]
+static int adam_tick(void* hip_stream, int32_t c0, int32_t c1, const double* const* lr, float* const* step, float* factors, double beta1,
+                     double beta2, const char* who)
+{
+    AdamTickArgs tick;
+    tick.count = c1 - c0; tick.beta1 = beta1; tick.beta2 = beta2; tick.factors = factors + 2 * (size_t)c0;
+    for (int32_t c = c0; c < c1; c++) {
+        if (!lr[c] || !step[c]) return gft_fail("%s: tensor %d: lr / step pointer is NULL", who, c);
+        tick.lr[c - c0] = lr[c]; tick.step[c - c0] = step[c];
+    }
+    hipLaunchKernelGGL(k_adam_tick, dim3(1), dim3(64), 0, (hipStream_t)hip_stream, tick);
+    return 0;
+}
+
+// lr == NULL: learning rates and step counts of the table (host); otherwise on the device (k_adam_tick in front)
+static int adam_rows(void* hip_stream, int32_t count, const gft_adam_tensor* tensors, int64_t rows, const uint8_t* row_mask,
+                     const double* const* lr, float* const* step, float* factors, double beta1, double beta2, double eps,
+                     double weight_decay, const float* grad_scale, const char* who)
+{
+    for (int32_t c0 = 0; c0 < count; c0 += GFT_ADAM_MAX_TENSORS) {
+        const int32_t c1 = count < c0 + GFT_ADAM_MAX_TENSORS ? count : c0 + GFT_ADAM_MAX_TENSORS;
+        AdamRowsArgs a;
+        a.row_mask = row_mask;
+        uint64_t blocks = 0;
+        const int k = adam_table(a.m, tensors, c0, count, beta1, beta2, eps, weight_decay, &blocks, rows, a.row_floats, who, lr != nullptr);
+        if (k < 0) return 1;
+        if (lr) {
+            if (adam_tick(hip_stream, c0, c1, lr, step, factors, beta1, beta2, who)) return 1;
+            if (k > 0)
+                hipLaunchKernelGGL(k_adam_rows<true>, dim3((unsigned)blocks), dim3(ADAM_BLOCK), 0, (hipStream_t)hip_stream, a,
+                                   (const float*)(factors + 2 * (size_t)c0), grad_scale);
+        } else {
+            if (k == 0) continue;
+            hipLaunchKernelGGL(k_adam_rows<false>, dim3((unsigned)blocks), dim3(ADAM_BLOCK), 0, (hipStream_t)hip_stream, a,
+                               (const float*)nullptr, grad_scale);
+        }
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return gft_fail("%s: %s", who, hipGetErrorString(e));
+    }
+    return 0;
+}
+
+static int adam_multi(void* hip_stream, int32_t count, const gft_adam_tensor* tensors, const double* const* lr, float* const* step,
+                      float* factors, double beta1, double beta2, double eps, double weight_decay, const float* grad_scale,
+                      const char* who)
+{
+    for (int32_t c0 = 0; c0 < count; c0 += GFT_ADAM_MAX_TENSORS) {
+        const int32_t c1 = count < c0 + GFT_ADAM_MAX_TENSORS ? count : c0 + GFT_ADAM_MAX_TENSORS;
+        AdamMultiArgs a;
+        uint64_t blocks = 0;
+        const int k = adam_table(a, tensors, c0, count, beta1, beta2, eps, weight_decay, &blocks, 0, nullptr, who, lr != nullptr);
+        if (k < 0) return 1;
+        if (lr) {
+            // (the counts advance for every tensor of the table, as torch's capturable Adam advances state["step"] -- also for an
+            // empty tensor, which takes no update)
+            if (adam_tick(hip_stream, c0, c1, lr, step, factors, beta1, beta2, who)) return 1;
+            if (k > 0)
+                hipLaunchKernelGGL(k_adam_multi<true>, dim3((unsigned)blocks), dim3(ADAM_BLOCK), 0, (hipStream_t)hip_stream, a,
+                                   (const float*)(factors + 2 * (size_t)c0), grad_scale);
+        } else {
+            if (k == 0) continue;
+            hipLaunchKernelGGL(k_adam_multi<false>, dim3((unsigned)blocks), dim3(ADAM_BLOCK), 0, (hipStream_t)hip_stream, a,
+                               (const float*)nullptr, grad_scale);
+        }
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return gft_fail("%s: %s", who, hipGetErrorString(e));
+    }
+    return 0;
+}
+
 extern "C" int gft_adam_step_rows(void* hip_stream, int32_t count, const gft_adam_tensor* tensors, int64_t rows,
                                   const uint8_t* row_mask, double beta1, double beta2, double eps, double weight_decay)
 {
     if (count < 0) return gft_fail("gft_adam_step_rows: count < 0");
     if (count == 0 || rows == 0) return 0;
     if (!tensors || !row_mask || rows < 0) return gft_fail("gft_adam_step_rows: bad argument");
-    for (int32_t c0 = 0; c0 < count; c0 += GFT_ADAM_MAX_TENSORS) {
-        AdamRowsArgs a;
-        a.row_mask = row_mask;
-        uint64_t blocks = 0;
-        const int k = adam_table(a.m, tensors, c0, count, beta1, beta2, eps, weight_decay, &blocks, rows, a.row_floats, "gft_adam_step_rows");
-        if (k < 0) return 1;
-        if (k == 0) continue;
-        hipLaunchKernelGGL(k_adam_rows, dim3((unsigned)blocks), dim3(ADAM_BLOCK), 0, (hipStream_t)hip_stream, a);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return gft_fail("gft_adam_step_rows: %s", hipGetErrorString(e));
-    }
-    return 0;
+    return adam_rows(hip_stream, count, tensors, rows, row_mask, nullptr, nullptr, nullptr, beta1, beta2, eps, weight_decay, nullptr,
+                     "gft_adam_step_rows");
+}
+
+extern "C" int gft_adam_step_rows_clip(void* hip_stream, int32_t count, const gft_adam_tensor* tensors, int64_t rows,
+                                       const uint8_t* row_mask, double beta1, double beta2, double eps, double weight_decay,
+                                       const float* grad_scale)
+{
+    if (count < 0) return gft_fail("gft_adam_step_rows_clip: count < 0");
+    if (count == 0 || rows == 0) return 0;
+    if (!tensors || !row_mask || rows < 0) return gft_fail("gft_adam_step_rows_clip: bad argument (NULL table or mask, rows < 0)");
+    return adam_rows(hip_stream, count, tensors, rows, row_mask, nullptr, nullptr, nullptr, beta1, beta2, eps, weight_decay, grad_scale,
+                     "gft_adam_step_rows_clip");
+}
+
+extern "C" int gft_adam_step_rows_dev(void* hip_stream, int32_t count, const gft_adam_tensor* tensors, int64_t rows,
+                                      const uint8_t* row_mask, const double* const* lr, float* const* step, float* factors,
+                                      double beta1, double beta2, double eps, double weight_decay, const float* grad_scale)
+{
+    if (count < 0) return gft_fail("gft_adam_step_rows_dev: count < 0");
+    if (count == 0) return 0;
+    if (!tensors || !row_mask || !lr || !step || !factors) return gft_fail("gft_adam_step_rows_dev: NULL argument");
+    // (no rows: there would be counts to advance and nothing to update -- such tensors belong in gft_adam_step_multi_dev)
+    if (rows <= 0) return gft_fail("gft_adam_step_rows_dev: rows must be > 0");
+    return adam_rows(hip_stream, count, tensors, rows, row_mask, lr, step, factors, beta1, beta2, eps, weight_decay, grad_scale,
+                     "gft_adam_step_rows_dev");
 }
 
 extern "C" int gft_adam_step_multi(void* hip_stream, int32_t count, const gft_adam_tensor* tensors, double beta1,
@@ -271,17 +564,17 @@ extern "C" int gft_adam_step_multi(void* hip_stream, int32_t count, const gft_ad
     if (count < 0) return gft_fail("gft_adam_step_multi: count < 0");
     if (count == 0) return 0;
     if (!tensors) return gft_fail("gft_adam_step_multi: tensors is NULL");
-    for (int32_t c0 = 0; c0 < count; c0 += GFT_ADAM_MAX_TENSORS) {
-        AdamMultiArgs a;
-        uint64_t blocks = 0;
-        const int k = adam_table(a, tensors, c0, count, beta1, beta2, eps, weight_decay, &blocks, 0, nullptr, "gft_adam_step_multi");
-        if (k < 0) return 1;
-        if (k == 0) continue;
-        hipLaunchKernelGGL(k_adam_multi<false>, dim3((unsigned)blocks), dim3(ADAM_BLOCK), 0, (hipStream_t)hip_stream, a, (const float*)nullptr);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return gft_fail("gft_adam_step_multi: %s", hipGetErrorString(e));
-    }
-    return 0;
+    return adam_multi(hip_stream, count, tensors, nullptr, nullptr, nullptr, beta1, beta2, eps, weight_decay, nullptr, "gft_adam_step_multi");
+}
+
+extern "C" int gft_adam_step_multi_clip(void* hip_stream, int32_t count, const gft_adam_tensor* tensors, double beta1,
+                                        double beta2, double eps, double weight_decay, const float* grad_scale)
+{
+    if (count < 0) return gft_fail("gft_adam_step_multi_clip: count < 0");
+    if (count == 0) return 0;
+    if (!tensors) return gft_fail("gft_adam_step_multi_clip: tensors is NULL");
+    return adam_multi(hip_stream, count, tensors, nullptr, nullptr, nullptr, beta1, beta2, eps, weight_decay, grad_scale,
+                      "gft_adam_step_multi_clip");
 }
 
 extern "C" int gft_adam_step_multi_dev(void* hip_stream, int32_t count, const gft_adam_tensor* tensors, const double* const* lr,
@@ -291,28 +584,18 @@ extern "C" int gft_adam_step_multi_dev(void* hip_stream, int32_t count, const gf
     if (count < 0) return gft_fail("gft_adam_step_multi_dev: count < 0");
     if (count == 0) return 0;
     if (!tensors || !lr || !step || !factors) return gft_fail("gft_adam_step_multi_dev: NULL argument");
-    for (int32_t c0 = 0; c0 < count; c0 += GFT_ADAM_MAX_TENSORS) {
-        const int32_t c1 = count < c0 + GFT_ADAM_MAX_TENSORS ? count : c0 + GFT_ADAM_MAX_TENSORS;
-        AdamTickArgs tick;
-        tick.count = c1 - c0; tick.beta1 = beta1; tick.beta2 = beta2; tick.factors = factors + 2 * (size_t)c0;
-        for (int32_t c = c0; c < c1; c++) {
-            if (!lr[c] || !step[c]) return gft_fail("gft_adam_step_multi_dev: tensor %d: lr / step pointer is NULL", c);
-            tick.lr[c - c0] = lr[c]; tick.step[c - c0] = step[c];
-        }
-        AdamMultiArgs a;
-        uint64_t blocks = 0;
-        const int k = adam_table(a, tensors, c0, count, beta1, beta2, eps, weight_decay, &blocks, 0, nullptr, "gft_adam_step_multi_dev", true);
-        if (k < 0) return 1;
-        // (the counts advance for every tensor of the table, as torch's capturable Adam advances state["step"] -- also for an
-        // empty tensor, which takes no update)
-        hipLaunchKernelGGL(k_adam_tick, dim3(1), dim3(64), 0, (hipStream_t)hip_stream, tick);
-        if (k > 0)
-            hipLaunchKernelGGL(k_adam_multi<true>, dim3((unsigned)blocks), dim3(ADAM_BLOCK), 0, (hipStream_t)hip_stream, a,
-                               (const float*)(factors + 2 * (size_t)c0));
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return gft_fail("gft_adam_step_multi_dev: %s", hipGetErrorString(e));
-    }
-    return 0;
+    return adam_multi(hip_stream, count, tensors, lr, step, factors, beta1, beta2, eps, weight_decay, nullptr, "gft_adam_step_multi_dev");
+}
+
+extern "C" int gft_adam_step_multi_dev_clip(void* hip_stream, int32_t count, const gft_adam_tensor* tensors, const double* const* lr,
+                                            float* const* step, float* factors, double beta1, double beta2, double eps,
+                                            double weight_decay, const float* grad_scale)
+{
+    if (count < 0) return gft_fail("gft_adam_step_multi_dev_clip: count < 0");
+    if (count == 0) return 0;
+    if (!tensors || !lr || !step || !factors) return gft_fail("gft_adam_step_multi_dev_clip: NULL argument");
+    return adam_multi(hip_stream, count, tensors, lr, step, factors, beta1, beta2, eps, weight_decay, grad_scale,
+                      "gft_adam_step_multi_dev_clip");
 }
 
 extern "C" int gft_adam_step(void* hip_stream, int64_t n, float* param, const float* grad, float* exp_avg,
@@ -336,6 +619,7 @@ extern "C" int gft_adam_step(void* hip_stream, int64_t n, float* param, const fl
     a.bias2_sqrt = (float)sqrt(1.0 - pow(beta2, (double)step));
     a.eps = (float)eps;
     a.weight_decay = (float)weight_decay;
+    a.grad_scale = 1.f;
     const int64_t n4 = n >> 2;
     const int64_t blocks = n4 > 0 ? (n4 + ADAM_BLOCK - 1) / ADAM_BLOCK : 1;
     hipLaunchKernelGGL(k_adam_step, dim3((unsigned)blocks), dim3(ADAM_BLOCK), 0, (hipStream_t)hip_stream, a);

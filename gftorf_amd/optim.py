@@ -21,11 +21,90 @@ the learning rates are read on the device from a small buffer that every ``step(
 pinned host memory -- a copy node when captured, so a replay sees whatever ``refresh_lr()`` (or any eager bookkeeping
 that ends in it: the reference's ``update_learning_rate``, scene/gaussian_model.py:294-310, then ``refresh_lr()``) wrote
 there since.  Bias corrections are formed in double precision on the device: N replays leave the parameters N eager
-non-capturable steps would (to the rounding of one double ``pow``).  ``visibility`` is not available in this mode.
+non-capturable steps would (to the rounding of one double ``pow``).  ``step(visibility=mask)`` works in this mode too: the
+mask is read when the kernel runs, so a replay follows the mask's contents of that replay.
+
+Gradient-norm clipping (``train.py:468``: ``torch.nn.utils.clip_grad_norm_(deform.parameters(), max_norm=1.0)``) has two
+forms.  ``clip_grad_norm_`` is the drop-in: one norm launch per 40 tensors, a one-workgroup sum, one scaling launch per 40
+tensors, no host read, so it can be captured.  ``FusedAdam.step(max_grad_norm=1.0)`` folds the scaling into the update: the
+norm over every gradient of this optimizer is left on the device with torch's coefficient ``min(1, max_norm / (norm + 1e-6))``,
+and every Adam launch multiplies the gradients by it as it reads them -- the update is the one ``clip_grad_norm_`` followed by
+``step()`` gives, bit for bit, but ``.grad`` is NOT written (the reference drops the gradients two lines later,
+``train.py:473-474``).  ``optimizer.last_grad_norm`` is the norm, a 0-dim device tensor.  Eager, capturable and
+``visibility`` steps all take it.  Under data parallelism the clip comes after ``allreduce_gradients``.
 """
+import ctypes as C
+
 import torch
 
 from . import _lib
+
+_NORM_SCRATCH = {}          # (device index, stream) -> the norm's partial sums (bytes), kept from call to call
+
+
+def _span_tables(grads):
+    n = len(grads)
+    return (C.c_void_p * n)(*[g.data_ptr() for g in grads]), (C.c_int64 * n)(*[g.numel() for g in grads])
+
+
+def _grad_norm(lib, dev, grads, max_norm, ptrs=None, ns=None):
+    """(norm, coefficient) of gft_grad_norm over ``grads`` (contiguous fp32 tensors on ``dev``) as a fresh 2-element device
+    tensor.  The partial sums go through a buffer kept per device and stream -- except while a graph is captured: a buffer
+    baked into a graph comes from the graph's pool (a kept one may be replaced by a larger one, which would free it under
+    the graph), the rule of ``api.py``."""
+    if ptrs is None:
+        ptrs, ns = _span_tables(grads)
+    n = len(grads)
+    need = lib.gft_grad_norm_scratch_bytes(sum(ns), n)
+    stream = _lib.raw_stream(dev)
+    if torch.cuda.is_current_stream_capturing():
+        scratch = torch.empty((need,), device=dev, dtype=torch.uint8)
+    else:
+        key = (dev.index, stream)
+        scratch = _NORM_SCRATCH.get(key)
+        if scratch is None or scratch.numel() < need:
+            if len(_NORM_SCRATCH) > 16:
+                _NORM_SCRATCH.clear()
+            scratch = _NORM_SCRATCH[key] = torch.empty((max(need, 4096),), device=dev, dtype=torch.uint8)
+    out = torch.empty((2,), device=dev, dtype=torch.float32)
+    with _lib.on_device(dev):
+        _lib.check(lib.gft_grad_norm(stream, n, ptrs, ns, float(max_norm), scratch.data_ptr(), scratch.numel(), out.data_ptr()))
+    return out
+
+
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None):
+    """``torch.nn.utils.clip_grad_norm_`` for fp32 gradients on a HIP device, L2 norm (``train.py:468``): the gradients are
+    scaled in place by ``min(1, max_norm / (norm + 1e-6))``; returns the norm, a 0-dim fp32 device tensor.  Nothing is read
+    on the host and nothing is cleared: the call can be captured in a graph (``error_if_nonfinite=True`` reads the norm, so
+    it cannot).  ``foreach`` is accepted and ignored."""
+    if float(norm_type) != 2.0:
+        raise NotImplementedError("gftorf_amd.clip_grad_norm_: norm_type=%r is not supported (the L2 norm only)" % (norm_type,))
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    grads = [p.grad for p in parameters if p.grad is not None]
+    if not grads:
+        return torch.tensor(0.0)
+    dev = grads[0].device
+    for g in grads:
+        if g.device.type != "cuda":
+            raise RuntimeError("gftorf_amd.clip_grad_norm_ runs on a HIP device only (gradient on %s); there is no CPU path" % (g.device,))
+        if g.device != dev:
+            raise RuntimeError("gftorf_amd.clip_grad_norm_: gradients on %s and %s (one device per call)" % (dev, g.device))
+        if g.is_sparse or g.dtype != torch.float32 or not g.is_contiguous():
+            raise RuntimeError("gftorf_amd.clip_grad_norm_: gradients must be dense contiguous float32 tensors")
+    if error_if_nonfinite and torch.cuda.is_current_stream_capturing():
+        raise NotImplementedError("gftorf_amd.clip_grad_norm_: error_if_nonfinite=True reads the norm on the host, which a "
+                                  "captured call cannot")
+    lib = _lib.load()
+    ptrs, ns = _span_tables(grads)
+    out = _grad_norm(lib, dev, grads, max_norm, ptrs, ns)
+    if error_if_nonfinite and not bool(torch.isfinite(out[0])):
+        raise RuntimeError("The total norm of order %s for gradients from `parameters` is non-finite, so it cannot be clipped. "
+                           "To disable this error and scale the gradients by the non-finite norm anyway, set "
+                           "`error_if_nonfinite=False`" % (float(norm_type),))
+    with _lib.on_device(dev):
+        _lib.check(lib.gft_grad_scale(_lib.raw_stream(dev), len(grads), ptrs, ns, out.data_ptr() + 4))
+    return out[0]
 
 
 class FusedAdam(torch.optim.Adam):
@@ -36,6 +115,7 @@ class FusedAdam(torch.optim.Adam):
         kw.pop("fused", None)
         self._gft_capturable = bool(kw.pop("capturable", False))
         self._gft_dev = {}              # device -> dict(step, lr, lr_host, factors, used): the buffers of the capturable mode
+        self.last_grad_norm = None      # step(max_grad_norm=...): the gradients' global L2 norm, a 0-dim device tensor
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, **kw)
 
     # ---- capturable mode ------------------------------------------------------------------------------------------
@@ -105,9 +185,26 @@ class FusedAdam(torch.optim.Adam):
                     if slot is not None:
                         b["lr_np"][slot] = lr
 
-    def _step_capturable(self, lib):
-        import ctypes as C
-        buckets = {}
+    def _clip_coef(self, lib, grads, max_grad_norm):
+        """The device address of the clip coefficient for this step's launches (None: no clipping).  The norm runs over every
+        gradient of the step -- all groups, all launch buckets, in the order of ``param_groups`` -- as ``clip_grad_norm_`` over
+        the optimizer's parameters would; ``grads`` are the tensors the launches read (a gradient that was copied for
+        alignment is not copied again)."""
+        if max_grad_norm is None:
+            return None
+        if not grads:
+            self.last_grad_norm = torch.tensor(0.0)
+            return None
+        devs = {g.device for g in grads}
+        if len(devs) != 1:
+            raise RuntimeError("gftorf_amd.FusedAdam: step(max_grad_norm=...) needs all gradients on one device, got %s" % sorted(map(str, devs)))
+        out = _grad_norm(lib, grads[0].device, grads, max_grad_norm)
+        self._gft_clip = out            # (alive until the launches that read it are on the stream and the next step replaces it)
+        self.last_grad_norm = out[0]
+        return out.data_ptr() + 4
+
+    def _step_capturable(self, lib, visibility=None, rows=None, mask_u8=None, row_params=None, max_grad_norm=None):
+        buckets, grads = {}, []
         for group in self.param_groups:
             beta1, beta2 = group["betas"]
             eps, wd = group["eps"], group["weight_decay"]
@@ -132,12 +229,21 @@ class FusedAdam(torch.optim.Adam):
                     grad = grad.clone()
                 if p.data_ptr() % 16 or m.data_ptr() % 16 or v.data_ptr() % 16 or not (m.is_contiguous() and v.is_contiguous()):
                     raise RuntimeError("gftorf_amd.FusedAdam: parameters and optimizer state must be contiguous and 16-byte aligned")
-                buckets.setdefault((p.device, float(beta1), float(beta2), float(eps), float(wd)), []).append((p, grad, m, v, slot))
-        for (dev, beta1, beta2, eps, wd), items in buckets.items():
+                by_rows = rows is not None and p.dim() >= 1 and p.shape[0] == rows and rows > 0 and (
+                    row_params is None or id(p) in row_params)
+                if by_rows and visibility.device != p.device:
+                    raise RuntimeError("gftorf_amd.FusedAdam: visibility is on %s, the parameter on %s" % (visibility.device, p.device))
+                buckets.setdefault((p.device, float(beta1), float(beta2), float(eps), float(wd), by_rows), []).append((p, grad, m, v, slot))
+                grads.append(grad)
+        coef = self._clip_coef(lib, grads, max_grad_norm)
+        copied = set()
+        for (dev, beta1, beta2, eps, wd, by_rows), items in buckets.items():
             b = self._buffers(dev)
             # the learning rates of this step: host values -> device, a copy node under capture (a replay re-reads the pinned
-            # buffer: refresh_lr)
-            b["lr"].copy_(b["lr_host"], non_blocking=True)
+            # buffer: refresh_lr); once per device
+            if dev not in copied:
+                b["lr"].copy_(b["lr_host"], non_blocking=True)
+                copied.add(dev)
             n = len(items)
             tab = (_lib.AdamTensor * n)()
             lrs, steps = (C.c_void_p * n)(), (C.c_void_p * n)()
@@ -147,16 +253,25 @@ class FusedAdam(torch.optim.Adam):
                 e.lr, e.step = 0.0, 0
                 lrs[i], steps[i] = lr0 + 8 * slot, st0 + 4 * slot
             with _lib.on_device(dev):
-                _lib.check(lib.gft_adam_step_multi_dev(_lib.raw_stream(dev), n, tab, lrs, steps, b["factors"].data_ptr(),
-                                                       beta1, beta2, eps, wd))
+                if by_rows:
+                    _lib.check(lib.gft_adam_step_rows_dev(_lib.raw_stream(dev), n, tab, rows, mask_u8.data_ptr(), lrs, steps,
+                                                          b["factors"].data_ptr(), beta1, beta2, eps, wd, coef))
+                elif coef is not None:
+                    _lib.check(lib.gft_adam_step_multi_dev_clip(_lib.raw_stream(dev), n, tab, lrs, steps, b["factors"].data_ptr(),
+                                                                beta1, beta2, eps, wd, coef))
+                else:
+                    _lib.check(lib.gft_adam_step_multi_dev(_lib.raw_stream(dev), n, tab, lrs, steps, b["factors"].data_ptr(),
+                                                           beta1, beta2, eps, wd))
 
     @torch.no_grad()
-    def step(self, closure=None, visibility=None, row_params=None):
+    def step(self, closure=None, visibility=None, row_params=None, max_grad_norm=None):
         """``visibility``: opt-in row mask (see the module docstring).  ``row_params``: the parameters the mask applies to
         (an iterable of tensors; default: every parameter whose first dimension equals ``visibility.numel()`` -- name
         them when another parameter, e.g. a network weight, could have that many rows by coincidence).  A row that is
         skipped keeps its moments, and the bias correction uses the tensor's one step count: a row that was skipped
-        k times is corrected as if it had taken those k steps (dense Adam differs there as well as in the decay)."""
+        k times is corrected as if it had taken those k steps (dense Adam differs there as well as in the decay).
+        ``max_grad_norm``: the update of ``clip_grad_norm_(all parameters of this optimizer, max_grad_norm)`` followed by
+        ``step()``, with ``.grad`` left unscaled and the norm in ``self.last_grad_norm`` (see the module docstring)."""
         loss = None
         rows = None
         if row_params is not None:
@@ -172,13 +287,11 @@ class FusedAdam(torch.optim.Adam):
                 loss = closure()
         lib = _lib.load()
         if self._gft_capturable:
-            if visibility is not None:
-                raise NotImplementedError("gftorf_amd.FusedAdam(capturable=True): step(visibility=...) is not available")
-            self._step_capturable(lib)
+            self._step_capturable(lib, visibility, rows, mask_u8 if visibility is not None else None, row_params, max_grad_norm)
             return loss
         # (parameter, gradient, moments, lr, step tensor) of every tensor that takes a step, bucketed by the settings
         # one launch shares: (device, betas, eps, weight decay)
-        buckets = {}
+        buckets, grads = {}, []
         for group in self.param_groups:
             beta1, beta2 = group["betas"]
             lr, eps, wd = group["lr"], group["eps"], group["weight_decay"]
@@ -216,15 +329,22 @@ class FusedAdam(torch.optim.Adam):
                     raise RuntimeError("gftorf_amd.FusedAdam: visibility is on %s, the parameter on %s" % (visibility.device, p.device))
                 buckets.setdefault((p.device, float(beta1), float(beta2), float(eps), float(wd), by_rows), []).append(
                     (p, grad, m, v, float(lr), state["step"]))
+                grads.append(grad)
+        coef = self._clip_coef(lib, grads, max_grad_norm)
         for (dev, beta1, beta2, eps, wd, by_rows), items in buckets.items():
             tab = (_lib.AdamTensor * len(items))()
             for e, (p, g, m, v, lr, st) in zip(tab, items):
                 e.param, e.grad, e.exp_avg, e.exp_avg_sq, e.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
                 e.lr, e.step = lr, int(st) + 1
             with _lib.on_device(dev):
-                if by_rows:
+                if by_rows and coef is not None:
+                    _lib.check(lib.gft_adam_step_rows_clip(_lib.raw_stream(dev), len(items), tab, rows, mask_u8.data_ptr(), beta1,
+                                                           beta2, eps, wd, coef))
+                elif by_rows:
                     _lib.check(lib.gft_adam_step_rows(_lib.raw_stream(dev), len(items), tab, rows, mask_u8.data_ptr(), beta1, beta2,
                                                       eps, wd))
+                elif coef is not None:
+                    _lib.check(lib.gft_adam_step_multi_clip(_lib.raw_stream(dev), len(items), tab, beta1, beta2, eps, wd, coef))
                 else:
                     _lib.check(lib.gft_adam_step_multi(_lib.raw_stream(dev), len(items), tab, beta1, beta2, eps, wd))
             # the step counters advance only once the launch was accepted (a rejected table leaves every tensor of the

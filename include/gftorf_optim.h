@@ -69,6 +69,51 @@ int gft_adam_step_multi_dev(void* hip_stream, int32_t count, const gft_adam_tens
                             const double* const* lr /*host array of device pointers*/, float* const* step /*host array of device pointers*/,
                             float* factors /*device, 2 * count floats*/, double beta1, double beta2, double eps, double weight_decay);
 
+/* The row-masked update with the learning rates and step counts on the device: gft_adam_step_rows behind the tick of
+ * gft_adam_step_multi_dev (lr, step, factors as there; every count advances, one per tensor, whatever the mask holds).
+ * row_mask is read when the kernel runs: a replayed graph follows the mask's contents of that replay.  rows > 0.
+ * grad_scale: see below; NULL = none. */
+int gft_adam_step_rows_dev(void* hip_stream, int32_t count, const gft_adam_tensor* tensors /*host*/, int64_t rows,
+                           const uint8_t* row_mask, const double* const* lr /*host array of device pointers*/,
+                           float* const* step /*host array of device pointers*/, float* factors /*device, 2 * count floats*/,
+                           double beta1, double beta2, double eps, double weight_decay, const float* grad_scale /*device or NULL*/);
+
+/* ---- gradient-norm clipping: torch.nn.utils.clip_grad_norm_(parameters, max_norm) with the L2 norm (reference train.py:468).
+ *
+ * A set of gradient tensors is given as two host arrays: grads[c] (device pointer, fp32, any 4-byte alignment) and n[c]
+ * (elements, >= 0; a span of 0 elements is skipped and its pointer is not looked at).
+ *
+ * gft_grad_norm:  out[0] = sqrt(sum of g^2 over all spans), out[1] = min(1, max_norm / (out[0] + 1e-6)), the coefficient
+ * torch multiplies the gradients by, formed in fp32 as torch forms it (reciprocal, times max_norm, clamp: a NaN stays a NaN).
+ * Squares are added in fp32 inside a thread (16 groups of four at most), everything above that in double; one double per
+ * workgroup goes through `scratch` (device, 8-byte aligned, gft_grad_norm_scratch_bytes(sum of n, count) bytes: host-only
+ * query, an upper bound) and is added in a fixed order: no atomics, no counters, nothing to clear beforehand, the same bits
+ * every call.  Squares that overflow fp32 give inf, a NaN gives NaN in both outputs, as in torch.  count == 0 (or only
+ * empty spans) writes out = {0, 1}; with count == 0 and out == NULL nothing is done.  No host read: capturable. */
+size_t gft_grad_norm_scratch_bytes(int64_t total_elements, int32_t count);
+int gft_grad_norm(void* hip_stream, int32_t count, const float* const* grads /*host array of device pointers*/,
+                  const int64_t* n /*host*/, double max_norm, void* scratch /*device*/, size_t scratch_bytes,
+                  float* out /*device, 2 floats*/);
+
+/* g *= *coef over the same kind of table, in place (coef: device, e.g. out + 1 of gft_grad_norm).  Nothing is stored when
+ * *coef == 1, the values being the same. */
+int gft_grad_scale(void* hip_stream, int32_t count, float* const* grads /*host array of device pointers*/,
+                   const int64_t* n /*host*/, const float* coef /*device*/);
+
+/* The three Adam launches with the gradient scale read from the device (grad_scale: device pointer to one float, e.g.
+ * out + 1 of gft_grad_norm; NULL = the functions above): every gradient value is multiplied by *grad_scale, rounded to fp32,
+ * before anything else -- the update equals the one of the functions above on gradients scaled by gft_grad_scale, bit for
+ * bit -- and the gradient memory is not written. */
+int gft_adam_step_multi_clip(void* hip_stream, int32_t count, const gft_adam_tensor* tensors /*host*/, double beta1,
+                             double beta2, double eps, double weight_decay, const float* grad_scale /*device or NULL*/);
+int gft_adam_step_rows_clip(void* hip_stream, int32_t count, const gft_adam_tensor* tensors /*host*/, int64_t rows,
+                            const uint8_t* row_mask, double beta1, double beta2, double eps, double weight_decay,
+                            const float* grad_scale /*device or NULL*/);
+int gft_adam_step_multi_dev_clip(void* hip_stream, int32_t count, const gft_adam_tensor* tensors /*host*/,
+                                 const double* const* lr /*host array of device pointers*/, float* const* step /*host array of device pointers*/,
+                                 float* factors /*device, 2 * count floats*/, double beta1, double beta2, double eps, double weight_decay,
+                                 const float* grad_scale /*device or NULL*/);
+
 #ifdef __cplusplus
 }
 #endif
