@@ -7,6 +7,8 @@ The reference's statements on torch tensors (they are device-agnostic; the tests
 * :func:`stats_loops` -- the same, one Gaussian at a time in numpy float32 (pins the eager statements).
 * :func:`prune_optimizer_eager`, :func:`cat_tensors_to_optimizer_eager` -- GaussianModel._prune_optimizer /
   cat_tensors_to_optimizer (scene/gaussian_model.py:473-492, 516-537).
+* :class:`EagerGaussians` -- the composites (:494-646) and the opacity reset (``reset_opacity`` :369-376 through
+  ``replace_tensor_to_optimizer`` :456-471) as methods of a minimal model object; :func:`reset_opacity_loops` pins the reset.
 
 Only tests/, __graft_entry__.smoke() and bench.py's baseline leg may import this module.
 """
@@ -84,6 +86,25 @@ def cat_tensors_to_optimizer_eager(optimizer, tensors_dict):
     return out
 
 
+def inverse_sigmoid(x):                                                                                   # utils/general_utils.py:20-21
+    return torch.log(x / (1 - x))
+
+
+def reset_opacity_loops(opacity_raw, apply=None):
+    """reset_opacity's new raw opacities one Gaussian at a time (numpy, float64 arithmetic on the float32 values):
+    (new values, rows the reset wrote).  A row outside ``apply`` keeps its bits."""
+    out = np.asarray(opacity_raw, np.float32).copy()
+    wrote = np.zeros(out.shape[0], bool)
+    cap = np.float64(np.float32(0.01))
+    for i in range(out.shape[0]):
+        if apply is not None and not apply[i]:
+            continue
+        o = min(1.0 / (1.0 + np.exp(-np.float64(out[i, 0]))), cap)
+        out[i, 0] = np.float32(np.log(o / (1.0 - o)))
+        wrote[i] = True
+    return out, wrote
+
+
 # ---- the composites of scene/gaussian_model.py:494-646, restated on a minimal model object ------------------------
 class EagerGaussians:
     """The attributes of the reference's ``GaussianModel`` that densification touches (scene/gaussian_model.py:55-153),
@@ -97,28 +118,78 @@ class EagerGaussians:
 
     def __init__(self, P, dev, seed, optimizer_cls=torch.optim.Adam):
         g = torch.Generator().manual_seed(seed)
+        tensors = {}
         for name, attr, shape in self.GROUPS:
             t = torch.randn((P,) + shape, generator=g)
             if name == "scaling":
                 t = torch.log(torch.exp(t * 0.7) * 0.02)          # world-space extents around 0.02
             if name == "opacity":
                 t = t * 2.0                                       # sigmoid(.) spread over (0, 1)
-            setattr(self, attr, nn.Parameter(t.to(dev).requires_grad_(True)))
-        self._phase_offset = nn.Parameter(torch.zeros(1, device=dev))
-        l = [{"params": [getattr(self, attr)], "lr": 1e-3, "name": name} for name, attr, _ in self.GROUPS]
-        l.append({"params": [self._phase_offset], "lr": 0.0, "name": "phase_offset"})
-        self.optimizer = optimizer_cls(l, lr=0.0, eps=1e-15)
+            tensors[name] = t.to(dev)
+        self._setup(tensors, optimizer_cls, {})
         for grp in self.optimizer.param_groups:                  # one step so that the moments exist
             p = grp["params"][0]
             p.grad = torch.randn(p.shape, generator=g).to(dev) * 1e-3
         self.optimizer.step()
         self.optimizer.zero_grad(set_to_none=True)
-        self.percent_dense = 0.01
-        self.isotropic = False
         self.xyz_gradient_accum = (torch.rand((P, 1), generator=g) * 4e-4 * 50).to(dev)
         self.denom = torch.randint(0, 100, (P, 1), generator=g).float().to(dev)            # zeros -> nan gradients
         self.max_radii2D = (torch.rand(P, generator=g) * 30).to(dev)
+
+    def _setup(self, tensors, optimizer_cls, lrs, **optimizer_kw):
+        """Parameters (group name -> tensor, copied), the reference's optimizer groups (scene/gaussian_model.py:247-274)
+        and zero statistics (:239-241)."""
+        for name, attr, _ in self.GROUPS:
+            setattr(self, attr, nn.Parameter(tensors[name].detach().clone().requires_grad_(True)))
+        dev = self._xyz.device
+        P = self._xyz.shape[0]
+        self._phase_offset = nn.Parameter(torch.zeros(1, device=dev))
+        l = [{"params": [getattr(self, attr)], "lr": lrs.get(name, 1e-3), "name": name} for name, attr, _ in self.GROUPS]
+        l.append({"params": [self._phase_offset], "lr": 0.0, "name": "phase_offset"})
+        self.optimizer = optimizer_cls(l, lr=0.0, eps=1e-15, **optimizer_kw)
+        self.percent_dense = 0.01
+        self.isotropic = False
+        self.xyz_gradient_accum = torch.zeros((P, 1), device=dev)
+        self.denom = torch.zeros((P, 1), device=dev)
+        self.max_radii2D = torch.zeros((P,), device=dev)
         self.scaling_activation, self.scaling_inverse_activation = torch.exp, torch.log
+
+    @classmethod
+    def from_scene(cls, gaussians, dev, optimizer_cls=torch.optim.Adam, lrs=None, **optimizer_kw):
+        """A model that renders: ``gaussians`` holds ACTIVATED values as the rasterizer takes them (means3D, opacities in
+        (0, 1), scales > 0, rotations, shs [P, 16, 3], shs_p [P, 16, 2]: gftorf_amd.synth.make_gaussians); the model keeps
+        what GaussianModel keeps -- the inverse sigmoid of the opacity, the log of the scaling, the feature tensors split
+        into their dc and rest parts (scene/gaussian_model.py:180-236).  No optimizer step is taken."""
+        t = lambda a: torch.as_tensor(np.asarray(a, np.float32))
+        P = gaussians["means3D"].shape[0]
+        shs, shs_p = t(gaussians["shs"]), t(gaussians["shs_p"])
+        tensors = {"xyz": t(gaussians["means3D"]), "f_dc_color": shs[:, :1, :], "f_rest_color": shs[:, 1:, :],
+                   "phase_f_dc": shs_p[:, :1, :1], "phase_f_rest": shs_p[:, 1:, :1], "amp_f_dc": shs_p[:, :1, 1:],
+                   "amp_f_rest": shs_p[:, 1:, 1:], "opacity": inverse_sigmoid(t(gaussians["opacities"]).reshape(P, 1)),
+                   "scaling": torch.log(t(gaussians["scales"])), "rotation": t(gaussians["rotations"]),
+                   "f_seg_color": torch.zeros((P, 3))}
+        self = cls.__new__(cls)
+        self._setup({k: v.contiguous().to(dev) for k, v in tensors.items()}, optimizer_cls, lrs or {}, **optimizer_kw)
+        return self
+
+    def twin(self, optimizer_cls=torch.optim.Adam, dev=None):
+        """A copy that shares no memory with this model: parameters, both Adam moments and ``step`` of every group that has
+        a state, learning rates, the three statistics -- under an optimizer of ``optimizer_cls`` (``step`` as a 0-dim fp32 CPU
+        tensor, as torch.optim.Adam keeps it)."""
+        dev = self._xyz.device if dev is None else dev
+        other = type(self).__new__(type(self))
+        other._setup({name: getattr(self, attr).detach().to(dev) for name, attr, _ in self.GROUPS}, optimizer_cls,
+                     {g["name"]: g["lr"] for g in self.optimizer.param_groups})
+        other.percent_dense, other.isotropic = self.percent_dense, self.isotropic
+        for k in ("xyz_gradient_accum", "denom", "max_radii2D"):
+            setattr(other, k, getattr(self, k).detach().clone().to(dev))
+        for mine, theirs in zip(self.optimizer.param_groups, other.optimizer.param_groups):
+            st = self.optimizer.state.get(mine["params"][0], None)
+            if st is not None and "exp_avg" in st:
+                other.optimizer.state[theirs["params"][0]] = {
+                    "step": torch.tensor(float(st["step"]), dtype=torch.float32),
+                    "exp_avg": st["exp_avg"].detach().clone().to(dev), "exp_avg_sq": st["exp_avg_sq"].detach().clone().to(dev)}
+        return other
 
     get_xyz = property(lambda self: self._xyz)
     get_scaling = property(lambda self: self.scaling_activation(self._scaling))
@@ -132,7 +203,35 @@ class EagerGaussians:
             st = self.optimizer.state.get(grp["params"][0], None)
             if st is not None and "exp_avg" in st:
                 d["m:" + grp["name"]], d["v:" + grp["name"]] = st["exp_avg"].cpu(), st["exp_avg_sq"].cpu()
+                d["step:" + grp["name"]] = torch.tensor(float(st["step"]))
         return d
+
+    # scene/gaussian_model.py:369-376
+    def reset_opacity(self, apply_mask=None):
+        if apply_mask is None:
+            opacities_new = inverse_sigmoid(torch.min(self.get_opacity, torch.ones_like(self.get_opacity) * 0.01))
+        else:
+            opacities_new = self._opacity.clone()
+            opacities_new[apply_mask] = inverse_sigmoid(torch.min(self.get_opacity[apply_mask],
+                                                                  torch.ones_like(self.get_opacity[apply_mask]) * 0.01))
+        optimizable_tensors = self.replace_tensor_to_optimizer(opacities_new, "opacity")
+        self._opacity = optimizable_tensors["opacity"]
+
+    # :456-471
+    def replace_tensor_to_optimizer(self, tensor, name):
+        optimizable_tensors = {}
+        for group in self.optimizer.param_groups:
+            if group["name"] in SKIP:
+                continue
+            if group["name"] == name:
+                stored_state = self.optimizer.state.get(group["params"][0], None)
+                stored_state["exp_avg"] = torch.zeros_like(tensor)
+                stored_state["exp_avg_sq"] = torch.zeros_like(tensor)
+                del self.optimizer.state[group["params"][0]]
+                group["params"][0] = nn.Parameter(tensor.requires_grad_(True))
+                self.optimizer.state[group["params"][0]] = stored_state
+                optimizable_tensors[group["name"]] = group["params"][0]
+        return optimizable_tensors
 
     # scene/gaussian_model.py:494-514
     def prune_points(self, mask):
