@@ -33,15 +33,15 @@ constexpr int DF_PAD = 192;
 constexpr int DF_DW_TILE = 64;             // point granularity of the weight-gradient splits
 
 // packed parameter buffer (floats): forward stream, backward stream, biases
-constexpr int64_t DF_F_SZ0 = (int64_t)DF_INK * DF_W;                  // 20480
+constexpr int64_t DF_F_SZ0 = (int64_t)DF_INK * DF_W;                  // 24576
 constexpr int64_t DF_F_SZ = (int64_t)DF_W * DF_W;                     // 65536
 constexpr int64_t DF_F_HEAD_SZ = (int64_t)DF_W * DF_HEAD;             // 16384
 // forward stream, in the order it is used: L0 | L1 L2 L3 L4 | L5 (encoding rows) | L5 (hidden rows) | L6 | L7 | heads
-constexpr int64_t DF_F_TOTAL = 2 * DF_F_SZ0 + 7 * DF_F_SZ + DF_F_HEAD_SZ;   // 516096
+constexpr int64_t DF_F_TOTAL = 2 * DF_F_SZ0 + 7 * DF_F_SZ + DF_F_HEAD_SZ;   // 524288
 constexpr int64_t DF_B_BASE = DF_F_TOTAL;
 constexpr int64_t DF_B_TOTAL = DF_F_HEAD_SZ + 7 * DF_F_SZ;            // 475136
-constexpr int64_t DF_BIAS_BASE = DF_B_BASE + DF_B_TOTAL;              // 991232
-constexpr int64_t DF_PACKED_FLOATS = DF_BIAS_BASE + DF_D * DF_W + DF_HEAD;   // 993344
+constexpr int64_t DF_BIAS_BASE = DF_B_BASE + DF_B_TOTAL;              // 999424
+constexpr int64_t DF_PACKED_FLOATS = DF_BIAS_BASE + DF_D * DF_W + DF_HEAD;   // 1001536
 
 // bf16 plane copy of the two weight streams (after the fp32 floats): every fp32 weight as hi + mid + lo bf16
 // (24 mantissa bits), per segment [plane][k/8][n][8]: the operand layout of v_mfma_f32_32x32x16_bf16
@@ -70,7 +70,21 @@ struct PackArgs {
     float* out;
     int in;                                // encoded inputs (<= DF_INK)
     uint32_t* flag;                        // range flag of the fp16 stream, cleared here (k_deform_pack_h sets it)
+    float* bmax;                           // largest |weight| of every 256 elements of the two streams (k_deform_pack_h's scales)
 };
+
+// the largest of a 256-thread workgroup's values (a NaN is dropped: k_deform_pack_h flags it by itself).  Every thread of
+// the workgroup calls it; the barrier in front keeps a second call in one kernel from overwriting what the first still reads.
+__device__ __forceinline__ float block_max_256(float m)
+{
+    __shared__ float wave_max[4];
+    __syncthreads();
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = m;
+    __syncthreads();
+    return fmaxf(fmaxf(wave_max[0], wave_max[1]), fmaxf(wave_max[2], wave_max[3]));
+}
 
 // head column hc -> (weight row pointer, bias): columns 0..47 are d_sh[coefficient c][channel ch] = c*3+ch
 __device__ __forceinline__ const float* head_row(const gft_deform_params& p, int hc, float& bias)
@@ -93,7 +107,8 @@ __device__ __forceinline__ const float* head_row(const gft_deform_params& p, int
 __global__ __launch_bounds__(256) void k_deform_pack(PackArgs a)
 {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= DF_PACKED_FLOATS) return;
+    static_assert(DF_BIAS_BASE % 256 == 0, "whole workgroups of weights, then the biases");
+    if (e >= DF_PACKED_FLOATS) return;     // (in the last workgroup, which holds biases only)
     if (e == 0) a.flag[0] = 0u;
     float v = 0.f;
     if (e < DF_F_TOTAL) {
@@ -139,6 +154,10 @@ __global__ __launch_bounds__(256) void k_deform_pack(PackArgs a)
         else (void)head_row(a.p, r - DF_D * DF_W, v);
     }
     a.out[e] = v;
+    if (e < DF_BIAS_BASE) {                // (workgroup-uniform)
+        const float m = block_max_256(fabsf(v));
+        if (threadIdx.x == 0) a.bmax[blockIdx.x] = m;
+    }
 }
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -358,9 +377,17 @@ __device__ __forceinline__ void store_split4(char* plane0, size_t plane_bytes, s
 constexpr int64_t DF_H_FLOATS = DF_BF_ELEMS;                   // both streams (round 6: the backward walk too): 2 planes x 2 bytes per weight
 constexpr int64_t DF_FLAG_FLOATS = 4;                          // behind it: word 0 != 0 = a weight is outside the fp16 planes' range
 constexpr int64_t DF_FLAG_OFF = DF_PACKED_FLOATS + DF_BF_FLOATS + DF_H_FLOATS;
+// ... then, per segment, 1 / (the power of two its fp16 planes hold the weights times), and the maxima k_deform_pack leaves
+constexpr int64_t DF_WINV_OFF = DF_FLAG_OFF + DF_FLAG_FLOATS;
+constexpr int64_t DF_WINV_FLOATS = 20;                         // DF_NSEG, padded
+constexpr int64_t DF_BMAX_OFF = DF_WINV_OFF + DF_WINV_FLOATS;
+constexpr int64_t DF_BMAX_FLOATS = DF_BF_ELEMS / 256;
+constexpr int64_t DF_TAIL_FLOATS = DF_FLAG_FLOATS + DF_WINV_FLOATS + DF_BMAX_FLOATS;
+static_assert(DF_NSEG <= DF_WINV_FLOATS && DF_BF_ELEMS % 256 == 0, "a scale per segment, a maximum per workgroup of k_deform_pack");
 constexpr float DF_H_MAX = 65504.f;                            // largest fp16
 
-// The fp16 planes hold |weight| < 64 and |activation| < 4094 (fp16's 65504 over the plane scales).  The reference computes
+// The fp16 planes hold |activation| < 4094 and |weight| < 65504 over the segment's weight scale (h_wscale: |weight| < 64
+// where that is 2^10; a segment that gets a larger power has no weight above 2^-10 and cannot overflow).  The reference computes
 // in fp32, so a network outside that range must still come out right: the pack kernel flags such weights in the packed
 // buffer, the fp16 walk tracks the largest scaled activation it splits and, when one does not fit, writes its call's
 // number into this table; gft_deform_forward launches the bf16 walk (fp32 range) right behind it with that number, and its
@@ -540,7 +567,8 @@ __global__ __launch_bounds__(64 * DF_FWD_WAVES) void k_deform_fwd_bf(FwdArgs a)
 // because a bf16 carries 8 mantissa bits.  An fp16 carries 11: x = hi + lo with hi = fp16(x), lo = fp16(x - hi) holds 22
 // bits, and a product is hi*hi + hi*lo + lo*hi -- THREE v_mfma_f32_32x32x16_f16 into one fp32 accumulator (the dropped
 // lo*lo is below 2^-22 of the product).  fp16 has 5 exponent bits, so both operands are moved into its range first:
-// weights are stored times 2^10, activations times 2^4, and the accumulator is scaled by 2^-14 once per tile.  With that
+// weights are stored times 2^10 (times a larger power of two where a whole segment's weights are small: h_wscale),
+// activations times 2^4, and the accumulator is scaled back once per tile.  With that
 // a weight of magnitude 1e-4 .. 64 and an activation of 8e-3 .. 4094 have a NORMAL lo part (the full 22 bits); smaller
 // ones have a subnormal lo, which still resolves 6e-8 of the scaled value (4e-9 of an activation, 6e-11 of a weight:
 // absolute errors far below the fp32 rounding of the sums they enter) -- the matrix pipe honours fp16 subnormals
@@ -555,7 +583,7 @@ __global__ __launch_bounds__(64 * DF_FWD_WAVES) void k_deform_fwd_bf(FwdArgs a)
 #endif
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-constexpr float DF_H_WSCALE = 1024.0f, DF_H_ASCALE = 16.0f, DF_H_OUT = 1.0f / (1024.0f * 16.0f);
+constexpr float DF_H_WSCALE = 1024.0f, DF_H_ASCALE = 16.0f;      // (DF_H_WSCALE: unless the segment's weights are small, h_wscale)
 constexpr size_t DF_FWD_H_LDS = 2 * DF_BF_ACT_PLANE + 2 * DF_BF_ENC_PLANE + (size_t)DF_BIAS_FLOATS * 4;   // 99584
 constexpr size_t DF_FWD_H_SAVE_LDS = 2 * DF_BF_ACT_PLANE + (size_t)DF_BIAS_FLOATS * 4;                    // 72960: two per CU
 constexpr int DF_FWD_H_SAVE_WAVES = 4;
@@ -571,18 +599,39 @@ __device__ __forceinline__ uint32_t cvt_pk_f16(float a, float b)
 __device__ __forceinline__ float f16_lo(uint32_t u) { f16x2_t h; __builtin_memcpy(&h, &u, 4); return (float)h.x; }
 __device__ __forceinline__ float f16_hi(uint32_t u) { f16x2_t h; __builtin_memcpy(&h, &u, 4); return (float)h.y; }
 
-// fp32 packed streams ([k/4][n][4] per segment) -> fp16 planes ([plane][k/8][n][8] per segment)
-__global__ __launch_bounds__(256) void k_deform_pack_h(const float* __restrict__ packed, _Float16* __restrict__ out, uint32_t* __restrict__ flag)
+// The power of two the fp16 planes of a segment hold its weights times, from the segment's largest |weight| m.  2^10
+// wherever m >= 2^-10: a typical weight is then within fp16's normal range with a normal lo part, and what the planes lose
+// of a smaller one (half a subnormal spacing, 2^-25) is below 2^-25 of the segment's largest.  Below that -- the reference
+// starts its heads at N(0, 1e-5), where times 2^10 most lo parts are subnormal and a weight keeps 17 bits, not 22 -- the
+// largest goes to [2^13, 2^14).  A power of two: the scaling is exact and the walks' epilogues undo it exactly.
+__device__ __forceinline__ float h_wscale(float m)
+{
+    if (!(m < 0x1p-10f) || m == 0.f) return DF_H_WSCALE;           // (inf too; a NaN never gets here: block_max_256)
+    const int k = 14 - __builtin_amdgcn_frexp_expf(m);             // m = f 2^e, f in [0.5, 1)
+    return __uint_as_float((uint32_t)(127 + (k > 100 ? 100 : k)) << 23);
+}
+
+// fp32 packed streams ([k/4][n][4] per segment) -> fp16 planes ([plane][k/8][n][8] per segment).  The two segments of
+// layer 5 (encoding rows, hidden rows) add up in one accumulator and share a scale.
+__global__ __launch_bounds__(256) void k_deform_pack_h(const float* __restrict__ packed, _Float16* __restrict__ out, uint32_t* __restrict__ flag,
+                                                       const float* __restrict__ bmax, float* __restrict__ winv)
 {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= DF_BF_ELEMS) return;
+    static_assert(DF_BF_ELEMS % 256 == 0, "whole workgroups");
     int sgi = 0;
     for (int q = 1; q < DF_NSEG; q++)
         if (e >= df_seg(q).off) sgi = q;
-    const DfSeg sg = df_seg(sgi);
+    const DfSeg sg = df_seg(sgi);                       // (workgroup-uniform: every segment starts at a multiple of 256)
+    const bool l5 = sgi == 5 || sgi == 6;
+    const int b0 = (int)((l5 ? df_seg(5).off : sg.off) / 256);
+    const int nb = l5 ? (int)((DF_F_SZ0 + DF_F_SZ) / 256) : sg.K * sg.ncol / 256;
+    float m = 0.f;
+    for (int q = threadIdx.x; q < nb; q += 256) m = fmaxf(m, bmax[b0 + q]);
+    const float ws = h_wscale(block_max_256(m));
+    if (e == sg.off) winv[sgi] = 1.0f / ws;
     const int64_t r = e - sg.off;
     const int kq = (int)(r / (sg.ncol * 4)), n = (int)((r >> 2) % sg.ncol), k = 4 * kq + (int)(r & 3);
-    const float x = packed[e] * DF_H_WSCALE;
+    const float x = packed[e] * ws;
     if (!(fabsf(x) <= DF_H_MAX)) flag[0] = 1u;          // (NaN too)
     const _Float16 hi = (_Float16)x;
     const _Float16 lo = (_Float16)(x - (float)hi);
@@ -702,10 +751,12 @@ __device__ __forceinline__ void stream_gemm_h(f32x16 (&acc)[NR][NC], const char*
     }
 }
 
-// sin and cos of a moderate argument (the encoding's 2^f x with x in [0, 1]: below 2^15 here, beyond that the library
-// routine): three-constant Cody-Waite reduction by pi/2 with fused multiply-adds, then the Cephes single-precision
-// polynomials on [-pi/4, pi/4] -- about 1 ulp, a third of the instructions of the library's sincosf, which also carries
-// the large-argument reduction.  The encoding phase was a tenth of the kernel.
+// sin and cos of a moderate argument of either sign, |a| < 2^15 (the encoding's 2^f x: world coordinates up to 64 at the
+// highest octave, a time below 1 at up to 16 octaves; beyond that, NaN included, the library routine): three-constant
+// Cody-Waite reduction by pi/2 with fused multiply-adds, then the Cephes single-precision polynomials on [-pi/4, pi/4] --
+// about 1 ulp, a third of the instructions of the library's sincosf, which also carries the large-argument reduction.  The
+// quadrant q = rint(2 a / pi) is negative for a negative argument; its two low bits in two's complement are q mod 4, which
+// is all the selects below look at.  The encoding phase was a tenth of the kernel.
 __device__ __forceinline__ void sincos_enc(float a, float& sn, float& cs)
 {
     if (!(fabsf(a) < 32768.f)) {
@@ -941,6 +992,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
         // (the accumulators start at zero and the bias is added in the epilogue: started AT the scaled bias the walk took
         // 0.45 ms longer and its error against float64 grew five-fold -- measured, profiles/README)
         zero_acc(acc);
+        // what turns this layer's accumulator into the pre-activation: 1 / (its segment's weight scale * 2^4)
+        const float out_l = a.packed[DF_WINV_OFF + (l < 6 ? l : l + 1)] * (1.0f / DF_H_ASCALE);
         if (l == 0) {
             const WSegH nx = wseg_h(1, n0 + li, hh);
             stream_gemm_h<2, NC, DF_W>(acc, e_lane, E_ROW * 2, E_PLANE, DF_INK / 16, rw, seg, &nx, wcur, wnx1, wnx2);
@@ -1001,9 +1054,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
                         *reinterpret_cast<uint2*>(st + lds_off) = ph;
                         continue;
                     }
-                    // activation = max(acc 2^-14 + bias, 0): packed fused multiply-adds, two values each
-                    const f32x2_t a01 = __builtin_elementwise_fma(f32x2_t{acc[rt][ct][4 * g], acc[rt][ct][4 * g + 1]}, f32x2_t{DF_H_OUT, DF_H_OUT}, bq[g][0]);
-                    const f32x2_t a23 = __builtin_elementwise_fma(f32x2_t{acc[rt][ct][4 * g + 2], acc[rt][ct][4 * g + 3]}, f32x2_t{DF_H_OUT, DF_H_OUT}, bq[g][1]);
+                    // activation = max(acc / (weight scale * 2^4) + bias, 0): packed fused multiply-adds, two values each
+                    const f32x2_t a01 = __builtin_elementwise_fma(f32x2_t{acc[rt][ct][4 * g], acc[rt][ct][4 * g + 1]}, f32x2_t{out_l, out_l}, bq[g][0]);
+                    const f32x2_t a23 = __builtin_elementwise_fma(f32x2_t{acc[rt][ct][4 * g + 2], acc[rt][ct][4 * g + 3]}, f32x2_t{out_l, out_l}, bq[g][1]);
                     const float4 v = make_float4(fmaxf(a01.x, 0.f), fmaxf(a01.y, 0.f), fmaxf(a23.x, 0.f), fmaxf(a23.y, 0.f));
                     const f32x2_t s01 = f32x2_t{v.x, v.y} * DF_H_ASCALE, s23 = f32x2_t{v.z, v.w} * DF_H_ASCALE;
                     top = fmaxf(fmaxf(top, fmaxf(s01.x, s01.y)), fmaxf(s23.x, s23.y));
@@ -1043,13 +1096,14 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
         stream_gemm_h<1, 1, DF_HEAD>(hacc, hP + (size_t)(r0 + li) * DF_BH * 2 + 16 * hh, DF_BH * 2, DF_BF_ACT_PLANE, DF_W / 16,
                                      rw, hs, nullptr, hw, hw1, hw2);
         const int64_t p = p0 + r0 + li;
+        const float out_h = a.packed[DF_WINV_OFF + 9] * (1.0f / DF_H_ASCALE);
         if (p < a.n && !(DF_ABL & 16)) {
 #pragma unroll
             for (int g = 0; g < 4; g++) {
                 const int col = 32 * ct + acc_col4(g, hh);
                 const float4 bq = *reinterpret_cast<const float4*>(bL + DF_D * DF_W + col);
-                const float4 v = make_float4(fmaf(hacc[0][0][4 * g], DF_H_OUT, bq.x), fmaf(hacc[0][0][4 * g + 1], DF_H_OUT, bq.y),
-                                             fmaf(hacc[0][0][4 * g + 2], DF_H_OUT, bq.z), fmaf(hacc[0][0][4 * g + 3], DF_H_OUT, bq.w));
+                const float4 v = make_float4(fmaf(hacc[0][0][4 * g], out_h, bq.x), fmaf(hacc[0][0][4 * g + 1], out_h, bq.y),
+                                             fmaf(hacc[0][0][4 * g + 2], out_h, bq.z), fmaf(hacc[0][0][4 * g + 3], out_h, bq.w));
                 if (col < 48) {
                     *reinterpret_cast<float4*>(a.d_sh + p * 48 + col) = v;
                 } else if (col == 48) {
@@ -1181,18 +1235,25 @@ __global__ __launch_bounds__(64 * DF_BWD_WAVES) void k_deform_bwd_bf(BwdArgs a)
 // ---------------------------------------------------------------------------------------------
 // Backward walk on TWO fp16 planes (round 6): k_deform_bwd_bf's walk with k_deform_fwd_h's arithmetic -- three
 // v_mfma_f32_32x32x16_f16 per product instead of six bf16 ones, two thirds of the operand bytes, 68 KB of LDS (two
-// workgroups per CU; the three bf16 planes allowed one).  Weights: the fp16 planes of the backward stream (times 2^10; a
+// workgroups per CU; the three bf16 planes allowed one).  Weights: the fp16 planes of the backward stream (times their
+// segment's power of two, 2^10 unless the segment's weights are small: h_wscale; a
 // weight >= 64 sets the pack kernel's flag, this kernel returns and k_deform_bwd_bf behind it does the work).  Gradients
 // have no fixed range (1e-12 early in a run, 1e+2 under a large loss scale), so every point's row of the tile carries
 // its own power-of-two scale: the largest magnitude of the row goes to [2^13, 2^14) before the split, and the
-// accumulator of that point -- a point is a lane of the MFMA's output -- is multiplied by the inverse (times 2^-10 for
+// accumulator of that point -- a point is a lane of the MFMA's output -- is multiplied by the inverse (times 2^-10 or what the segment has for
 // the weights) when it is read.  Powers of two: the scaling itself is exact; entries down to 2^-27 of their row's largest
 // keep a normal hi part and 22 bits, smaller ones fade out against a sum (the next layer's gradient, the weight
 // gradients) that the large entries of the same row dominate.  Measured against float64: tests/test_deform.py.
 // ---------------------------------------------------------------------------------------------
 constexpr size_t DF_BWD_H_LDS = 2 * DF_BF_ACT_PLANE + (size_t)(DF_BWD_WAVES + 1) * 64 * 4;   // planes + the rows' maxima per wave + the head tile's
 
-// m = f 2^e with f in [0.5, 1): e (0 for 0, inf, NaN), kept where 2^(14 - e) and 2^(e - 24) are normal floats
+// m = f 2^e with f in [0.5, 1): e (0 for 0, inf, NaN), kept at -100 or more: 2^(14 - e) and 2^(e - 14) are normal floats.
+// The walk multiplies 2^(e - 14) by its segment's inverse weight scale 2^-k (h_wscale: k = 10, or 14 - e_w up to 100 where
+// the segment's largest weight is below 2^e_w <= 2^-10).  A product of two powers of two is exact down to 2^-149.  With
+// k = 10 it is 2^-124 or more, as before; with a small segment it is 2^(e + e_w - 28) and leaves the normal range only where
+// e + e_w < -98, i.e. where the row's largest gradient times the segment's largest weight is below 2^-98.  The gradient
+// that is scaled by it, a sum of 256 such products, is then below 2^-90 (8e-28) itself; what comes out subnormal or zero there
+// is what fp32 holds of it.
 __device__ __forceinline__ int grad_exp(float m)
 {
     const int e = __builtin_amdgcn_frexp_expf(m);
@@ -1263,9 +1324,10 @@ __global__ __launch_bounds__(64 * DF_BWD_WAVES) __attribute__((amdgpu_waves_per_
     const char* g_lane = gP + (size_t)li * DF_BH * 2 + 16 * hh;
     f32x16 acc[2][NC];
     uint32_t sg[2][NC];
-    float inv[2];                      // what turns the accumulator of this lane's two points into the gradient: 1 / (row scale * 2^10)
+    float inv[2];                      // what turns the accumulator of this lane's two points into the gradient: 1 / (row scale * weight scale)
+    const float* winv = a.packed + DF_WINV_OFF;      // per segment, 1 / its weight scale (2^-10 unless its weights are small)
 #pragma unroll
-    for (int rt = 0; rt < 2; rt++) inv[rt] = pow2_f(grad_exp(hm[32 * rt + li]) - 24);
+    for (int rt = 0; rt < 2; rt++) inv[rt] = pow2_f(grad_exp(hm[32 * rt + li]) - 14) * winv[10];
     auto load_signs = [&](int l) {
 #pragma unroll
         for (int rt = 0; rt < 2; rt++)
@@ -1312,7 +1374,7 @@ __global__ __launch_bounds__(64 * DF_BWD_WAVES) __attribute__((amdgpu_waves_per_
                 for (int w = 1; w < DF_BWD_WAVES; w++) m = fmaxf(m, pm[w * 64 + 32 * rt + li]);
                 const int e = grad_exp(m);
                 sc[rt] = pow2_f(14 - e);
-                inv[rt] = pow2_f(e - 24);
+                inv[rt] = pow2_f(e - 14) * winv[11 + (7 - l)];      // (the product with W_l below)
                 if (wave == 0 && hh == 0) a.rowmax[(int64_t)l * a.n_pad + p0 + 32 * rt + li] = m;
             }
         }
@@ -2068,7 +2130,7 @@ static int arch_inputs(int xm, int tm)
 
 extern "C" int gft_deform_inputs(int xyz_multires, int t_multires) { return arch_inputs(xyz_multires, t_multires); }
 
-extern "C" size_t gft_deform_packed_bytes(void) { return (size_t)(DF_PACKED_FLOATS + DF_BF_FLOATS + DF_H_FLOATS + DF_FLAG_FLOATS) * sizeof(float); }
+extern "C" size_t gft_deform_packed_bytes(void) { return (size_t)(DF_PACKED_FLOATS + DF_BF_FLOATS + DF_H_FLOATS + DF_TAIL_FLOATS) * sizeof(float); }
 
 extern "C" size_t gft_deform_saved_bytes(int64_t n)
 {
@@ -2110,6 +2172,7 @@ extern "C" int gft_deform_pack(void* hip_stream, int xyz_multires, int t_multire
     a.out = (float*)packed;
     a.in = in;
     a.flag = reinterpret_cast<uint32_t*>((float*)packed + DF_FLAG_OFF);
+    a.bmax = (float*)packed + DF_BMAX_OFF;
     hipLaunchKernelGGL(k_deform_pack, dim3((unsigned)((DF_PACKED_FLOATS + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, a);
     GFT_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_deform_pack_bf, dim3((unsigned)((DF_BF_ELEMS + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream,
@@ -2117,7 +2180,8 @@ extern "C" int gft_deform_pack(void* hip_stream, int xyz_multires, int t_multire
     GFT_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_deform_pack_h, dim3((unsigned)((DF_BF_ELEMS + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream,
                        (const float*)packed, reinterpret_cast<_Float16*>((float*)packed + DF_PACKED_FLOATS + DF_BF_FLOATS),
-                       reinterpret_cast<uint32_t*>((float*)packed + DF_FLAG_OFF));
+                       reinterpret_cast<uint32_t*>((float*)packed + DF_FLAG_OFF), (const float*)packed + DF_BMAX_OFF,
+                       (float*)packed + DF_WINV_OFF);
     GFT_CHECK_HIP(hipGetLastError());
     return 0;
 }

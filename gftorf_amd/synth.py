@@ -192,15 +192,16 @@ def deform_param_shapes(t_multires=10, xyz_multires=10, D=8, W=256, num_shs=16):
     return s
 
 
-def random_deform_params(seed, head_std=0.05, t_multires=10):
+def random_deform_params(seed, head_std=0.05, t_multires=10, bias_std=0.02):
     """Seeded parameters of a usable magnitude (Xavier-like trunk; heads larger than the reference's 1e-5 initialisation so
     that outputs and gradients are well away from zero): numpy arrays under the reference's ``state_dict`` names, torch's
-    ``[out, in]`` layout."""
+    ``[out, in]`` layout.  ``head_std=1e-5, bias_std=0.0`` is the distribution the reference starts from
+    (utils/time_utils.py:85-101); a bias still takes its draws from the generator, so the weights do not depend on it."""
     rng = np.random.default_rng(seed)
     p = {}
     for name, shape in deform_param_shapes(t_multires).items():
         if name.endswith(".bias"):
-            p[name] = rng.normal(0.0, 0.02, shape).astype(np.float32)
+            p[name] = rng.normal(0.0, bias_std, shape).astype(np.float32)
         elif name.startswith("linear."):
             p[name] = rng.normal(0.0, np.sqrt(2.0 / (shape[0] + shape[1])), shape).astype(np.float32)
         else:

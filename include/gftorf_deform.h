@@ -20,13 +20,23 @@
  * The forward walk goes one step further: its operands are split into two fp16 numbers, x = hi + lo (hi = fp16(x),
  * lo = fp16(x - hi): 22 mantissa bits), and a product is three `v_mfma_f32_32x32x16_f16` terms (hi*hi, hi*lo, lo*hi;
  * lo*lo is below 2^-22 of the product and dropped) into one fp32 accumulator.  fp16 has five exponent bits, so weights
- * are stored times 2^10 and activations times 2^4 (the accumulator is scaled back once per tile): a weight of 1e-4 .. 64
- * and an activation of 8e-3 .. 4094 keep all 22 bits, smaller ones have a subnormal lo that still resolves 4e-9 of an
- * activation (the matrix pipe honours fp16 subnormals).  Measured against float64 the outputs are as close as the
- * six-term bf16 walk's (1.7e-7 of the max-norm at 300 k points) at 0.75 x its time.  A weight, activation or input beyond
- * that range does not fit the planes: the pack kernel flags such weights, the walk notices such values, and the bf16 walk
- * (fp32 range), launched behind the fp16 one in every call, then redoes the call -- its workgroups return at once
- * otherwise.  GFT_DEFORM_FP16X2=0 runs the bf16 walk alone.
+ * are stored times a power of two and activations times 2^4 (the accumulator is scaled back once per tile, exactly).  The
+ * weights' power is chosen by gft_deform_pack per packed segment (a layer's matrix in one direction; the heads together)
+ * from the segment's largest |weight| m: 2^10 where m >= 2^-10 -- every network whose layers hold a weight of 1e-3 or more,
+ * the benchmark's among them -- and otherwise the power that puts m into [2^13, 2^14).  So a weight within 2^-11 of its
+ * segment's largest (at 2^10: a weight of 1e-4 .. 64) and an activation of 8e-3 .. 4094 keep all 22 bits; smaller ones
+ * have a subnormal lo that still resolves 4e-9 of an activation and 2^-25 of what the segment's largest weight is stored
+ * as (the matrix pipe honours fp16 subnormals).  The reference starts its heads at N(0, 1e-5): under a fixed 2^10 those
+ * would keep 17 bits (measured with the power held at 2^10: outputs at 2.8e-6 of the max-norm against float64 for such
+ * heads, 2.7e-5 for heads of 1e-6, 1.9e-4 for 1e-7).  With the segment's own power the device's outputs are at
+ * 6.6e-7 .. 8.0e-7 of the max-norm for heads of 0.05, 1e-3, 1e-5, 1e-6 and 1e-7 alike (1500 world-space points; numpy in
+ * fp32: 7.1e-7 .. 7.7e-7), the worst parameter gradient at 1.5e-6 .. 1.7e-6 (numpy in fp32: 1.3e-6 .. 1.8e-6):
+ * tests/test_deform_domain.py::test_head_magnitude_sweep, table in DESIGN.md section 6.  At 300 k points with heads of 0.05
+ * the outputs are as close as the six-term bf16 walk's (1.7e-7 of the max-norm) at 0.75 x its time.  A weight of 64 or more where the power is 2^10, an activation or an encoded input beyond 4094 (NaN included) does
+ * not fit the planes: the pack kernel flags such weights, the walk notices such values, and the bf16 walk (fp32 range),
+ * launched behind the fp16 one in every call, then redoes the call -- its workgroups return at once otherwise.  Inputs are
+ * world coordinates of either sign: the encoding reduces |2^f x| < 2^15 itself and leaves larger arguments to the
+ * library's sincosf.  GFT_DEFORM_FP16X2=0 runs the bf16 walk alone.
  * Since round 6 the backward's two heavy kernels multiply on two fp16 planes as well (GFT_DEFORM_BWD_FP16=0: three bf16
  * planes).  Gradients have no fixed range, so they carry power-of-two scales chosen from the data: the backward walk
  * scales every point's gradient row by its own (the accumulator of a point is a lane of the MFMA's output), the

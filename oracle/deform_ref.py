@@ -75,6 +75,70 @@ def random_params(seed, head_std=0.05, t_multires=T_MULTIRES):
     return p
 
 
+def reference_init_params(seed, t_multires=T_MULTIRES, head_std=1e-5):
+    """Seeded parameters drawn as the reference's ``initialize_weights`` draws them (time_utils.py:85-101): Xavier-normal
+    trunk, every bias zero, heads N(0, 1e-5).  ``head_std`` moves the heads alone."""
+    from gftorf_amd import synth
+    p = synth.random_deform_params(seed, head_std=head_std, t_multires=t_multires, bias_std=0.0)
+    assert {k: v.shape for k, v in p.items()} == param_shapes(t_multires)
+    return p
+
+
+# Named input sets of the domain the reference queries the network on: world coordinates, signed and as large as the scene
+# (scene/gaussian_model.py:170-174), times fid / (N - 1) including 0 and 1 exactly and a little beyond the last view
+# (train.py:169-176).  x 2^f is exact in float32 and float64 alike, so forward(..., dtype=np.float64) on these float32
+# values is the reference of every row.
+DOMAIN_SETS = ("signed_unit", "room", "far", "reduction_switch", "time_switch", "plane_edge_below", "plane_edge_above",
+               "guard_edge_below", "guard_edge_above")
+# The fp16 walk takes an encoded input v while |16 v| <= 65504, i.e. |x| <= 4094.  plane_edge_* sit where 16 |x| passes
+# 4094 (|x| = 255.875: both sides are still inside the planes), guard_edge_* at the guard itself: 4094 is the last value
+# the walk keeps, 16 * 4096 = 65536 is beyond the largest fp16 and the call has to leave for the fp32-range walk.
+EDITED = {"plane_edge_above": 300.0, "guard_edge_above": 4096.0}
+
+
+def domain_inputs(name, n, seed):
+    """(x[n,3], t[n,1], shared_t) of the input set ``name``, float32; the rows with exact values come first."""
+    rng = np.random.default_rng(seed)
+    sign = lambda shape: np.where(rng.random(shape) < 0.5, -1.0, 1.0)
+    t = rng.uniform(0.0, 1.0, (n, 1))
+    shared_t = False
+    if name in ("signed_unit", "time_switch"):
+        x = rng.uniform(-1.0, 1.0, (n, 3))
+    elif name in ("room", "plane_edge_above", "guard_edge_above"):
+        x = rng.uniform(-8.0, 8.0, (n, 3))
+    elif name == "far":
+        x = rng.uniform(-60.0, 60.0, (n, 3))
+        t[:] = rng.uniform(0.0, 1.0)
+        shared_t = True
+    elif name == "reduction_switch":
+        # 2^9 * 64 = 2^8 * 128 = 32768: where the encoding goes from its own reduction to the library's
+        centre = np.where(rng.random((n, 3)) < 0.5, 64.0, 128.0)
+        x = sign((n, 3)) * (centre + rng.uniform(-0.1, 0.1, (n, 3)))
+    elif name == "plane_edge_below":
+        x = sign((n, 3)) * rng.uniform(255.0, 255.87, (n, 3))
+    elif name == "guard_edge_below":
+        x = sign((n, 3)) * rng.uniform(4090.0, 4094.0, (n, 3))
+    else:
+        raise KeyError(name)
+    x, t = x.astype(np.float32), t.astype(np.float32)
+    if name in ("signed_unit", "time_switch") and n >= 4:
+        x[0], x[1], x[2, 1], x[3, 2] = 0.0, -0.0, 0.0, -0.0
+    if name == "reduction_switch" and n >= 4:
+        x[0], x[1], x[2], x[3] = 64.0, -64.0, 128.0, (64.0, -128.0, 128.0)
+    if name == "time_switch":
+        # 2^15 t: 0, the last value below the encoding's switch, the switch itself (t_multires = 16), past the last view
+        t[:, 0] = np.resize(np.array([0.0, 1.0 - 2.0 ** -16, 1.0, 1.04], np.float32), n)
+    elif not shared_t and n >= 4:
+        t[0], t[1] = 0.0, 1.0
+        if name != "signed_unit":
+            t[2], t[3] = -0.04, 1.04
+    if name == "guard_edge_below" and n >= 4:
+        x[0], x[1] = 4094.0, -4094.0
+    if name in EDITED:
+        x[n // 2, 1] = EDITED[name]                      # one coordinate of one row; every other value is `room`'s
+    return x, t, shared_t
+
+
 def embed_one(v, multires, dtype):
     """Embedder.embed (time_utils.py:24-53) of v[n, d]."""
     v = np.asarray(v, dtype)

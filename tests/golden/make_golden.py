@@ -16,6 +16,10 @@ files themselves never travel; only the input/output vectors written here do.
                    no-ops for the run), with the seeded parameters of oracle/deform_ref.random_params; only
                    inputs, outputs and gradients (small ones whole, weight gradients as strided samples)
   deform_t6.npz  : the same for the class signature's defaults (t_multires 6, time_utils.py:57)
+  deform_world.npz : the configured network at the reference's own initialisation (the distribution of
+                   time_utils.py:85-101, seeded: oracle/deform_ref.reference_init_params) on world-space inputs: 48 points
+                   mixed from the `room` and `reduction_switch` sets of deform_ref.domain_inputs, times 0 and 1 exactly
+                   and past both ends
 """
 import math
 import os
@@ -53,17 +57,34 @@ def reference_kwargs():
     return kwargs
 
 
-def deform_fixture(kwargs, fname):
+def world_inputs(params):
+    """48 points: 27 of `room` and 27 of `reduction_switch` (the rows with exact coordinates and times first in each), less
+    the six closest to a ReLU edge among the rows without an exact value."""
+    xa, ta, _ = deform_ref.domain_inputs("room", 27, DEFORM_SEED + 2)
+    xb, tb, _ = deform_ref.domain_inputs("reduction_switch", 27, DEFORM_SEED + 3)
+    x, t = np.concatenate([xa, xb]), np.concatenate([ta, tb])
+    margin = deform_ref.relu_margin(params, x, t)
+    margin[:4] = margin[27:31] = np.inf
+    keep = np.sort(np.argsort(-margin)[:48])
+    return x[keep], t[keep]
+
+
+def deform_fixture(kwargs, fname, world=False):
     torch.Tensor.cuda = lambda self, *a, **k: self          # time_utils.py:121,127 on a CPU-only host
     net = DeformNetwork(**kwargs)
     net.isotropic = False
-    params = deform_ref.random_params(DEFORM_SEED, t_multires=net.t_multires)
+    if world:
+        params = deform_ref.reference_init_params(DEFORM_SEED, net.t_multires)
+    else:
+        params = deform_ref.random_params(DEFORM_SEED, t_multires=net.t_multires)
     net.load_state_dict({k: torch.tensor(v) for k, v in params.items()})
     rng = np.random.default_rng(DEFORM_SEED + 1)
     n = 48
     x = rng.random((n, 3)).astype(np.float32)
     t = np.full((n, 1), 0.37, np.float32)
     t[n // 2:] = rng.random((n - n // 2, 1)).astype(np.float32)
+    if world:
+        x, t = world_inputs(params)
     g_dxyz = rng.normal(size=(n, 3)).astype(np.float32)
     g_dsh = rng.normal(size=(n, 16, 3)).astype(np.float32)
     d_xyz, d_rot, d_sh, d_sh_p = net(torch.tensor(x), torch.tensor(t))
@@ -136,6 +157,7 @@ def main():
     assert kw == dict(D=8, W=256, xyz_multires=10, t_multires=10, sh_degree=3), kw
     deform_fixture(kw, "deform.npz")
     deform_fixture({}, "deform_t6.npz")
+    deform_fixture(kw, "deform_world.npz", world=True)
     print("wrote", sorted(os.listdir(HERE)))
 
 
