@@ -15,6 +15,7 @@ from .deform import DeformNetwork, REFERENCE_ARCH, reference_network  # noqa: F4
 from . import densify  # noqa: F401
 from . import loss  # noqa: F401
 from . import flow  # noqa: F401
+from . import reg  # noqa: F401
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "GaussianRasterizerPair", "render_pair", "assemble_inputs", "assemble_parameters", "distCUDA2", "FusedAdam", "clip_grad_norm_",
            "DeformNetwork", "REFERENCE_ARCH", "reference_network", "densify"]

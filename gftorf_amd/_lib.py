@@ -155,6 +155,10 @@ FLOW_EXPORTS = ["gft_flow_loss_blocks", "gft_flow_loss_forward", "gft_flow_loss_
                 "gft_flow_project_backward"]
 # include/gftorf_features.h (the feature blend over a drawn frame; no struct, so the ABI version is unchanged)
 FEATURE_EXPORTS = ["gft_render_features", "gft_render_features_backward"]
+# include/gftorf_reg.h (the per-Gaussian regularisers of the loss; no struct, so the ABI version is unchanged)
+REG_EXPORTS = ["gft_reg_blocks", "gft_reg_result_words", "gft_reg_forward", "gft_reg_backward"]
+REG_PARTIAL_WORDS = 8           # GFT_REG_PARTIAL_WORDS
+REG_MEANS, REG_COUNTS, REG_RECIPS, REG_TOTAL = 0, 4, 6, 10      # GFT_REG_*: words of the result block
 
 
 def load():
@@ -291,6 +295,19 @@ def load():
     lib.gft_render_features.argtypes = _feat_frame + [C.c_void_p] * 3
     lib.gft_render_features_backward.restype = C.c_int
     lib.gft_render_features_backward.argtypes = _feat_frame + [C.c_void_p] * 3
+    # stream, n_dxyz, P, pixels, d_xyz, opacity, motion_mask, opacity_is_raw, scaling, scaling_cols, scaling_is_raw, visible,
+    # visible_is_radii
+    _reg_inputs = ([C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                    C.c_int32, C.c_void_p, C.c_int32])
+    _reg_weights = [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float]
+    lib.gft_reg_blocks.restype = C.c_int64
+    lib.gft_reg_blocks.argtypes = [C.c_int64, C.c_int64, C.c_int64]
+    lib.gft_reg_result_words.restype = C.c_int64
+    lib.gft_reg_result_words.argtypes = []
+    lib.gft_reg_forward.restype = C.c_int
+    lib.gft_reg_forward.argtypes = _reg_inputs + [C.c_void_p] + _reg_weights + [C.c_void_p, C.c_void_p]
+    lib.gft_reg_backward.restype = C.c_int
+    lib.gft_reg_backward.argtypes = _reg_inputs + _reg_weights + [C.c_void_p] * 6
     lib.gft_densify_stats.restype = C.c_int
     lib.gft_densify_stats.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8
     lib.gft_rows_rank_scratch_bytes.restype = C.c_size_t
