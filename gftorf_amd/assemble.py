@@ -36,12 +36,19 @@ def _is_tensor(x):
     return isinstance(x, torch.Tensor)
 
 
+def _aligned(t):
+    return t.data_ptr() % 16 == 0
+
+
 def _f32c(t, dev, name):
     if t.device != dev:
         raise RuntimeError("gftorf_amd.assemble_inputs: %s is on %s, expected %s" % (name, t.device, dev))
     if t.dtype != torch.float32:
         t = t.float()
-    return t.contiguous()
+    t = t.contiguous()
+    # the kernels read and write quaternions and feature rows 16 bytes at a time (include/gftorf_assemble.h): a contiguous view
+    # that starts off such a boundary (a slice of a flat buffer) is copied to storage of its own
+    return t if _aligned(t) else t.clone()
 
 
 def _p(t):
@@ -152,8 +159,8 @@ class _AssembleInputs(torch.autograd.Function):
         # Gaussian read and written again; the kernel then only gathers the dynamic rows for d_sh).  With a region left
         # out its rows must come out zero whatever arrives: the copy stays.
         alias = bool(rs and rd) and _ALIAS_SH_GRADS
-        alias_fc = alias and need[6] and g_shs is not None and g_shs.dtype == torch.float32 and g_shs.is_contiguous()
-        alias_fp = alias and need[7] and g_shs_p is not None and g_shs_p.dtype == torch.float32 and g_shs_p.is_contiguous()
+        alias_fc = alias and need[6] and g_shs is not None and g_shs.dtype == torch.float32 and g_shs.is_contiguous() and _aligned(g_shs)
+        alias_fp = alias and need[7] and g_shs_p is not None and g_shs_p.dtype == torch.float32 and g_shs_p.is_contiguous() and _aligned(g_shs_p)
         g_fc = None if alias_fc else new(need[6], (P, M, 3))
         g_fp = None if alias_fp else new(need[7], (P, M_p, 2))
         nd = ctx.off_rows
@@ -211,14 +218,14 @@ class _AssembleParameters(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, screenspace, opacity_raw, scaling_raw, rotation_raw, f_dc, f_rest, phase_dc, phase_rest, amp_dc, amp_rest,
                 motion_mask, d_xyz, d_rot, d_sh, d_sh_p, render_static, render_dynamic):
-        lib = _lib.load()
-        dev = xyz.device
-        if dev.type != "cuda":
-            raise RuntimeError("gftorf_amd.assemble_parameters runs on a HIP device only (xyz is on %s); there is no CPU path" % (dev,))
-        P = xyz.size(0)
         M, M_p = f_dc.size(1) + f_rest.size(1), phase_dc.size(1) + phase_rest.size(1)
         if f_dc.size(1) != 1 or phase_dc.size(1) != 1 or amp_dc.size(1) != 1 or amp_dc.size(1) + amp_rest.size(1) != M_p:
             raise RuntimeError("assemble_parameters: the dc tensors hold one coefficient, phase and amplitude the same number")
+        dev = xyz.device
+        if dev.type != "cuda":
+            raise RuntimeError("gftorf_amd.assemble_parameters runs on a HIP device only (xyz is on %s); there is no CPU path" % (dev,))
+        lib = _lib.load()
+        P = xyz.size(0)
         names = ("xyz", "screenspace_points", "_opacity", "_scaling", "_rotation", "_features_dc_color", "_features_rest_color",
                  "phase_f_dc", "phase_f_rest", "amp_f_dc", "amp_f_rest")
         src = [_f32c(t, dev, n) for t, n in zip((xyz, screenspace, opacity_raw, scaling_raw, rotation_raw, f_dc, f_rest, phase_dc,

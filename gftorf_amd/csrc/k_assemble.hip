@@ -19,6 +19,8 @@
 // HBM-bound elementwise work: no LDS tiling, no MFMA; 16-byte accesses, one pass.
 #include "gft_internal.h"
 #include "gftorf_assemble.h"
+#include <initializer_list>
+#include <utility>
 
 namespace {
 
@@ -29,7 +31,7 @@ namespace {
 
 __global__ __launch_bounds__(ASM_RANK_ROWS) void k_assemble_rank(int P, const uint8_t* __restrict__ mask,
                                                                  uint32_t* block_sums, uint32_t* ticket,
-                                                                 uint32_t* __restrict__ num_dynamic)
+                                                                 uint32_t* __restrict__ num_dynamic, uint32_t num_offset_rows)
 {
     __shared__ uint32_t s_w[ASM_RANK_ROWS / 64];
     __shared__ uint32_t s_last;
@@ -73,7 +75,8 @@ __global__ __launch_bounds__(ASM_RANK_ROWS) void k_assemble_rank(int P, const ui
         if (tid == ASM_RANK_ROWS - 1) s_carry = carry + woff + x;
         __syncthreads();
     }
-    if (tid == 0) { *num_dynamic = s_carry; *ticket = 0; }
+    // (num_dynamic[1]: the rows of the offset tensors, for the backward -- its rows beyond num_dynamic belong to no Gaussian)
+    if (tid == 0) { num_dynamic[0] = s_carry; num_dynamic[1] = num_offset_rows; *ticket = 0; }
 }
 
 struct RowsArgs {
@@ -273,14 +276,26 @@ __global__ __launch_bounds__(ASM_BLOCK) void k_assemble_wide_bwd_split(size_t to
 struct RowsBwdArgs {
     int P;
     int render_static, render_dynamic;
+    int M, M_p;
     gft_assemble_bwd_io io;
     const uint32_t* dyn_rank;
+    const uint32_t* counts;         // num_dynamic, rows of the offset tensors (k_assemble_rank)
 };
 
 __global__ __launch_bounds__(ASM_BLOCK) void k_assemble_rows_bwd(RowsBwdArgs a)
 {
     const int i = blockIdx.x * ASM_BLOCK + threadIdx.x;
     if (i >= a.P) return;
+    // An offset tensor with more rows than the mask has Trues (a mask rewritten under a captured graph): the rows past the
+    // last dynamic Gaussian reach no output, their gradient is zero -- written here, the gradients are allocated with empty().
+    // (rows <= P: lane i takes row i)
+    if ((uint32_t)i >= a.counts[0] && (uint32_t)i < a.counts[1]) {
+        const size_t r = (size_t)i;
+        if (a.io.g_d_xyz) for (int c = 0; c < 3; c++) a.io.g_d_xyz[3 * r + c] = 0.f;
+        if (a.io.g_d_rot) reinterpret_cast<float4*>(a.io.g_d_rot)[r] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (a.io.g_d_sh) for (int c = 0; c < 3 * a.M; c++) a.io.g_d_sh[r * (size_t)(3 * a.M) + c] = 0.f;
+        if (a.io.g_d_sh_p) for (int c = 0; c < 2 * a.M_p; c++) a.io.g_d_sh_p[r * (size_t)(2 * a.M_p) + c] = 0.f;
+    }
     const uint32_t rank_w = a.dyn_rank[i];
     const bool m = rank_w != ASM_STATIC;
     const bool oob = m && (rank_w & ASM_OOB);   // no row in the offset tensors (k_assemble_rows): zero gradients
@@ -467,6 +482,14 @@ extern "C" size_t gft_assemble_scratch_bytes(int32_t P)
     return p * 4 + ((p + ASM_RANK_ROWS - 1) / ASM_RANK_ROWS) * 4 + 256;
 }
 
+// The kernels above go through these pointers with 16-byte accesses (float4): checked on the host, before any launch.
+static const char* misaligned(std::initializer_list<std::pair<const char*, const void*>> ptrs)
+{
+    for (const auto& p : ptrs)
+        if ((uintptr_t)p.second % 16 != 0) return p.first;
+    return nullptr;
+}
+
 static void assemble_scratch(void* scratch, int32_t P, uint32_t** rank, uint32_t** sums, uint32_t** ticket, uint32_t** ndyn)
 {
     char* b = (char*)scratch;
@@ -502,17 +525,30 @@ extern "C" int gft_assemble_forward(void* hip_stream, int32_t P, int32_t M, int3
         return gft_fail("gft_assemble_forward: the phasor features' parts are incomplete");
     if ((io->d_xyz || io->d_rot || io->d_sh || io->d_sh_p) && (io->num_offset_rows < 0 || io->num_offset_rows > P))
         return gft_fail("gft_assemble_forward: the offset tensors have %lld rows for %d Gaussians", (long long)io->num_offset_rows, P);
+    // k_assemble_rows reads and writes the quaternions as float4; k_assemble_wide<4> (a whole feature tensor whose row is a
+    // multiple of four floats) the feature, offset and output rows.  The split kernels (the features in their parts) and
+    // k_assemble_wide<1> go float by float.
+    const bool color_vec = !color_parts && M > 0 && (M * 3) % 4 == 0, phasor_vec = !phasor_parts && M_p > 0 && (M_p * 2) % 4 == 0;
+    if (const char* bad = misaligned({{"rotation", io->rotation}, {"rotation_raw", io->rotation_raw}, {"d_rot", io->d_rot},
+                                      {"out_rotations", io->out_rotations},
+                                      {"feat_color", color_vec ? io->feat_color : nullptr}, {"d_sh", color_vec ? io->d_sh : nullptr},
+                                      {"out_shs", color_vec ? io->out_shs : nullptr},
+                                      {"feat_phasor", phasor_vec ? io->feat_phasor : nullptr}, {"d_sh_p", phasor_vec ? io->d_sh_p : nullptr},
+                                      {"out_shs_p", phasor_vec ? io->out_shs_p : nullptr}}))
+        return gft_fail("gft_assemble_forward: %s is not 16-byte aligned", bad);
     hipStream_t s = (hipStream_t)hip_stream;
     uint32_t *rank, *sums, *ticket, *ndyn;
     assemble_scratch(io->scratch, P, &rank, &sums, &ticket, &ndyn);
     GFT_CHECK_HIP(gft_zero_async(ticket, 8, s));
     const int nrb = (P + ASM_RANK_ROWS - 1) / ASM_RANK_ROWS;
-    hipLaunchKernelGGL(k_assemble_rank, dim3(nrb), dim3(ASM_RANK_ROWS), 0, s, P, io->motion_mask, sums, ticket, ndyn);
+    const bool any_offset = io->d_xyz || io->d_rot || io->d_sh || io->d_sh_p;
+    hipLaunchKernelGGL(k_assemble_rank, dim3(nrb), dim3(ASM_RANK_ROWS), 0, s, P, io->motion_mask, sums, ticket, ndyn,
+                       any_offset ? (uint32_t)io->num_offset_rows : 0u);
     RowsArgs a;
     a.P = P; a.render_static = render_static; a.render_dynamic = render_dynamic;
     a.io = *io;
     // rows of the offset tensors; with scalar offsets only, every rank is in range
-    if (!io->d_xyz && !io->d_rot && !io->d_sh && !io->d_sh_p) a.io.num_offset_rows = (int64_t)1 << 40;
+    if (!any_offset) a.io.num_offset_rows = (int64_t)1 << 40;
     a.dyn_rank = rank;
     a.block_sums = sums;
     hipLaunchKernelGGL(k_assemble_rows, dim3(nrb), dim3(ASM_RANK_ROWS), 0, s, a);
@@ -551,13 +587,26 @@ extern "C" int gft_assemble_backward(void* hip_stream, int32_t P, int32_t M, int
     if (!io) return gft_fail("gft_assemble_backward: io is NULL");
     if (P == 0) return 0;
     if (!io->scratch || !io->rotation_raw) return gft_fail("gft_assemble_backward: required pointer is NULL");
+    // k_assemble_rows_bwd: the quaternions and their gradients as float4; k_assemble_wide_bwd<4> / k_assemble_wide_gather (the
+    // features' gradient whole, a row a multiple of four floats): g_shs, g_feat_color, g_d_sh.  The split kernel goes float by float.
+    const bool color_vec = !(io->g_feat_dc_color || io->g_feat_rest_color) && M > 0 && (M * 3) % 4 == 0;
+    const bool phasor_vec = !(io->g_phase_dc || io->g_phase_rest || io->g_amp_dc || io->g_amp_rest) && M_p > 0 && (M_p * 2) % 4 == 0;
+    if (const char* bad = misaligned({{"rotation_raw", io->rotation_raw}, {"d_rot", io->d_rot}, {"g_rotations", io->g_rotations},
+                                      {"g_rotation", io->g_rotation}, {"g_rotation_raw", io->g_rotation_raw}, {"g_d_rot", io->g_d_rot},
+                                      {"g_shs", color_vec ? io->g_shs : nullptr}, {"g_feat_color", color_vec ? io->g_feat_color : nullptr},
+                                      {"g_d_sh", color_vec ? io->g_d_sh : nullptr},
+                                      {"g_shs_p", phasor_vec ? io->g_shs_p : nullptr}, {"g_feat_phasor", phasor_vec ? io->g_feat_phasor : nullptr},
+                                      {"g_d_sh_p", phasor_vec ? io->g_d_sh_p : nullptr}}))
+        return gft_fail("gft_assemble_backward: %s is not 16-byte aligned", bad);
     hipStream_t s = (hipStream_t)hip_stream;
     uint32_t *rank, *sums, *ticket, *ndyn;
     assemble_scratch(const_cast<void*>(io->scratch), P, &rank, &sums, &ticket, &ndyn);
     RowsBwdArgs a;
     a.P = P; a.render_static = render_static; a.render_dynamic = render_dynamic;
+    a.M = M; a.M_p = M_p;
     a.io = *io;
     a.dyn_rank = rank;
+    a.counts = ndyn;
     hipLaunchKernelGGL(k_assemble_rows_bwd, dim3((P + ASM_BLOCK - 1) / ASM_BLOCK), dim3(ASM_BLOCK), 0, s, a);
     if (io->g_feat_dc_color || io->g_feat_rest_color)
         launch_wide_bwd_split(s, P, M * 3, io->g_shs, rank, render_static, render_dynamic,

@@ -18,6 +18,19 @@
  * Plain device pointers and sizes, no torch types; every entry point returns 0 on success
  * (message from gft_last_error()).  The caller owns all memory; outputs and gradients are
  * written in full, so they can be allocated uninitialised.
+ *
+ * Alignment.  The quaternions go through the kernels 16 bytes at a time, and so do the rows of a feature
+ * tensor given whole when a row is a multiple of four floats (3 M % 4 == 0, 2 M_p % 4 == 0).  These
+ * pointers must therefore be 16-byte aligned wherever they are not NULL:
+ *   forward:   rotation, rotation_raw, d_rot, out_rotations;
+ *              feat_color, d_sh, out_shs when 3 M % 4 == 0 and the colour features are given whole;
+ *              feat_phasor, d_sh_p, out_shs_p when 2 M_p % 4 == 0 and the phasor features are given whole
+ *   backward:  rotation_raw, d_rot, g_rotations, g_rotation, g_rotation_raw, g_d_rot;
+ *              g_shs, g_feat_color, g_d_sh when 3 M % 4 == 0 and neither g_feat_dc_color nor g_feat_rest_color is given;
+ *              g_shs_p, g_feat_phasor, g_d_sh_p when 2 M_p % 4 == 0 and none of the four phase / amp gradients is given
+ * Every other pointer needs its element's alignment only (the features in their parts are read and written
+ * float by float).  gft_assemble_forward / gft_assemble_backward check this on the host before any launch
+ * and fail with "... is not 16-byte aligned".
  */
 #ifndef GFTORF_ASSEMBLE_H
 #define GFTORF_ASSEMBLE_H
@@ -62,7 +75,9 @@ typedef struct gft_assemble_io {
     /* Nd: rows of the d_* tensors that are given (all share it; 0 <= Nd <= P; ignored when all four are scalars).
      * A dynamic Gaussian whose rank among the dynamic ones is >= Nd has no offset row -- the reference's masked
      * assignment raises for such shapes -- : nothing is read or written out of bounds, that Gaussian's outputs are
-     * NaN and its gradients zero.  gft_assemble_num_dynamic() gives the exact count for a host-side check. */
+     * NaN and its gradients zero.  With more rows than dynamic Gaussians (Nd > the mask's Trues) the rows past the last
+     * dynamic Gaussian reach no output and their gradients are written as zeros.  gft_assemble_num_dynamic() gives the
+     * exact count for a host-side check. */
     int64_t num_offset_rows;
     /* ---- (round 6) the model's own tensors as sources: what pc.get_* computes from them before render() reads it
      * (scene/gaussian_model.py:123-153) is then done here, forward and backward -- no eager exp / sigmoid / cat and no

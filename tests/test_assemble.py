@@ -9,6 +9,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import assemble_ref as R   # noqa: E402
+from test_assemble_parameters import PATTERNS, ROW_COUNTS, pattern_mask   # noqa: E402
 
 
 def make_case(P, M=16, M_p=16, frac=0.3, seed=0, offsets="tensor", mask=None):
@@ -95,7 +96,12 @@ CASES = {
     "all_dynamic": dict(P=2047, M=16, M_p=16, frac=1.0),
     "mlp_zeros": dict(P=3000, M=16, M_p=16, offsets="mlp"),
     "float_offsets": dict(P=3000, M=16, M_p=16, offsets="float"),
+    "straddling_pieces": dict(P=1025, M=4, M_p=2),          # rows of 12 and 4 floats: three and one 16-byte pieces
+    "one_phasor_coeff": dict(P=1025, M=16, M_p=1),          # M != M_p; 2 floats per phasor row: scalar path
 }
+# every row count at a wave's and a rank block's edge under every mask pattern (test_assemble_parameters.py)
+CASES.update({"P%d_%s" % (P, pattern): dict(P=P, M=4, M_p=2, mask=pattern_mask(P, pattern, seed=P))
+              for P in ROW_COUNTS for pattern in PATTERNS})
 
 
 @pytest.mark.gpu
