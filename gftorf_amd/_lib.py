@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgftorf_rast.so")
-ABI_VERSION = 15
+ABI_VERSION = 16
 DEFORM_MAX_INPUTS = 96          # GFT_DEFORM_MAX_INPUTS (include/gftorf_deform.h)
 ACC_STRIDE = 16
 
@@ -140,14 +140,13 @@ EXPORTS = [
     "gft_det_partials_bytes", "gft_get_layout", "gft_binning_capacity", "gft_set_binning_mode", "gft_binning_mode", "gft_set_render_mode", "gft_forward_preprocess", "gft_forward_render", "gft_forward", "gft_forward_enqueue", "gft_backward", "gft_grads_rezero",
     "gft_mark_visible", "gft_profile_enable", "gft_profile_reset", "gft_profile_read",
     "gft_assemble_scratch_bytes", "gft_assemble_forward", "gft_assemble_num_dynamic", "gft_assemble_backward",
-    "gft_knn_scratch_bytes", "gft_knn_mean_dist2", "gft_adam_step", "gft_adam_step_multi", "gft_adam_step_rows", "gft_adam_step_multi_dev",
+    "gft_knn_scratch_bytes", "gft_knn_mean_dist2", "gft_adam_step",
     "gft_deform_inputs", "gft_deform_packed_bytes", "gft_deform_saved_bytes", "gft_deform_scratch_bytes", "gft_deform_pack",
     "gft_deform_forward", "gft_deform_backward", "gft_deform_compact", "gft_deform_rows_work_bytes", "gft_deform_backward_rows",
     "gft_deform_dw_splits", "gft_deform_rows_splits_capacity",
     "gft_ssim_blocks", "gft_ssim_l2_forward", "gft_ssim_l2_backward",
     "gft_image_loss_forward", "gft_image_loss_backward", "gft_pixel_loss_blocks", "gft_pixel_loss_forward", "gft_pixel_loss_backward",
-    "gft_grad_norm_scratch_bytes", "gft_grad_norm", "gft_grad_scale", "gft_adam_step_multi_clip", "gft_adam_step_rows_clip",
-    "gft_adam_step_multi_dev_clip", "gft_adam_step_rows_dev",
+    "gft_grad_norm_scratch_bytes", "gft_grad_norm", "gft_grad_scale",
     "gft_densify_stats", "gft_rows_rank_scratch_bytes", "gft_rows_rank", "gft_rows_rank_dev", "gft_rows_gather", "gft_rows_any_nonzero",
 ]
 # include/gftorf_flow.h (the scene-flow term; no struct, so the ABI version is unchanged)
@@ -202,28 +201,11 @@ def load():
     lib.gft_forward_preprocess.argtypes = [C.c_void_p, C.POINTER(Config), C.POINTER(ForwardIO),
                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.gft_forward_render.restype = C.c_int
-    lib.gft_adam_step.restype = C.c_int
-    lib.gft_adam_step.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                  C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64]
-    lib.gft_adam_step_multi.restype = C.c_int
-    lib.gft_adam_step_multi.argtypes = [C.c_void_p, C.c_int32, C.POINTER(AdamTensor), C.c_double, C.c_double, C.c_double,
-                                        C.c_double]
-    lib.gft_adam_step_multi_dev.restype = C.c_int
-    lib.gft_adam_step_multi_dev.argtypes = [C.c_void_p, C.c_int32, C.POINTER(AdamTensor), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
-                                            C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double]
-    lib.gft_adam_step_rows.restype = C.c_int
-    lib.gft_adam_step_rows.argtypes = [C.c_void_p, C.c_int32, C.POINTER(AdamTensor), C.c_int64, C.c_void_p, C.c_double, C.c_double,
-                                       C.c_double, C.c_double]
     _ptrs = C.POINTER(C.c_void_p)
-    lib.gft_adam_step_multi_clip.restype = C.c_int
-    lib.gft_adam_step_multi_clip.argtypes = lib.gft_adam_step_multi.argtypes + [C.c_void_p]
-    lib.gft_adam_step_rows_clip.restype = C.c_int
-    lib.gft_adam_step_rows_clip.argtypes = lib.gft_adam_step_rows.argtypes + [C.c_void_p]
-    lib.gft_adam_step_multi_dev_clip.restype = C.c_int
-    lib.gft_adam_step_multi_dev_clip.argtypes = lib.gft_adam_step_multi_dev.argtypes + [C.c_void_p]
-    lib.gft_adam_step_rows_dev.restype = C.c_int
-    lib.gft_adam_step_rows_dev.argtypes = [C.c_void_p, C.c_int32, C.POINTER(AdamTensor), C.c_int64, C.c_void_p, _ptrs, _ptrs, C.c_void_p,
-                                           C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]
+    lib.gft_adam_step.restype = C.c_int
+    # stream, count, tensors, rows, row_mask, lr, step, factors, beta1, beta2, eps, weight_decay, grad_scale
+    lib.gft_adam_step.argtypes = [C.c_void_p, C.c_int32, C.POINTER(AdamTensor), C.c_int64, C.c_void_p, _ptrs, _ptrs, C.c_void_p,
+                                  C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]
     lib.gft_grad_norm_scratch_bytes.restype = C.c_size_t
     lib.gft_grad_norm_scratch_bytes.argtypes = [C.c_int64, C.c_int32]
     lib.gft_grad_norm.restype = C.c_int

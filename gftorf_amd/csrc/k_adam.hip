@@ -29,33 +29,6 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
     p = p + (-a.step_size) * (m / denom);                     // addcdiv_(exp_avg, denom, value=-step_size)
 }
 
-__global__ __launch_bounds__(ADAM_BLOCK) void k_adam_step(AdamArgs a)
-{
-    const int64_t n4 = a.n >> 2;
-    const int64_t i = (int64_t)blockIdx.x * ADAM_BLOCK + threadIdx.x;
-    if (i < n4) {
-        float4 p = reinterpret_cast<float4*>(a.p)[i];
-        const float4 g = reinterpret_cast<const float4*>(a.g)[i];
-        float4 m = reinterpret_cast<float4*>(a.m)[i];
-        float4 v = reinterpret_cast<float4*>(a.v)[i];
-        adam_one(p.x, g.x, m.x, v.x, a);
-        adam_one(p.y, g.y, m.y, v.y, a);
-        adam_one(p.z, g.z, m.z, v.z, a);
-        adam_one(p.w, g.w, m.w, v.w, a);
-        reinterpret_cast<float4*>(a.p)[i] = p;
-        reinterpret_cast<float4*>(a.m)[i] = m;
-        reinterpret_cast<float4*>(a.v)[i] = v;
-    }
-    // tail (n not a multiple of 4): the first workgroup's first lanes
-    const int64_t tail = a.n & 3;
-    if (blockIdx.x == 0 && (int64_t)threadIdx.x < tail) {
-        const int64_t k = (n4 << 2) + threadIdx.x;
-        float p = a.p[k], m = a.m[k], v = a.v[k];
-        adam_one(p, a.g[k], m, v, a);
-        a.p[k] = p; a.m[k] = m; a.v[k] = v;
-    }
-}
-
 // Several tensors in ONE launch (own learning rate and step count each; betas, eps, weight decay shared): the
 // reference's optimizers hold 13 one-tensor groups of per-Gaussian parameters and the 36 tensors of the deformation
 // network; at 100 k Gaussians a launch per tensor is bound by launch latency, not by HBM.  Workgroup b serves the
@@ -66,7 +39,7 @@ struct AdamMultiArgs {
     struct T { float* p; const float* g; float* m; float* v; int64_t n; float step_size, bias2_sqrt; uint32_t first_block; uint32_t pad; } t[GFT_ADAM_MAX_TENSORS];
 };
 
-// Learning rates and step counts on the device (gft_adam_step_multi_dev): one workgroup, thread c advances step[c] and leaves
+// Learning rates and step counts on the device (gft_adam_step with lr / step / factors): one workgroup, thread c advances step[c] and leaves
 // the two derived factors of tensor c where the update kernel behind it reads them.
 struct AdamTickArgs {
     int count;
@@ -88,24 +61,34 @@ __global__ __launch_bounds__(64) void k_adam_tick(AdamTickArgs a)
     a.factors[2 * c + 1] = (float)sqrt(1.0 - pow(a.beta2, (double)t));
 }
 
-template <bool DEV>
-__global__ __launch_bounds__(ADAM_BLOCK) void k_adam_multi(AdamMultiArgs a, const float* __restrict__ factors,
-                                                           const float* __restrict__ grad_scale)
+struct AdamBlock { int k; uint32_t blk; };     // the tensor's index in the launch's table, the workgroup's index within the tensor
+
+// The opening of both update kernels: the tensor whose block range holds this workgroup, and its arguments in `s`.
+// dev: step size and bias correction are the factors k_adam_tick left for the tensor, not the table's.
+__device__ __forceinline__ AdamBlock adam_args_of_block(const AdamMultiArgs& a, bool dev, const float* factors, const float* grad_scale,
+                                                        AdamArgs& s)
 {
     int k = 0;
 #pragma unroll 1
     for (int q = 1; q < a.count; q++)
         if (blockIdx.x >= a.t[q].first_block) k = q;
-    AdamArgs s;
     s.n = a.t[k].n; s.p = a.t[k].p; s.g = a.t[k].g; s.m = a.t[k].m; s.v = a.t[k].v;
     s.one_m_beta1 = a.one_m_beta1; s.beta2 = a.beta2; s.one_m_beta2 = a.one_m_beta2; s.step_size = a.t[k].step_size;
     s.bias2_sqrt = a.t[k].bias2_sqrt; s.eps = a.eps; s.weight_decay = a.weight_decay;
     s.grad_scale = grad_scale ? *grad_scale : 1.f;
-    if (DEV) {          // (t[k].pad: the tensor's index in the caller's table = its slot in `factors`)
+    if (dev) {          // (t[k].pad: the tensor's index in the caller's table = its slot in `factors`)
         s.step_size = factors[2 * a.t[k].pad];
         s.bias2_sqrt = factors[2 * a.t[k].pad + 1];
     }
-    const uint32_t blk = blockIdx.x - a.t[k].first_block;
+    return {k, blockIdx.x - a.t[k].first_block};
+}
+
+template <bool DEV>
+__global__ __launch_bounds__(ADAM_BLOCK) void k_adam_multi(AdamMultiArgs a, const float* __restrict__ factors,
+                                                           const float* __restrict__ grad_scale)
+{
+    AdamArgs s;
+    const uint32_t blk = adam_args_of_block(a, DEV, factors, grad_scale, s).blk;
     const int64_t n4 = s.n >> 2;
     // ADAM_ITEMS 16-byte groups per thread, all their loads issued before the arithmetic (index clamped, the stores
     // predicated): one group per thread kept too few bytes in flight for the HBM rate (3.7 TB/s)
@@ -156,21 +139,9 @@ template <bool DEV>
 __global__ __launch_bounds__(ADAM_BLOCK) void k_adam_rows(AdamRowsArgs a, const float* __restrict__ factors,
                                                           const float* __restrict__ grad_scale)
 {
-    int k = 0;
-#pragma unroll 1
-    for (int q = 1; q < a.m.count; q++)
-        if (blockIdx.x >= a.m.t[q].first_block) k = q;
     AdamArgs s;
-    s.n = a.m.t[k].n; s.p = a.m.t[k].p; s.g = a.m.t[k].g; s.m = a.m.t[k].m; s.v = a.m.t[k].v;
-    s.one_m_beta1 = a.m.one_m_beta1; s.beta2 = a.m.beta2; s.one_m_beta2 = a.m.one_m_beta2; s.step_size = a.m.t[k].step_size;
-    s.bias2_sqrt = a.m.t[k].bias2_sqrt; s.eps = a.m.eps; s.weight_decay = a.m.weight_decay;
-    s.grad_scale = grad_scale ? *grad_scale : 1.f;
-    if (DEV) {          // as k_adam_multi<true>: the factors k_adam_tick left for this tensor
-        s.step_size = factors[2 * a.m.t[k].pad];
-        s.bias2_sqrt = factors[2 * a.m.t[k].pad + 1];
-    }
+    const auto [k, blk] = adam_args_of_block(a.m, DEV, factors, grad_scale, s);
     const uint32_t rf = a.row_floats[k];
-    const uint32_t blk = blockIdx.x - a.m.t[k].first_block;
     const int64_t n4 = s.n >> 2;
     const int64_t i = (int64_t)blk * ADAM_BLOCK + threadIdx.x;
     if (i < n4) {
@@ -239,19 +210,30 @@ __device__ __forceinline__ double norm_block_sum(double d, double* lds)
     return lds[0] + lds[1] + lds[2] + lds[3];
 }
 
-__global__ __launch_bounds__(NORM_BLOCK) void k_grad_norm_partial(GradSpanArgs a, double* __restrict__ partials)
+// The span walk of k_grad_norm_partial and k_grad_scale: the span whose block range holds this workgroup (its blk-th), as up to
+// three scalars in front of the first 16-byte boundary (head), n4 16-byte groups (body) and up to three scalars behind them.
+struct GradSpan { float* g; int64_t n; uint32_t head; uint32_t blk; float4* body; int64_t n4; };
+
+__device__ __forceinline__ GradSpan grad_span_of_block(const GradSpanArgs& a)
 {
-    __shared__ double lds[NORM_BLOCK / 64];
     int k = 0;
 #pragma unroll 1
     for (int q = 1; q < a.count; q++)
         if (blockIdx.x >= a.t[q].first_block) k = q;
-    const float* g = a.t[k].g;
-    const int64_t n = a.t[k].n;
-    const uint32_t head = a.t[k].head;
-    const uint32_t blk = blockIdx.x - a.t[k].first_block;
-    const float4* body = reinterpret_cast<const float4*>(g + head);
-    const int64_t n4 = (n - head) >> 2;
+    GradSpan s;
+    s.g = a.t[k].g;
+    s.n = a.t[k].n;
+    s.head = a.t[k].head;
+    s.blk = blockIdx.x - a.t[k].first_block;
+    s.body = reinterpret_cast<float4*>(s.g + s.head);
+    s.n4 = (s.n - s.head) >> 2;
+    return s;
+}
+
+__global__ __launch_bounds__(NORM_BLOCK) void k_grad_norm_partial(GradSpanArgs a, double* __restrict__ partials)
+{
+    __shared__ double lds[NORM_BLOCK / 64];
+    const auto [g, n, head, blk, body, n4] = grad_span_of_block(a);
     float4 x[NORM_ITEMS];
     int64_t idx[NORM_ITEMS];
 #pragma unroll
@@ -295,16 +277,7 @@ __global__ __launch_bounds__(NORM_BLOCK) void k_grad_scale(GradSpanArgs a, const
 {
     const float c = *coef;
     if (c == 1.0f) return;          // g * 1 is g: nothing to store
-    int k = 0;
-#pragma unroll 1
-    for (int q = 1; q < a.count; q++)
-        if (blockIdx.x >= a.t[q].first_block) k = q;
-    float* g = a.t[k].g;
-    const int64_t n = a.t[k].n;
-    const uint32_t head = a.t[k].head;
-    const uint32_t blk = blockIdx.x - a.t[k].first_block;
-    float4* body = reinterpret_cast<float4*>(g + head);
-    const int64_t n4 = (n - head) >> 2;
+    const auto [g, n, head, blk, body, n4] = grad_span_of_block(a);
     float4 x[NORM_ITEMS];
     int64_t idx[NORM_ITEMS];
 #pragma unroll
@@ -413,10 +386,10 @@ extern "C" int gft_grad_scale(void* hip_stream, int32_t count, float* const* gra
     return 0;
 }
 
-// fills the per-tensor table of a launch from tensors[c0 ...]; returns the number of entries (< 0: error)
+// fills the per-tensor table of a launch from tensors[c0 ...]; returns the number of entries (< 0: error).  row_floats: the
+// row-masked launch (every tensor has `rows` rows); dev: learning rates and step counts are on the device, the table's are not read
 static int adam_table(AdamMultiArgs& a, const gft_adam_tensor* tensors, int32_t c0, int32_t count, double beta1, double beta2,
-                      double eps, double weight_decay, uint64_t* blocks_out, int64_t rows, uint32_t* row_floats, const char* who,
-                      bool dev = false)
+                      double eps, double weight_decay, uint64_t* blocks_out, int64_t rows, uint32_t* row_floats, bool dev)
 {
     a.one_m_beta1 = (float)(1.0 - beta1);
     a.beta2 = (float)beta2;
@@ -427,19 +400,21 @@ static int adam_table(AdamMultiArgs& a, const gft_adam_tensor* tensors, int32_t 
     uint64_t blocks = 0;
     for (int32_t c = c0; c < count && c < c0 + GFT_ADAM_MAX_TENSORS; c++) {
         const gft_adam_tensor& t = tensors[c];
-        if (t.n < 0) { gft_fail("%s: tensor %d has n < 0", who, c); return -1; }
+        if (t.n < 0) { gft_fail("gft_adam_step: tensor %d has n < 0", c); return -1; }
         if (t.n == 0) continue;
-        if (!dev && t.step < 1) { gft_fail("%s: tensor %d: step must be >= 1", who, c); return -1; }
-        if (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq) { gft_fail("%s: tensor %d has a NULL pointer", who, c); return -1; }
+        if (!dev && t.step < 1) { gft_fail("gft_adam_step: tensor %d: step must be >= 1", c); return -1; }
+        if (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq) { gft_fail("gft_adam_step: tensor %d has a NULL pointer", c); return -1; }
         if ((((uintptr_t)t.param | (uintptr_t)t.grad | (uintptr_t)t.exp_avg | (uintptr_t)t.exp_avg_sq) & 15) != 0) {
-            gft_fail("%s: pointers of tensor %d are not 16-byte aligned", who, c);
+            gft_fail("gft_adam_step: pointers of tensor %d are not 16-byte aligned", c);
             return -1;
         }
         if (row_floats) {
-            if (t.n % rows != 0 || t.n / rows > 0xffffffffll) { gft_fail("%s: tensor %d does not have %lld rows", who, c, (long long)rows); return -1; }
+            if (t.n % rows != 0 || t.n / rows > 0xffffffffll) { gft_fail("gft_adam_step: tensor %d does not have %lld rows", c, (long long)rows); return -1; }
             row_floats[k] = (uint32_t)(t.n / rows);
         }
         a.t[k].p = t.param; a.t[k].g = t.grad; a.t[k].m = t.exp_avg; a.t[k].v = t.exp_avg_sq; a.t[k].n = t.n;
+        // torch/optim/adam.py: bias_correction1 = 1 - beta1 ** step; step_size = lr / bias_correction1;
+        // bias_correction2_sqrt = (1 - beta2 ** step) ** 0.5 -- Python floats, rounded when they meet a tensor
         a.t[k].step_size = dev ? 0.f : (float)(t.lr / (1.0 - pow(beta1, (double)t.step)));
         a.t[k].bias2_sqrt = dev ? 1.f : (float)sqrt(1.0 - pow(beta2, (double)t.step));
         a.t[k].first_block = (uint32_t)blocks; a.t[k].pad = (uint32_t)(c - c0);
@@ -448,182 +423,63 @@ static int adam_table(AdamMultiArgs& a, const gft_adam_tensor* tensors, int32_t 
         blocks += n4 > 0 ? (uint64_t)((n4 + per_block - 1) / per_block) : 1;
         k++;
     }
-    if (blocks > 0x7fffffffull) { gft_fail("%s: too many elements for one launch", who); return -1; }
+    if (blocks > 0x7fffffffull) { gft_fail("gft_adam_step: too many elements for one launch"); return -1; }
     a.count = k;
     *blocks_out = blocks;
     return k;
 }
 
-// the tick of the device-side variants: the counts of tensors [c0, c1) advance, their factors are left in factors[2 c ...]
+// the tick in front of an update with device-side rates: the counts of tensors [c0, c1) advance, their factors are left in
+// factors[2 c ...]
 static int adam_tick(void* hip_stream, int32_t c0, int32_t c1, const double* const* lr, float* const* step, float* factors, double beta1,
-                     double beta2, const char* who)
+                     double beta2)
 {
     AdamTickArgs tick;
     tick.count = c1 - c0; tick.beta1 = beta1; tick.beta2 = beta2; tick.factors = factors + 2 * (size_t)c0;
     for (int32_t c = c0; c < c1; c++) {
-        if (!lr[c] || !step[c]) return gft_fail("%s: tensor %d: lr / step pointer is NULL", who, c);
+        if (!lr[c] || !step[c]) return gft_fail("gft_adam_step: tensor %d: lr / step pointer is NULL", c);
         tick.lr[c - c0] = lr[c]; tick.step[c - c0] = step[c];
     }
     hipLaunchKernelGGL(k_adam_tick, dim3(1), dim3(64), 0, (hipStream_t)hip_stream, tick);
     return 0;
 }
 
-// lr == NULL: learning rates and step counts of the table (host); otherwise on the device (k_adam_tick in front)
-static int adam_rows(void* hip_stream, int32_t count, const gft_adam_tensor* tensors, int64_t rows, const uint8_t* row_mask,
-                     const double* const* lr, float* const* step, float* factors, double beta1, double beta2, double eps,
-                     double weight_decay, const float* grad_scale, const char* who)
+extern "C" int gft_adam_step(void* hip_stream, int32_t count, const gft_adam_tensor* tensors, int64_t rows, const uint8_t* row_mask,
+                             const double* const* lr, float* const* step, float* factors, double beta1, double beta2, double eps,
+                             double weight_decay, const float* grad_scale)
 {
+    const bool dev = lr || step || factors;
+    if (count < 0) return gft_fail("gft_adam_step: count < 0");
+    if (count == 0 || (row_mask && !dev && rows == 0)) return 0;
+    if (!tensors) return gft_fail("gft_adam_step: tensors is NULL");
+    if (dev && (!lr || !step || !factors)) return gft_fail("gft_adam_step: lr, step and factors go together, one of them is NULL");
+    if (!row_mask && rows != 0) return gft_fail("gft_adam_step: bad argument (rows without a row_mask)");
+    // (a mask without rows: under device-side rates there would be counts to advance and nothing to update -- such tensors belong
+    // in a dense call)
+    if (row_mask && dev && rows <= 0) return gft_fail("gft_adam_step: rows must be > 0");
+    if (row_mask && rows < 0) return gft_fail("gft_adam_step: bad argument (rows < 0)");
     for (int32_t c0 = 0; c0 < count; c0 += GFT_ADAM_MAX_TENSORS) {
         const int32_t c1 = count < c0 + GFT_ADAM_MAX_TENSORS ? count : c0 + GFT_ADAM_MAX_TENSORS;
-        AdamRowsArgs a;
+        AdamRowsArgs a;         // (a.m alone is the dense kernel's argument)
         a.row_mask = row_mask;
         uint64_t blocks = 0;
-        const int k = adam_table(a.m, tensors, c0, count, beta1, beta2, eps, weight_decay, &blocks, rows, a.row_floats, who, lr != nullptr);
+        const int k = adam_table(a.m, tensors, c0, count, beta1, beta2, eps, weight_decay, &blocks, rows, row_mask ? a.row_floats : nullptr, dev);
         if (k < 0) return 1;
-        if (lr) {
-            if (adam_tick(hip_stream, c0, c1, lr, step, factors, beta1, beta2, who)) return 1;
-            if (k > 0)
-                hipLaunchKernelGGL(k_adam_rows<true>, dim3((unsigned)blocks), dim3(ADAM_BLOCK), 0, (hipStream_t)hip_stream, a,
-                                   (const float*)(factors + 2 * (size_t)c0), grad_scale);
-        } else {
-            if (k == 0) continue;
-            hipLaunchKernelGGL(k_adam_rows<false>, dim3((unsigned)blocks), dim3(ADAM_BLOCK), 0, (hipStream_t)hip_stream, a,
-                               (const float*)nullptr, grad_scale);
+        // (the counts advance for every tensor of the table, as torch's capturable Adam advances state["step"] -- also for an
+        // empty tensor, which takes no update)
+        if (dev && adam_tick(hip_stream, c0, c1, lr, step, factors, beta1, beta2)) return 1;
+        if (k == 0 && !dev) continue;
+        if (k > 0) {
+            const dim3 grid((unsigned)blocks), block(ADAM_BLOCK);
+            const hipStream_t s = (hipStream_t)hip_stream;
+            const float* f = dev ? factors + 2 * (size_t)c0 : nullptr;
+            if (row_mask && dev) hipLaunchKernelGGL(k_adam_rows<true>, grid, block, 0, s, a, f, grad_scale);
+            else if (row_mask) hipLaunchKernelGGL(k_adam_rows<false>, grid, block, 0, s, a, f, grad_scale);
+            else if (dev) hipLaunchKernelGGL(k_adam_multi<true>, grid, block, 0, s, a.m, f, grad_scale);
+            else hipLaunchKernelGGL(k_adam_multi<false>, grid, block, 0, s, a.m, f, grad_scale);
         }
         hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return gft_fail("%s: %s", who, hipGetErrorString(e));
+        if (e != hipSuccess) return gft_fail("gft_adam_step: %s", hipGetErrorString(e));
     }
-    return 0;
-}
-
-static int adam_multi(void* hip_stream, int32_t count, const gft_adam_tensor* tensors, const double* const* lr, float* const* step,
-                      float* factors, double beta1, double beta2, double eps, double weight_decay, const float* grad_scale,
-                      const char* who)
-{
-    for (int32_t c0 = 0; c0 < count; c0 += GFT_ADAM_MAX_TENSORS) {
-        const int32_t c1 = count < c0 + GFT_ADAM_MAX_TENSORS ? count : c0 + GFT_ADAM_MAX_TENSORS;
-        AdamMultiArgs a;
-        uint64_t blocks = 0;
-        const int k = adam_table(a, tensors, c0, count, beta1, beta2, eps, weight_decay, &blocks, 0, nullptr, who, lr != nullptr);
-        if (k < 0) return 1;
-        if (lr) {
-            // (the counts advance for every tensor of the table, as torch's capturable Adam advances state["step"] -- also for an
-            // empty tensor, which takes no update)
-            if (adam_tick(hip_stream, c0, c1, lr, step, factors, beta1, beta2, who)) return 1;
-            if (k > 0)
-                hipLaunchKernelGGL(k_adam_multi<true>, dim3((unsigned)blocks), dim3(ADAM_BLOCK), 0, (hipStream_t)hip_stream, a,
-                                   (const float*)(factors + 2 * (size_t)c0), grad_scale);
-        } else {
-            if (k == 0) continue;
-            hipLaunchKernelGGL(k_adam_multi<false>, dim3((unsigned)blocks), dim3(ADAM_BLOCK), 0, (hipStream_t)hip_stream, a,
-                               (const float*)nullptr, grad_scale);
-        }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return gft_fail("%s: %s", who, hipGetErrorString(e));
-    }
-    return 0;
-}
-
-extern "C" int gft_adam_step_rows(void* hip_stream, int32_t count, const gft_adam_tensor* tensors, int64_t rows,
-                                  const uint8_t* row_mask, double beta1, double beta2, double eps, double weight_decay)
-{
-    if (count < 0) return gft_fail("gft_adam_step_rows: count < 0");
-    if (count == 0 || rows == 0) return 0;
-    if (!tensors || !row_mask || rows < 0) return gft_fail("gft_adam_step_rows: bad argument");
-    return adam_rows(hip_stream, count, tensors, rows, row_mask, nullptr, nullptr, nullptr, beta1, beta2, eps, weight_decay, nullptr,
-                     "gft_adam_step_rows");
-}
-
-extern "C" int gft_adam_step_rows_clip(void* hip_stream, int32_t count, const gft_adam_tensor* tensors, int64_t rows,
-                                       const uint8_t* row_mask, double beta1, double beta2, double eps, double weight_decay,
-                                       const float* grad_scale)
-{
-    if (count < 0) return gft_fail("gft_adam_step_rows_clip: count < 0");
-    if (count == 0 || rows == 0) return 0;
-    if (!tensors || !row_mask || rows < 0) return gft_fail("gft_adam_step_rows_clip: bad argument (NULL table or mask, rows < 0)");
-    return adam_rows(hip_stream, count, tensors, rows, row_mask, nullptr, nullptr, nullptr, beta1, beta2, eps, weight_decay, grad_scale,
-                     "gft_adam_step_rows_clip");
-}
-
-extern "C" int gft_adam_step_rows_dev(void* hip_stream, int32_t count, const gft_adam_tensor* tensors, int64_t rows,
-                                      const uint8_t* row_mask, const double* const* lr, float* const* step, float* factors,
-                                      double beta1, double beta2, double eps, double weight_decay, const float* grad_scale)
-{
-    if (count < 0) return gft_fail("gft_adam_step_rows_dev: count < 0");
-    if (count == 0) return 0;
-    if (!tensors || !row_mask || !lr || !step || !factors) return gft_fail("gft_adam_step_rows_dev: NULL argument");
-    // (no rows: there would be counts to advance and nothing to update -- such tensors belong in gft_adam_step_multi_dev)
-    if (rows <= 0) return gft_fail("gft_adam_step_rows_dev: rows must be > 0");
-    return adam_rows(hip_stream, count, tensors, rows, row_mask, lr, step, factors, beta1, beta2, eps, weight_decay, grad_scale,
-                     "gft_adam_step_rows_dev");
-}
-
-extern "C" int gft_adam_step_multi(void* hip_stream, int32_t count, const gft_adam_tensor* tensors, double beta1,
-                                   double beta2, double eps, double weight_decay)
-{
-    if (count < 0) return gft_fail("gft_adam_step_multi: count < 0");
-    if (count == 0) return 0;
-    if (!tensors) return gft_fail("gft_adam_step_multi: tensors is NULL");
-    return adam_multi(hip_stream, count, tensors, nullptr, nullptr, nullptr, beta1, beta2, eps, weight_decay, nullptr, "gft_adam_step_multi");
-}
-
-extern "C" int gft_adam_step_multi_clip(void* hip_stream, int32_t count, const gft_adam_tensor* tensors, double beta1,
-                                        double beta2, double eps, double weight_decay, const float* grad_scale)
-{
-    if (count < 0) return gft_fail("gft_adam_step_multi_clip: count < 0");
-    if (count == 0) return 0;
-    if (!tensors) return gft_fail("gft_adam_step_multi_clip: tensors is NULL");
-    return adam_multi(hip_stream, count, tensors, nullptr, nullptr, nullptr, beta1, beta2, eps, weight_decay, grad_scale,
-                      "gft_adam_step_multi_clip");
-}
-
-extern "C" int gft_adam_step_multi_dev(void* hip_stream, int32_t count, const gft_adam_tensor* tensors, const double* const* lr,
-                                       float* const* step, float* factors, double beta1, double beta2, double eps,
-                                       double weight_decay)
-{
-    if (count < 0) return gft_fail("gft_adam_step_multi_dev: count < 0");
-    if (count == 0) return 0;
-    if (!tensors || !lr || !step || !factors) return gft_fail("gft_adam_step_multi_dev: NULL argument");
-    return adam_multi(hip_stream, count, tensors, lr, step, factors, beta1, beta2, eps, weight_decay, nullptr, "gft_adam_step_multi_dev");
-}
-
-extern "C" int gft_adam_step_multi_dev_clip(void* hip_stream, int32_t count, const gft_adam_tensor* tensors, const double* const* lr,
-                                            float* const* step, float* factors, double beta1, double beta2, double eps,
-                                            double weight_decay, const float* grad_scale)
-{
-    if (count < 0) return gft_fail("gft_adam_step_multi_dev_clip: count < 0");
-    if (count == 0) return 0;
-    if (!tensors || !lr || !step || !factors) return gft_fail("gft_adam_step_multi_dev_clip: NULL argument");
-    return adam_multi(hip_stream, count, tensors, lr, step, factors, beta1, beta2, eps, weight_decay, grad_scale,
-                      "gft_adam_step_multi_dev_clip");
-}
-
-extern "C" int gft_adam_step(void* hip_stream, int64_t n, float* param, const float* grad, float* exp_avg,
-                             float* exp_avg_sq, double lr, double beta1, double beta2, double eps, double weight_decay,
-                             int64_t step)
-{
-    if (n < 0) return gft_fail("gft_adam_step: n < 0");
-    if (step < 1) return gft_fail("gft_adam_step: step must be >= 1");
-    if (n == 0) return 0;
-    if (!param || !grad || !exp_avg || !exp_avg_sq) return gft_fail("gft_adam_step: NULL pointer");
-    if ((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) != 0)
-        return gft_fail("gft_adam_step: pointers must be 16-byte aligned");
-    AdamArgs a;
-    a.n = n; a.p = param; a.g = grad; a.m = exp_avg; a.v = exp_avg_sq;
-    // torch/optim/adam.py: bias_correction1 = 1 - beta1 ** step; step_size = lr / bias_correction1;
-    // bias_correction2_sqrt = (1 - beta2 ** step) ** 0.5 -- Python floats, rounded when they meet a tensor
-    a.one_m_beta1 = (float)(1.0 - beta1);
-    a.beta2 = (float)beta2;
-    a.one_m_beta2 = (float)(1.0 - beta2);
-    a.step_size = (float)(lr / (1.0 - pow(beta1, (double)step)));
-    a.bias2_sqrt = (float)sqrt(1.0 - pow(beta2, (double)step));
-    a.eps = (float)eps;
-    a.weight_decay = (float)weight_decay;
-    a.grad_scale = 1.f;
-    const int64_t n4 = n >> 2;
-    const int64_t blocks = n4 > 0 ? (n4 + ADAM_BLOCK - 1) / ADAM_BLOCK : 1;
-    hipLaunchKernelGGL(k_adam_step, dim3((unsigned)blocks), dim3(ADAM_BLOCK), 0, (hipStream_t)hip_stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return gft_fail("gft_adam_step: %s", hipGetErrorString(e));
     return 0;
 }

@@ -203,11 +203,16 @@ class FusedAdam(torch.optim.Adam):
         self.last_grad_norm = out[0]
         return out.data_ptr() + 4
 
-    def _step_capturable(self, lib, visibility=None, rows=None, mask_u8=None, row_params=None, max_grad_norm=None):
+    def _collect(self, visibility, rows, row_params):
+        """Every tensor that takes a step, in the order of ``param_groups``: ``buckets`` maps the settings one launch shares,
+        (device, betas, eps, weight decay, by rows), to its tensors as (parameter, gradient, both moments, lr, ``state["step"]``,
+        slot); ``grads`` are the gradients the launches read.  Capturable: ``slot`` is the tensor's place in the device buffers,
+        whose learning rate is written here (eager: None)."""
+        cap = self._gft_capturable
         buckets, grads = {}, []
         for group in self.param_groups:
             beta1, beta2 = group["betas"]
-            eps, wd = group["eps"], group["weight_decay"]
+            lr, eps, wd = float(group["lr"]), group["eps"], group["weight_decay"]
             for p in group["params"]:
                 if p.grad is None:
                     continue
@@ -218,50 +223,42 @@ class FusedAdam(torch.optim.Adam):
                 if p.dtype != torch.float32 or not p.is_contiguous():
                     raise RuntimeError("gftorf_amd.FusedAdam: parameters must be contiguous float32 tensors")
                 state = self.state[p]
-                if "exp_avg" not in state:
-                    state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                slot, b = self._slot(p, state)
-                b["lr_np"][slot] = float(group["lr"])
+                if cap:
+                    # (the count is created, or adopted, with its slot)
+                    if "exp_avg" not in state:
+                        state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                        state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    slot, b = self._slot(p, state)
+                    b["lr_np"][slot] = lr
+                else:
+                    if len(state) == 0:
+                        # same state as torch.optim.Adam._init_group
+                        state["step"] = torch.tensor(0.0, dtype=torch.float32)
+                        state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                        state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    slot = None
                 m, v = state["exp_avg"], state["exp_avg_sq"]
                 grad = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+                # the kernels move 16-byte pieces: a gradient that is a view at an odd offset (e.g. the rasterizer's
+                # dc_offset gradient, element 1 of a two-float tensor) is copied once; parameter and moments are the
+                # caller's own allocations and must be aligned as torch allocates them
                 if grad.data_ptr() % 16:
                     grad = grad.clone()
-                if p.data_ptr() % 16 or m.data_ptr() % 16 or v.data_ptr() % 16 or not (m.is_contiguous() and v.is_contiguous()):
+                contiguous = m.is_contiguous() and v.is_contiguous()
+                aligned = not (p.data_ptr() % 16 or m.data_ptr() % 16 or v.data_ptr() % 16)
+                if cap and not (contiguous and aligned):
                     raise RuntimeError("gftorf_amd.FusedAdam: parameters and optimizer state must be contiguous and 16-byte aligned")
+                if not contiguous:
+                    raise RuntimeError("gftorf_amd.FusedAdam: optimizer state must be contiguous")
+                if not aligned:
+                    raise RuntimeError("gftorf_amd.FusedAdam: parameters and optimizer state must be 16-byte aligned")
                 by_rows = rows is not None and p.dim() >= 1 and p.shape[0] == rows and rows > 0 and (
                     row_params is None or id(p) in row_params)
                 if by_rows and visibility.device != p.device:
                     raise RuntimeError("gftorf_amd.FusedAdam: visibility is on %s, the parameter on %s" % (visibility.device, p.device))
-                buckets.setdefault((p.device, float(beta1), float(beta2), float(eps), float(wd), by_rows), []).append((p, grad, m, v, slot))
+                buckets.setdefault((p.device, float(beta1), float(beta2), float(eps), float(wd), by_rows), []).append((p, grad, m, v, lr, state["step"], slot))
                 grads.append(grad)
-        coef = self._clip_coef(lib, grads, max_grad_norm)
-        copied = set()
-        for (dev, beta1, beta2, eps, wd, by_rows), items in buckets.items():
-            b = self._buffers(dev)
-            # the learning rates of this step: host values -> device, a copy node under capture (a replay re-reads the pinned
-            # buffer: refresh_lr); once per device
-            if dev not in copied:
-                b["lr"].copy_(b["lr_host"], non_blocking=True)
-                copied.add(dev)
-            n = len(items)
-            tab = (_lib.AdamTensor * n)()
-            lrs, steps = (C.c_void_p * n)(), (C.c_void_p * n)()
-            lr0, st0 = b["lr"].data_ptr(), b["step"].data_ptr()
-            for i, (e, (p, g, m, v, slot)) in enumerate(zip(tab, items)):
-                e.param, e.grad, e.exp_avg, e.exp_avg_sq, e.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
-                e.lr, e.step = 0.0, 0
-                lrs[i], steps[i] = lr0 + 8 * slot, st0 + 4 * slot
-            with _lib.on_device(dev):
-                if by_rows:
-                    _lib.check(lib.gft_adam_step_rows_dev(_lib.raw_stream(dev), n, tab, rows, mask_u8.data_ptr(), lrs, steps,
-                                                          b["factors"].data_ptr(), beta1, beta2, eps, wd, coef))
-                elif coef is not None:
-                    _lib.check(lib.gft_adam_step_multi_dev_clip(_lib.raw_stream(dev), n, tab, lrs, steps, b["factors"].data_ptr(),
-                                                                beta1, beta2, eps, wd, coef))
-                else:
-                    _lib.check(lib.gft_adam_step_multi_dev(_lib.raw_stream(dev), n, tab, lrs, steps, b["factors"].data_ptr(),
-                                                           beta1, beta2, eps, wd))
+        return buckets, grads
 
     @torch.no_grad()
     def step(self, closure=None, visibility=None, row_params=None, max_grad_norm=None):
@@ -273,7 +270,7 @@ class FusedAdam(torch.optim.Adam):
         ``max_grad_norm``: the update of ``clip_grad_norm_(all parameters of this optimizer, max_grad_norm)`` followed by
         ``step()``, with ``.grad`` left unscaled and the norm in ``self.last_grad_norm`` (see the module docstring)."""
         loss = None
-        rows = None
+        rows = mask_u8 = None
         if row_params is not None:
             row_params = {id(t) for t in row_params}
         if visibility is not None:
@@ -286,68 +283,34 @@ class FusedAdam(torch.optim.Adam):
             with torch.enable_grad():
                 loss = closure()
         lib = _lib.load()
-        if self._gft_capturable:
-            self._step_capturable(lib, visibility, rows, mask_u8 if visibility is not None else None, row_params, max_grad_norm)
-            return loss
-        # (parameter, gradient, moments, lr, step tensor) of every tensor that takes a step, bucketed by the settings
-        # one launch shares: (device, betas, eps, weight decay)
-        buckets, grads = {}, []
-        for group in self.param_groups:
-            beta1, beta2 = group["betas"]
-            lr, eps, wd = group["lr"], group["eps"], group["weight_decay"]
-            if isinstance(lr, torch.Tensor):
-                lr = float(lr)
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                if p.device.type != "cuda":
-                    raise RuntimeError("gftorf_amd.FusedAdam runs on a HIP device only (parameter on %s); there is no CPU path" % (p.device,))
-                if p.grad.is_sparse:
-                    raise RuntimeError("Adam does not support sparse gradients, please consider SparseAdam instead")
-                if p.dtype != torch.float32 or not p.is_contiguous():
-                    raise RuntimeError("gftorf_amd.FusedAdam: parameters must be contiguous float32 tensors")
-                state = self.state[p]
-                if len(state) == 0:
-                    # same state as torch.optim.Adam._init_group
-                    state["step"] = torch.tensor(0.0, dtype=torch.float32)
-                    state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                m, v = state["exp_avg"], state["exp_avg_sq"]
-                if not (m.is_contiguous() and v.is_contiguous()):
-                    raise RuntimeError("gftorf_amd.FusedAdam: optimizer state must be contiguous")
-                grad = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                # the kernels move 16-byte pieces: a gradient that is a view at an odd offset (e.g. the rasterizer's
-                # dc_offset gradient, element 1 of a two-float tensor) is copied once; parameter and moments are the
-                # caller's own allocations and must be aligned as torch allocates them
-                if grad.data_ptr() % 16:
-                    grad = grad.clone()
-                if p.data_ptr() % 16 or m.data_ptr() % 16 or v.data_ptr() % 16:
-                    raise RuntimeError("gftorf_amd.FusedAdam: parameters and optimizer state must be 16-byte aligned")
-                by_rows = rows is not None and p.dim() >= 1 and p.shape[0] == rows and rows > 0 and (
-                    row_params is None or id(p) in row_params)
-                if by_rows and visibility.device != p.device:
-                    raise RuntimeError("gftorf_amd.FusedAdam: visibility is on %s, the parameter on %s" % (visibility.device, p.device))
-                buckets.setdefault((p.device, float(beta1), float(beta2), float(eps), float(wd), by_rows), []).append(
-                    (p, grad, m, v, float(lr), state["step"]))
-                grads.append(grad)
+        cap = self._gft_capturable
+        buckets, grads = self._collect(visibility, rows, row_params)
         coef = self._clip_coef(lib, grads, max_grad_norm)
+        copied = set()
         for (dev, beta1, beta2, eps, wd, by_rows), items in buckets.items():
-            tab = (_lib.AdamTensor * len(items))()
-            for e, (p, g, m, v, lr, st) in zip(tab, items):
+            n = len(items)
+            tab = (_lib.AdamTensor * n)()
+            lrs = steps = factors = None
+            if cap:
+                b = self._buffers(dev)
+                # the learning rates of this step: host values -> device, a copy node under capture (a replay re-reads the pinned
+                # buffer: refresh_lr); once per device
+                if dev not in copied:
+                    b["lr"].copy_(b["lr_host"], non_blocking=True)
+                    copied.add(dev)
+                lrs, steps, factors = (C.c_void_p * n)(), (C.c_void_p * n)(), b["factors"].data_ptr()
+                lr0, st0 = b["lr"].data_ptr(), b["step"].data_ptr()
+            for i, (e, (p, g, m, v, lr, st, slot)) in enumerate(zip(tab, items)):
                 e.param, e.grad, e.exp_avg, e.exp_avg_sq, e.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
-                e.lr, e.step = lr, int(st) + 1
-            with _lib.on_device(dev):
-                if by_rows and coef is not None:
-                    _lib.check(lib.gft_adam_step_rows_clip(_lib.raw_stream(dev), len(items), tab, rows, mask_u8.data_ptr(), beta1,
-                                                           beta2, eps, wd, coef))
-                elif by_rows:
-                    _lib.check(lib.gft_adam_step_rows(_lib.raw_stream(dev), len(items), tab, rows, mask_u8.data_ptr(), beta1, beta2,
-                                                      eps, wd))
-                elif coef is not None:
-                    _lib.check(lib.gft_adam_step_multi_clip(_lib.raw_stream(dev), len(items), tab, beta1, beta2, eps, wd, coef))
+                if cap:
+                    lrs[i], steps[i] = lr0 + 8 * slot, st0 + 4 * slot
                 else:
-                    _lib.check(lib.gft_adam_step_multi(_lib.raw_stream(dev), len(items), tab, beta1, beta2, eps, wd))
-            # the step counters advance only once the launch was accepted (a rejected table leaves every tensor of the
-            # bucket and its counter as they were)
-            torch._foreach_add_([it[5] for it in items], 1)
+                    e.lr, e.step = lr, int(st) + 1
+            with _lib.on_device(dev):
+                _lib.check(lib.gft_adam_step(_lib.raw_stream(dev), n, tab, rows if by_rows else 0, mask_u8.data_ptr() if by_rows else None,
+                                             lrs, steps, factors, beta1, beta2, eps, wd, coef))
+            if not cap:
+                # the step counters advance only once the launch was accepted (a rejected table leaves every tensor of the
+                # bucket and its counter as they were)
+                torch._foreach_add_([it[5] for it in items], 1)
         return loss

@@ -24,15 +24,9 @@
 extern "C" {
 #endif
 
-/* Hyper-parameters as torch holds them (Python floats = double); `step` = t, the 1-based count of
- * this update.  Derived factors (1 - beta, lr / (1 - beta1^t), sqrt(1 - beta2^t)) are formed in
- * double precision and rounded to fp32 once, as torch does. */
-int gft_adam_step(void* hip_stream, int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
-                  double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step);
-
-/* The same update for several tensors in one launch per GFT_ADAM_MAX_TENSORS tensors: every tensor has its own
- * learning rate and step count (the reference keeps one tensor per parameter group, each with its own lr,
- * scene/gaussian_model.py:247-272), betas / eps / weight decay are shared. */
+/* One entry of the table a step is given: a step updates several tensors in one launch per GFT_ADAM_MAX_TENSORS tensors.  Every
+ * tensor has its own learning rate and step count (the reference keeps one tensor per parameter group, each with its own lr,
+ * scene/gaussian_model.py:247-272); betas / eps / weight decay are shared. */
 #define GFT_ADAM_MAX_TENSORS 40
 typedef struct gft_adam_tensor {
     float* param;
@@ -44,39 +38,37 @@ typedef struct gft_adam_tensor {
     int64_t step;      /* 1-based count of this update */
 } gft_adam_tensor;
 
-int gft_adam_step_multi(void* hip_stream, int32_t count, const gft_adam_tensor* tensors /*host*/, double beta1,
-                        double beta2, double eps, double weight_decay);
-
-/* Opt-in, NOT the reference's optimizer (which is dense): the same update restricted to the rows of a mask -- SURVEY
- * section 8(f) row 4, "sparse Adam on visible Gaussians".  Every tensor has `rows` rows (n = rows x floats per row);
- * row r takes the step when row_mask[r] != 0 (device pointer, one byte per row: e.g. `radii > 0` of the iteration's
- * render, reference train.py:181 `visibility_filter`); the other rows' parameter and moments are left as they are
- * (their moments do not decay).  16-byte groups without a masked-in element are neither read nor written. */
-int gft_adam_step_rows(void* hip_stream, int32_t count, const gft_adam_tensor* tensors /*host*/, int64_t rows,
-                       const uint8_t* row_mask, double beta1, double beta2, double eps, double weight_decay);
-
-/* The same launch with the learning rates and step counts ON THE DEVICE: nothing the update depends on is baked into the
- * call, so it can be captured in a HIP graph (torch.cuda.graphs around a whole training iteration) and replayed while the
- * schedule moves the learning rates.  tensors[c].lr / .step are ignored; lr[c] (device, double: the Python float the
- * reference's scheduler computes, scene/gaussian_model.py:294-310) and step[c] (device, fp32 count of updates DONE, as
- * torch's capturable Adam keeps it) are read by a one-workgroup kernel in front of the update, which adds 1 to every
- * step[c] and derives lr / (1 - beta1^t) and sqrt(1 - beta2^t) in double precision, rounded to fp32 once -- the factors
- * gft_adam_step_multi forms on the host, to the rounding of the device's double pow -- into factors[2 c], factors[2 c + 1]
- * (device scratch, 2 * count floats).
- * lr and step are given per tensor (arrays of device pointers, host) because optimizer state is edited tensor by tensor
- * (scene/gaussian_model.py:456-540). */
-int gft_adam_step_multi_dev(void* hip_stream, int32_t count, const gft_adam_tensor* tensors /*host*/,
-                            const double* const* lr /*host array of device pointers*/, float* const* step /*host array of device pointers*/,
-                            float* factors /*device, 2 * count floats*/, double beta1, double beta2, double eps, double weight_decay);
-
-/* The row-masked update with the learning rates and step counts on the device: gft_adam_step_rows behind the tick of
- * gft_adam_step_multi_dev (lr, step, factors as there; every count advances, one per tensor, whatever the mask holds).
- * row_mask is read when the kernel runs: a replayed graph follows the mask's contents of that replay.  rows > 0.
- * grad_scale: see below; NULL = none. */
-int gft_adam_step_rows_dev(void* hip_stream, int32_t count, const gft_adam_tensor* tensors /*host*/, int64_t rows,
-                           const uint8_t* row_mask, const double* const* lr /*host array of device pointers*/,
-                           float* const* step /*host array of device pointers*/, float* factors /*device, 2 * count floats*/,
-                           double beta1, double beta2, double eps, double weight_decay, const float* grad_scale /*device or NULL*/);
+/* The step.  Hyper-parameters as torch holds them (Python floats = double); derived factors (1 - beta, lr / (1 - beta1^t),
+ * sqrt(1 - beta2^t)) are formed in double precision and rounded to fp32 once, as torch does.  Three optional inputs:
+ *
+ * row_mask, rows -- opt-in, NOT the reference's optimizer (which is dense): the update restricted to the rows of a mask, SURVEY
+ *   section 8(f) row 4, "sparse Adam on visible Gaussians".  Every tensor has `rows` rows (n = rows x floats per row); row r takes
+ *   the step when row_mask[r] != 0 (device pointer, one byte per row: e.g. `radii > 0` of the iteration's render, reference
+ *   train.py:181 `visibility_filter`); the other rows' parameter and moments are left as they are (their moments do not decay).
+ *   16-byte groups without a masked-in element are neither read nor written.  The mask is read when the kernel runs: a replayed
+ *   graph follows the mask's contents of that replay.  With the learning rates in the table rows == 0 is a call with nothing to
+ *   do; with them on the device rows must be > 0 (every count would advance with nothing to update).
+ *
+ * lr, step, factors -- the learning rates and step counts ON THE DEVICE: nothing the update depends on is baked into the call,
+ *   so it can be captured in a HIP graph (torch.cuda.graphs around a whole training iteration) and replayed while the schedule
+ *   moves the learning rates.  tensors[c].lr / .step are ignored; lr[c] (device, double: the Python float the reference's
+ *   scheduler computes, scene/gaussian_model.py:294-310) and step[c] (device, fp32 count of updates DONE, as torch's capturable
+ *   Adam keeps it) are read by a one-workgroup kernel in front of the update, which adds 1 to every step[c] -- one per tensor,
+ *   empty ones included, whatever a mask holds -- and derives lr / (1 - beta1^t) and sqrt(1 - beta2^t) in double precision,
+ *   rounded to fp32 once -- the factors the host forms otherwise, to the rounding of the device's double pow -- into
+ *   factors[2 c], factors[2 c + 1] (device scratch, 2 * count floats).  lr and step are host arrays of device pointers, one per
+ *   tensor, because optimizer state is edited tensor by tensor (scene/gaussian_model.py:456-540).
+ *
+ * grad_scale -- device pointer to one float, e.g. out + 1 of gft_grad_norm below: every gradient value is multiplied by
+ *   *grad_scale, rounded to fp32, before anything else -- the update equals the one without it on gradients scaled by
+ *   gft_grad_scale, bit for bit -- and the gradient memory is not written. */
+int gft_adam_step(void* hip_stream, int32_t count, const gft_adam_tensor* tensors /*host*/,
+                  int64_t rows, const uint8_t* row_mask      /* NULL: dense step, rows must be 0 */,
+                  const double* const* lr, float* const* step, float* factors
+                                                             /* all NULL: lr / step of the table (host);
+                                                                all given: on the device, tick in front */,
+                  double beta1, double beta2, double eps, double weight_decay,
+                  const float* grad_scale                    /* device or NULL */);
 
 /* ---- gradient-norm clipping: torch.nn.utils.clip_grad_norm_(parameters, max_norm) with the L2 norm (reference train.py:468).
  *
@@ -99,20 +91,6 @@ int gft_grad_norm(void* hip_stream, int32_t count, const float* const* grads /*h
  * *coef == 1, the values being the same. */
 int gft_grad_scale(void* hip_stream, int32_t count, float* const* grads /*host array of device pointers*/,
                    const int64_t* n /*host*/, const float* coef /*device*/);
-
-/* The three Adam launches with the gradient scale read from the device (grad_scale: device pointer to one float, e.g.
- * out + 1 of gft_grad_norm; NULL = the functions above): every gradient value is multiplied by *grad_scale, rounded to fp32,
- * before anything else -- the update equals the one of the functions above on gradients scaled by gft_grad_scale, bit for
- * bit -- and the gradient memory is not written. */
-int gft_adam_step_multi_clip(void* hip_stream, int32_t count, const gft_adam_tensor* tensors /*host*/, double beta1,
-                             double beta2, double eps, double weight_decay, const float* grad_scale /*device or NULL*/);
-int gft_adam_step_rows_clip(void* hip_stream, int32_t count, const gft_adam_tensor* tensors /*host*/, int64_t rows,
-                            const uint8_t* row_mask, double beta1, double beta2, double eps, double weight_decay,
-                            const float* grad_scale /*device or NULL*/);
-int gft_adam_step_multi_dev_clip(void* hip_stream, int32_t count, const gft_adam_tensor* tensors /*host*/,
-                                 const double* const* lr /*host array of device pointers*/, float* const* step /*host array of device pointers*/,
-                                 float* factors /*device, 2 * count floats*/, double beta1, double beta2, double eps, double weight_decay,
-                                 const float* grad_scale /*device or NULL*/);
 
 #ifdef __cplusplus
 }

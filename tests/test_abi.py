@@ -56,9 +56,10 @@ def test_header_is_plain_c_and_matches_ctypes(tmp_path, lib):
               "gft_assemble_io": _lib.ASSEMBLE_FIELDS, "gft_assemble_bwd_io": _lib.ASSEMBLE_BWD_FIELDS,
               "gft_deform_params": _lib.DEFORM_FIELDS, "gft_deform_grads": _lib.DEFORM_FIELDS,
               "gft_forward_hints": [f[0] for f in _lib.ForwardHints._fields_],
-              "gft_forward_report": [f[0] for f in _lib.ForwardReport._fields_]}
+              "gft_forward_report": [f[0] for f in _lib.ForwardReport._fields_],
+              "gft_adam_tensor": [f[0] for f in _lib.AdamTensor._fields_]}
     body = ['#include <stdio.h>', '#include <stddef.h>', '#include "gftorf_rast.h"', '#include "gftorf_assemble.h"',
-            '#include "gftorf_deform.h"', 'int main(void){']
+            '#include "gftorf_deform.h"', '#include "gftorf_optim.h"', 'int main(void){']
     for s, fl in fields.items():
         body.append('printf("%s %%zu\\n", sizeof(%s));' % (s, s))
         for f in fl:
@@ -72,7 +73,7 @@ def test_header_is_plain_c_and_matches_ctypes(tmp_path, lib):
                "gft_layout": _lib.Layout, "gft_profile": _lib.Profile,
                "gft_assemble_io": _lib.AssembleIO, "gft_assemble_bwd_io": _lib.AssembleBwdIO,
                "gft_deform_params": _lib.DeformParams, "gft_deform_grads": _lib.DeformParams,
-               "gft_forward_hints": _lib.ForwardHints, "gft_forward_report": _lib.ForwardReport}
+               "gft_forward_hints": _lib.ForwardHints, "gft_forward_report": _lib.ForwardReport, "gft_adam_tensor": _lib.AdamTensor}
     for s, cls in mirrors.items():
         assert int(out[s]) == C.sizeof(cls), s
         for f in fields[s]:

@@ -173,7 +173,7 @@ def test_header_is_plain_c_and_every_symbol_is_exported(tmp_path, lib):
     exe = tmp_path / "flow_abi"
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
                            "-c", str(prog), "-o", str(exe) + ".o"])
-    assert lib.gft_abi_version() == _lib.ABI_VERSION == 15
+    assert lib.gft_abi_version() == _lib.ABI_VERSION == 16
 
 
 def test_size_query_and_argument_errors(lib):

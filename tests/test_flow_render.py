@@ -43,7 +43,7 @@ def test_header_is_plain_c_and_every_symbol_is_exported(tmp_path, lib):
                                'printf("%d\\n", (int)(sizeof(f) / sizeof(f[0]))); return 0;}']))
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
                            "-c", str(prog), "-o", str(tmp_path / "features_abi.o")])
-    assert lib.gft_abi_version() == _lib.ABI_VERSION == 15
+    assert lib.gft_abi_version() == _lib.ABI_VERSION == 16
 
 
 def test_argument_errors_of_the_c_entry_points(lib):

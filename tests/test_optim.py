@@ -1,5 +1,7 @@
 """FusedAdam (optimizer part) against torch.optim.Adam, the optimizer the
 reference uses (scene/gaussian_model.py:274)."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -206,6 +208,107 @@ def test_capturable_adam_equals_the_eager_one_and_replays(gpu):
         assert float(eager.state[pe]["step"]) == float(cap.state[pc]["step"]) == 6.0
         assert torch.equal(pe, pc), ge["name"]
         assert torch.equal(eager.state[pe]["exp_avg_sq"], cap.state[pc]["exp_avg_sq"])
+
+
+# ---- a table that crosses GFT_ADAM_MAX_TENSORS (40): 43 one-tensor groups, every one with its own learning rate, so a tensor
+# that reads another one's factors, or a second launch that starts at the wrong entry, gives wrong values ------------------------
+WIDE_SIZES = [0, 1, 3, 4, 5, 7, 8, 255, 256, 257, 1025, 2053]      # empty; tails of 1..3; 2053 floats = 513 16-byte groups: two
+                                                                    # workgroups of the dense kernel (256 threads x 2 groups)
+WIDE_ROWS = 37
+WIDE_ROW_FLOATS = {5: 1, 17: 3, 29: 4, 41: 45}      # entry of the table -> floats per row of the per-row tensor there (entry 41 is
+                                                    # in the second launch; 37 x 45 floats = 416 groups: two workgroups of the
+                                                    # row kernel, 256 groups each)
+
+
+def wide_groups(dev):
+    gen = torch.Generator().manual_seed(11)
+    out, dense = [], 0
+    for i in range(43):
+        if i in WIDE_ROW_FLOATS:
+            shape = (WIDE_ROWS, WIDE_ROW_FLOATS[i])
+        else:
+            shape = (WIDE_SIZES[dense % len(WIDE_SIZES)],)
+            dense += 1
+        out.append({"params": [torch.nn.Parameter(torch.randn(*shape, generator=gen).to(dev))], "lr": 1e-3 * (1 + i), "name": str(i)})
+    assert dense == 39
+    return out
+
+
+def wide_grads(it):
+    gen = torch.Generator().manual_seed(100 + it)
+    return [torch.randn(g["params"][0].shape, generator=gen) for g in wide_groups("cpu")]
+
+
+def wide_steps(opt, dev, **kw):
+    for it in range(3):
+        for grp, g in zip(opt.param_groups, wide_grads(it)):
+            grp["params"][0].grad = g.to(dev)
+        opt.step(**kw)
+    return opt
+
+
+@functools.lru_cache(maxsize=None)
+def wide_reference():
+    """torch.optim.Adam on the CPU in fp32 (it steps the empty parameter too and advances its count); computed once, read only."""
+    return wide_steps(torch.optim.Adam(wide_groups("cpu"), lr=0.0, eps=1e-15), "cpu")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("capturable", [False, True])
+def test_table_longer_than_one_launch(capturable, gpu):
+    """43 tensors in one bucket: two launches (40 + 3), the second with its own tick and its own slice of the factors.  Dense:
+    three steps against torch.optim.Adam under the tolerance of test_fused_adam_vs_torch_adam, step counts equal, the empty
+    tensor's included.  With a visibility mask over the four per-row tensors: selected rows equal the dense twin's step bit
+    for bit, the other rows keep parameter and moments (as test_step_on_visible_rows_only asserts it), everything else takes
+    the dense step."""
+    from gftorf_amd import FusedAdam
+    ref = wide_reference()
+    got = wide_steps(FusedAdam(wide_groups(gpu), lr=0.0, eps=1e-15, capturable=capturable), gpu)
+    assert len(got.param_groups) == 43
+    for gr, gg in zip(ref.param_groups, got.param_groups):
+        pr, pg = gr["params"][0], gg["params"][0]
+        sr, sg = ref.state[pr], got.state[pg]
+        assert float(sr["step"]) == float(sg["step"]) == 3.0, gr["name"]
+        assert sg["step"].is_cuda == capturable
+        for name, a, b in (("param", pr, pg), ("exp_avg", sr["exp_avg"], sg["exp_avg"]), ("exp_avg_sq", sr["exp_avg_sq"], sg["exp_avg_sq"])):
+            ref_np = a.detach().numpy()
+            assert b.shape == a.shape
+            if ref_np.size:
+                np.testing.assert_allclose(b.detach().cpu().numpy(), ref_np, rtol=3e-6, atol=3e-7 * float(np.abs(ref_np).max()),
+                                           err_msg="%s of group %s" % (name, gr["name"]))
+    # ---- the row-masked step: the four per-row tensors in one launch, the other 39 in another
+    vis = (torch.rand(WIDE_ROWS, generator=torch.Generator().manual_seed(99)) < 0.5).to(gpu)
+    assert 0 < int(vis.sum()) < WIDE_ROWS
+    dense, rows = (FusedAdam(wide_groups(gpu), lr=0.0, eps=1e-15, capturable=capturable) for _ in range(2))
+    row_params = [rows.param_groups[i]["params"][0] for i in WIDE_ROW_FLOATS]
+    for it in range(3):
+        for gd, gr, g in zip(dense.param_groups, rows.param_groups, wide_grads(it)):
+            pd, pr = gd["params"][0], gr["params"][0]
+            pd.grad = g.to(gpu)
+            pr.grad = pd.grad.clone()
+            # the dense optimizer starts every step from the row-wise one's state: one step is compared at a time
+            pd.data.copy_(pr.data)
+            if pr in rows.state:
+                for k in ("step", "exp_avg", "exp_avg_sq"):
+                    dense.state[pd][k].copy_(rows.state[pr][k])
+        old = [(p.detach().clone(),
+                rows.state[p]["exp_avg"].clone() if p in rows.state else torch.zeros_like(p),
+                rows.state[p]["exp_avg_sq"].clone() if p in rows.state else torch.zeros_like(p))
+               for p in (g["params"][0] for g in rows.param_groups)]
+        dense.step()
+        rows.step(visibility=vis, row_params=row_params)
+        for i, ((p0, m0, v0), gd, gr) in enumerate(zip(old, dense.param_groups, rows.param_groups)):
+            pd, pr = gd["params"][0], gr["params"][0]
+            sd, sr = dense.state[pd], rows.state[pr]
+            assert float(sd["step"]) == float(sr["step"]) == it + 1, gr["name"]
+            if i in WIDE_ROW_FLOATS:
+                sel = vis.view(-1, 1)
+                want = (torch.where(sel, pd.detach(), p0), torch.where(sel, sd["exp_avg"], m0), torch.where(sel, sd["exp_avg_sq"], v0))
+                assert not torch.equal(pr.detach(), p0) and torch.equal(pr.detach()[~vis], p0[~vis])
+            else:
+                want = (pd.detach(), sd["exp_avg"], sd["exp_avg_sq"])
+            for name, w, g in zip(("param", "exp_avg", "exp_avg_sq"), want, (pr.detach(), sr["exp_avg"], sr["exp_avg_sq"])):
+                assert torch.equal(w.view(torch.int32), g.view(torch.int32)), "%s of group %s, step %d" % (name, gr["name"], it)
 
 
 # ---- densification re-keys the parameters: the reference replaces each nn.Parameter and hands the SAME state dict to the new

@@ -52,30 +52,33 @@ def test_new_entry_points_report_argument_errors_and_take_empty_tables(lib):
     tab = (_lib.AdamTensor * 1)()
     ptrs, ns = (C.c_void_p * 1)(), (C.c_int64 * 1)(4)
     dev = C.c_void_p(256)        # stands for a device pointer: no call below gets as far as a launch
-    # name -> (arguments with `count` as a hole, the same with the host tables NULL)
+    # name -> (arguments with `count` as a hole, the same with the host tables NULL).  gft_adam_step is one function: its four
+    # argument shapes (dense / rows x learning rates in the table / on the device, each with a grad_scale) are named after it
+    adam = lambda rows, mask, dev_rates: lambda n, t: (
+        None, n, tab if t else None, rows, mask, ptrs if dev_rates and t else None, ptrs if dev_rates and t else None,
+        dev if dev_rates else None, 0.9, 0.999, 1e-8, 0.0, dev)
     calls = {
         "gft_grad_norm": lambda n, t: (None, n, ptrs if t else None, ns if t else None, 1.0, dev, 64, dev),
         "gft_grad_scale": lambda n, t: (None, n, ptrs if t else None, ns if t else None, dev),
-        "gft_adam_step_multi_clip": lambda n, t: (None, n, tab if t else None, 0.9, 0.999, 1e-8, 0.0, dev),
-        "gft_adam_step_rows_clip": lambda n, t: (None, n, tab if t else None, 5, dev, 0.9, 0.999, 1e-8, 0.0, dev),
-        "gft_adam_step_multi_dev_clip": lambda n, t: (None, n, tab if t else None, ptrs if t else None, ptrs if t else None, dev,
-                                                      0.9, 0.999, 1e-8, 0.0, dev),
-        "gft_adam_step_rows_dev": lambda n, t: (None, n, tab if t else None, 5, dev, ptrs if t else None, ptrs if t else None, dev,
-                                                0.9, 0.999, 1e-8, 0.0, dev),
+        "gft_adam_step dense host": adam(0, None, False),
+        "gft_adam_step rows host": adam(5, dev, False),
+        "gft_adam_step dense device": adam(0, None, True),
+        "gft_adam_step rows device": adam(5, dev, True),
     }
-    for name, args in calls.items():
+    for what, args in calls.items():
+        name = what.split()[0]
         fn = getattr(lib, name)
-        assert fn(*args(-1, True)) != 0, name
-        assert (name + ":") in _lib.last_error() and "count < 0" in _lib.last_error(), (name, _lib.last_error())
-        assert fn(*args(1, False)) != 0, name
-        assert (name + ":") in _lib.last_error() and "NULL" in _lib.last_error(), (name, _lib.last_error())
+        assert fn(*args(-1, True)) != 0, what
+        assert (name + ":") in _lib.last_error() and "count < 0" in _lib.last_error(), (what, _lib.last_error())
+        assert fn(*args(1, False)) != 0, what
+        assert (name + ":") in _lib.last_error() and "NULL" in _lib.last_error(), (what, _lib.last_error())
     # nothing to do: 0, and no device is touched (this test runs without one).  gft_grad_norm with an `out` has {0, 1} to
     # write, so "nothing to do" is count == 0 with out == NULL
-    for name, args in calls.items():
+    for what, args in calls.items():
         a = list(args(0, True))
-        if name == "gft_grad_norm":
+        if what == "gft_grad_norm":
             a[-1] = None
-        assert getattr(lib, name)(*a) == 0, name
+        assert getattr(lib, what.split()[0])(*a) == 0, what
     # the per-span checks come before any launch as well
     bad = (C.c_int64 * 1)(-4)
     assert lib.gft_grad_norm(None, 1, ptrs, bad, 1.0, dev, 64, dev) != 0 and "gft_grad_norm: span 0 has n < 0" in _lib.last_error()
@@ -85,8 +88,13 @@ def test_new_entry_points_report_argument_errors_and_take_empty_tables(lib):
     ok = (C.c_void_p * 1)(260)
     assert lib.gft_grad_norm(None, 1, ok, ns, 1.0, dev, 0, dev) != 0 and "scratch" in _lib.last_error()
     assert lib.gft_grad_norm(None, 1, ok, ns, 1.0, dev, 64, None) != 0 and "out is NULL" in _lib.last_error()
-    assert lib.gft_adam_step_rows_dev(None, 1, tab, 0, dev, ptrs, ptrs, dev, 0.9, 0.999, 1e-8, 0.0, None) != 0
-    assert "rows must be > 0" in _lib.last_error()
+    assert lib.gft_adam_step(None, 1, tab, 0, dev, ptrs, ptrs, dev, 0.9, 0.999, 1e-8, 0.0, None) != 0
+    assert "gft_adam_step:" in _lib.last_error() and "rows must be > 0" in _lib.last_error()
+    # what one function for all of them can be handed that the eight could not: rows without a mask, half of the device rates
+    assert lib.gft_adam_step(None, 1, tab, 5, None, None, None, None, 0.9, 0.999, 1e-8, 0.0, None) != 0
+    assert "gft_adam_step:" in _lib.last_error() and "row_mask" in _lib.last_error()
+    assert lib.gft_adam_step(None, 1, tab, 0, None, ptrs, None, dev, 0.9, 0.999, 1e-8, 0.0, None) != 0
+    assert "gft_adam_step:" in _lib.last_error() and "NULL" in _lib.last_error()
     # the size query: host only, one double per workgroup of 4096 elements and at most one more per span
     q = lib.gft_grad_norm_scratch_bytes
     assert q(0, 0) == 8 and q(-1, 0) == 0 and q(0, -1) == 0
@@ -289,14 +297,19 @@ def _assert_same_state(a, b, what=""):
                 assert torch.equal(bits(sa[k]), bits(sb[k])), "%s of group %s %s" % (k, ga["name"], what)
 
 
+# (one list, so that the cases with the rates in the call keep the names they had before there was a `capturable`)
+CLIP_STEP_CASES = [pytest.param(wd, frac, cap, id="%s-%s%s" % (wd, frac, "-capturable" if cap else ""))
+                   for wd in (0.0, 0.01) for frac in (None, 0.14, 1.0) for cap in (False, True)]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("frac", [None, 0.14, 1.0])
-@pytest.mark.parametrize("wd", [0.0, 0.01])
-def test_fused_step_equals_clip_then_step(wd, frac, gpu):
+@pytest.mark.parametrize("wd,frac,capturable", CLIP_STEP_CASES)
+def test_fused_step_equals_clip_then_step(wd, frac, capturable, gpu):
     """`step(max_grad_norm=1.0)` against `clip_grad_norm_(all parameters, 1.0); step()`: parameters, both moments and step counts
-    bit for bit, `.grad` untouched, `last_grad_norm` the drop-in's norm -- dense and with a visibility mask."""
+    bit for bit, `.grad` untouched, `last_grad_norm` the drop-in's norm -- dense and with a visibility mask, with the learning
+    rates and step counts in the call and on the device (capturable: every step here is an eager one, the first included)."""
     import gftorf_amd
-    a, b = _twins(gpu, 2, wd)
+    a, b = _twins(gpu, 2, wd, capturable=capturable)
     vis = None if frac is None else (torch.rand(1001, generator=torch.Generator().manual_seed(99)) < frac).to(gpu)
     gen = torch.Generator().manual_seed(123)
     assert b.last_grad_norm is None

@@ -180,7 +180,7 @@ def test_header_is_plain_c_and_every_symbol_is_exported(tmp_path, lib):
                                   text=True)
     consts = [int(v) for v in out.split("REG_WORDS_ARE", 1)[1].split()]
     assert consts == [_lib.REG_PARTIAL_WORDS, _lib.REG_MEANS, _lib.REG_COUNTS, _lib.REG_RECIPS, _lib.REG_TOTAL]
-    assert lib.gft_abi_version() == _lib.ABI_VERSION == 15
+    assert lib.gft_abi_version() == _lib.ABI_VERSION == 16
     assert lib.gft_reg_result_words() > _lib.REG_TOTAL
 
 
