@@ -16,6 +16,7 @@ from . import densify  # noqa: F401
 from . import loss  # noqa: F401
 from . import flow  # noqa: F401
 from . import reg  # noqa: F401
+from . import tof  # noqa: F401
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "GaussianRasterizerPair", "render_pair", "assemble_inputs", "assemble_parameters", "distCUDA2", "FusedAdam", "clip_grad_norm_",
            "DeformNetwork", "REFERENCE_ARCH", "reference_network", "densify"]

@@ -158,6 +158,15 @@ FEATURE_EXPORTS = ["gft_render_features", "gft_render_features_backward"]
 REG_EXPORTS = ["gft_reg_blocks", "gft_reg_result_words", "gft_reg_forward", "gft_reg_backward"]
 REG_PARTIAL_WORDS = 8           # GFT_REG_PARTIAL_WORDS
 REG_MEANS, REG_COUNTS, REG_RECIPS, REG_TOTAL = 0, 4, 6, 10      # GFT_REG_*: words of the result block
+# include/gftorf_tof.h (the ToF depth and the training log's scalars; no struct, so the ABI version is unchanged)
+TOF_EXPORTS = ["gft_tof_depth", "gft_tof_log_blocks", "gft_tof_log_row"]
+TOF_PARTIAL_WORDS = 12          # GFT_TOF_PARTIAL_WORDS
+TOF_LOG_WORDS, TOF_LOG_MAX_EXTRAS = 24, 8                       # GFT_TOF_LOG_WORDS, GFT_TOF_LOG_MAX_EXTRAS
+# GFT_TOF_LOG_*: the float words of a row in order, then the uint32 words and the extras
+TOF_LOG_FLOATS = ("sp", "sp_tof", "gsp", "sp_err", "sp_tof_err", "depth_err", "tof_depth_err", "amp_err", "dd", "gs_sp",
+                  "gs_sp_visible")
+TOF_LOG_VISIBLE, TOF_LOG_PRESENT, TOF_LOG_NUM_EXTRAS, TOF_LOG_SEQ, TOF_LOG_EXTRAS = 11, 12, 13, 14, 16
+TOF_HAS_GT_DEPTH, TOF_HAS_DD, TOF_HAS_AMP, TOF_HAS_VISIBLE = 1, 2, 4, 8
 
 
 def load():
@@ -290,6 +299,18 @@ def load():
     lib.gft_reg_forward.argtypes = _reg_inputs + [C.c_void_p] + _reg_weights + [C.c_void_p, C.c_void_p]
     lib.gft_reg_backward.restype = C.c_int
     lib.gft_reg_backward.argtypes = _reg_inputs + _reg_weights + [C.c_void_p] * 6
+    # stream, pixels, tof, plane_stride, depth_range_dev, depth_range, phase_offset_dev, phase_offset, out
+    lib.gft_tof_depth.restype = C.c_int
+    lib.gft_tof_depth.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_float, C.c_void_p]
+    lib.gft_tof_log_blocks.restype = C.c_int64
+    lib.gft_tof_log_blocks.argtypes = [C.c_int64, C.c_int64]
+    # stream, pixels, P, phasor, stride, depth, gt_phasor, stride, depth_range_dev, depth_range, phase_offset_dev, phase_offset,
+    # tof_multiplier, gt_depth, depth_distortion, amp, amp_stride, visible, visible_is_radii, extras, num_extras, partials, rows,
+    # slots, cursor
+    lib.gft_tof_log_row.restype = C.c_int
+    lib.gft_tof_log_row.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                    C.c_float, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                    C.c_int32, _ptrs, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     lib.gft_densify_stats.restype = C.c_int
     lib.gft_densify_stats.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8
     lib.gft_rows_rank_scratch_bytes.restype = C.c_size_t
