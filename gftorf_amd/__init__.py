@@ -17,6 +17,9 @@ from . import loss  # noqa: F401
 from . import flow  # noqa: F401
 from . import reg  # noqa: F401
 from . import tof  # noqa: F401
+from . import query  # noqa: F401
+from .query import DeformQuery, ftorf_schedule, query_dmlp  # noqa: F401
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "GaussianRasterizerPair", "render_pair", "assemble_inputs", "assemble_parameters", "distCUDA2", "FusedAdam", "clip_grad_norm_",
-           "DeformNetwork", "REFERENCE_ARCH", "reference_network", "densify"]
+           "DeformNetwork", "REFERENCE_ARCH", "reference_network", "densify",
+           "DeformQuery", "ftorf_schedule", "query_dmlp"]

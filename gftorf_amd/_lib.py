@@ -167,6 +167,9 @@ TOF_LOG_FLOATS = ("sp", "sp_tof", "gsp", "sp_err", "sp_tof_err", "depth_err", "t
                   "gs_sp_visible")
 TOF_LOG_VISIBLE, TOF_LOG_PRESENT, TOF_LOG_NUM_EXTRAS, TOF_LOG_SEQ, TOF_LOG_EXTRAS = 11, 12, 13, 14, 16
 TOF_HAS_GT_DEPTH, TOF_HAS_DD, TOF_HAS_AMP, TOF_HAS_VISIBLE = 1, 2, 4, 8
+# include/gftorf_query.h (an iteration's deformation queries as one batch; no struct, so the ABI version is unchanged)
+QUERY_EXPORTS = ["gft_query_inputs", "gft_query_combine", "gft_query_combine_backward"]
+QUERY_MAX_TIMES, QUERY_MAX_OUTPUTS = 4, 4                       # GFT_QUERY_MAX_TIMES, GFT_QUERY_MAX_OUTPUTS
 
 
 def load():
@@ -311,6 +314,16 @@ def load():
     lib.gft_tof_log_row.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                     C.c_float, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                     C.c_int32, _ptrs, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    # stream, P, xyz, mask, rank, count_dev, n, K, scale, times_dev, times_host, x, t
+    lib.gft_query_inputs.restype = C.c_int
+    lib.gft_query_inputs.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float,
+                                     C.c_void_p, C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
+    # stream, n, K, M, d / g_out, coeffs_dev, coeffs_host, out / g_d
+    lib.gft_query_combine.restype = C.c_int
+    lib.gft_query_combine.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), _ptrs]
+    lib.gft_query_combine_backward.restype = C.c_int
+    lib.gft_query_combine_backward.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, _ptrs, C.c_void_p, C.POINTER(C.c_float),
+                                               C.c_void_p]
     lib.gft_densify_stats.restype = C.c_int
     lib.gft_densify_stats.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8
     lib.gft_rows_rank_scratch_bytes.restype = C.c_size_t
