@@ -170,6 +170,14 @@ TOF_HAS_GT_DEPTH, TOF_HAS_DD, TOF_HAS_AMP, TOF_HAS_VISIBLE = 1, 2, 4, 8
 # include/gftorf_query.h (an iteration's deformation queries as one batch; no struct, so the ABI version is unchanged)
 QUERY_EXPORTS = ["gft_query_inputs", "gft_query_combine", "gft_query_combine_backward"]
 QUERY_MAX_TIMES, QUERY_MAX_OUTPUTS = 4, 4                       # GFT_QUERY_MAX_TIMES, GFT_QUERY_MAX_OUTPUTS
+# include/gftorf_metrics.h (a view's evaluation metrics; no struct, so the ABI version is unchanged)
+METRICS_EXPORTS = ["gft_metrics_blocks", "gft_view_metrics", "gft_metrics_reset"]
+# GFT_METRICS_*: the eight values in the order of a row's first floats and of the accumulator's doubles
+METRICS_VALUES = ("l1", "psnr", "l1_p", "l2_p", "psnr_p", "l1_d", "l2_d", "l2_d_tof")
+METRICS_MAX_PLANES, METRICS_PARTIAL_WORDS = 8, 36               # GFT_METRICS_MAX_PLANES, GFT_METRICS_PARTIAL_WORDS
+METRICS_ROW_MSE, METRICS_ROW_PSNR, METRICS_ROW_PRESENT, METRICS_ROW_PLANES, METRICS_ROW_WORDS = 8, 16, 24, 25, 28
+METRICS_ACC_SUMS, METRICS_ACC_VIEWS, METRICS_ACC_PRESENT, METRICS_ACC_WORDS = 0, 16, 17, 18
+METRICS_HAS_COLOUR, METRICS_HAS_TOF, METRICS_HAS_DEPTH, METRICS_HAS_TOF_DEPTH = 1, 2, 4, 8
 
 
 def load():
@@ -324,6 +332,16 @@ def load():
     lib.gft_query_combine_backward.restype = C.c_int
     lib.gft_query_combine_backward.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, _ptrs, C.c_void_p, C.POINTER(C.c_float),
                                                C.c_void_p]
+    lib.gft_metrics_blocks.restype = C.c_int64
+    lib.gft_metrics_blocks.argtypes = [C.c_int64]
+    # stream, pixels_a, channels_a, image, stride, gt_image, stride, pixels_b, channels_b, tof, stride, gt_tof, stride, depth,
+    # gt_depth, phasor, stride, depth_range_dev, depth_range, phase_offset_dev, phase_offset, partials, row, accum
+    lib.gft_view_metrics.restype = C.c_int
+    lib.gft_view_metrics.argtypes = ([C.c_void_p] + [C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] * 2 +
+                                     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_float,
+                                      C.c_void_p, C.c_void_p, C.c_void_p])
+    lib.gft_metrics_reset.restype = C.c_int
+    lib.gft_metrics_reset.argtypes = [C.c_void_p, C.c_void_p]
     lib.gft_densify_stats.restype = C.c_int
     lib.gft_densify_stats.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8
     lib.gft_rows_rank_scratch_bytes.restype = C.c_size_t

@@ -1,0 +1,16 @@
+// gft_tof_depth.h -- the ToF depth of scene/torf_utils.py:59-64 as one device function, shared by k_tof.hip (gft_tof_depth,
+// the training log) and k_metrics.hip (the evaluation's l2_d_tof): both must form the same bits from the same phasor.
+#pragma once
+#include <hip/hip_runtime.h>
+
+constexpr float TOF_TWO_PI = 6.283185307179586f, TOF_FOUR_PI = 12.566370614359172f, TOF_TINY = 1e-6f;
+
+// torf_utils.py:60-64 in fp32, in its order
+__device__ __forceinline__ float depth_from_tof(float re, float im, float depth_range, float phase_offset)
+{
+    const float real = fabsf(re) < TOF_TINY ? TOF_TINY : re;
+    float phase = atan2f(im, real);
+    phase -= phase_offset;
+    phase = phase < 0.f ? phase + TOF_TWO_PI : phase;
+    return phase * depth_range / TOF_FOUR_PI;
+}

@@ -6,12 +6,12 @@
 // scalar loads only (a pixel's nine loads are each coalesced across the wave; the pass moves 36 bytes per pixel, and per
 // Gaussian one float amp_stride floats from the last one's plus its visibility).
 #include "gft_internal.h"
+#include "gft_tof_depth.h"
 #include "gftorf_tof.h"
 
 namespace {
 
 constexpr int TOF_THREADS = 256, TOF_MAX_BLOCKS = 1024, TOF_SUMS = 11;
-constexpr float TOF_TWO_PI = 6.283185307179586f, TOF_FOUR_PI = 12.566370614359172f, TOF_TINY = 1e-6f;
 constexpr float TOF_SH_C0 = 0.28209479177387814f;              // utils/sh_utils.py C0
 
 static_assert(GFT_TOF_PARTIAL_WORDS == TOF_SUMS + 1, "eleven sums and the visible count");
@@ -45,16 +45,6 @@ int64_t tof_blocks(int64_t total)
 {
     const int64_t b = (total + TOF_THREADS - 1) / TOF_THREADS;
     return b < 1 ? 1 : (b > TOF_MAX_BLOCKS ? TOF_MAX_BLOCKS : b);
-}
-
-// torf_utils.py:60-64 in fp32, in its order
-__device__ __forceinline__ float depth_from_tof(float re, float im, float depth_range, float phase_offset)
-{
-    const float real = fabsf(re) < TOF_TINY ? TOF_TINY : re;
-    float phase = atan2f(im, real);
-    phase -= phase_offset;
-    phase = phase < 0.f ? phase + TOF_TWO_PI : phase;
-    return phase * depth_range / TOF_FOUR_PI;
 }
 
 __global__ __launch_bounds__(TOF_THREADS) void k_tof_depth(int64_t pixels, const float* __restrict__ tof, int64_t plane_stride,
