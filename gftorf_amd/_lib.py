@@ -178,6 +178,18 @@ METRICS_MAX_PLANES, METRICS_PARTIAL_WORDS = 8, 36               # GFT_METRICS_MA
 METRICS_ROW_MSE, METRICS_ROW_PSNR, METRICS_ROW_PRESENT, METRICS_ROW_PLANES, METRICS_ROW_WORDS = 8, 16, 24, 25, 28
 METRICS_ACC_SUMS, METRICS_ACC_VIEWS, METRICS_ACC_PRESENT, METRICS_ACC_WORDS = 0, 16, 17, 18
 METRICS_HAS_COLOUR, METRICS_HAS_TOF, METRICS_HAS_DEPTH, METRICS_HAS_TOF_DEPTH = 1, 2, 4, 8
+# include/gftorf_present.h (a rendered view's display images; no struct, so the ABI version is unchanged)
+PRESENT_EXPORTS = ["gft_present_blocks", "gft_present_sheet_bytes", "gft_present_magma", "gft_present_view", "gft_present_ranges",
+                   "gft_present_ranges_reset"]
+# GFT_PRESENT_*: the images of a sheet in the order they lie in it: (name, bytes per pixel, numpy dtype, shape of an H x W view)
+PRESENT_IMAGES = (("color", 3, "uint8", lambda H, W: (H, W, 3)), ("real", 3, "uint8", lambda H, W: (H, W, 3)),
+                  ("imag", 3, "uint8", lambda H, W: (H, W, 3)), ("amp", 1, "uint8", lambda H, W: (H, W)),
+                  ("quad", 4, "uint8", lambda H, W: (4, H, W)), ("depth", 4, "uint8", lambda H, W: (H, W, 4)),
+                  ("depth_tof", 4, "uint8", lambda H, W: (H, W, 4)), ("depth_norm", 4, "uint8", lambda H, W: (H, W, 4)),
+                  ("dd", 1, "uint8", lambda H, W: (H, W)), ("depth_tof_f", 4, "float32", lambda H, W: (H, W)),
+                  ("depth_norm_f", 4, "float32", lambda H, W: (H, W)))
+PRESENT_HAS_COLOR, PRESENT_HAS_PHASOR, PRESENT_HAS_QUAD, PRESENT_HAS_DEPTH, PRESENT_HAS_ACC, PRESENT_HAS_DD = 1, 2, 4, 8, 16, 32
+PRESENT_ALIGN, PRESENT_PARTIAL_WORDS, PRESENT_RANGE_WORDS, PRESENT_MAGMA_ROWS = 16, 2, 6, 257      # GFT_PRESENT_*
 
 
 def load():
@@ -342,6 +354,22 @@ def load():
                                       C.c_void_p, C.c_void_p, C.c_void_p])
     lib.gft_metrics_reset.restype = C.c_int
     lib.gft_metrics_reset.argtypes = [C.c_void_p, C.c_void_p]
+    lib.gft_present_blocks.restype = C.c_int64
+    lib.gft_present_blocks.argtypes = [C.c_int64]
+    lib.gft_present_sheet_bytes.restype = C.c_int64
+    lib.gft_present_sheet_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
+    lib.gft_present_magma.restype = C.POINTER(C.c_uint8)
+    lib.gft_present_magma.argtypes = []
+    # stream, H, W, image, stride, phasor, stride, planes, depth, acc, dd, ranges_dev, ranges_host, depth_range_dev, depth_range,
+    # phase_offset_dev, phase_offset, znear, zfar, tof_multiplier, partials, sheet
+    lib.gft_present_view.restype = C.c_int
+    lib.gft_present_view.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_void_p, C.c_float, C.c_void_p, C.c_float,
+                                     C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
+    lib.gft_present_ranges.restype = C.c_int
+    lib.gft_present_ranges.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.gft_present_ranges_reset.restype = C.c_int
+    lib.gft_present_ranges_reset.argtypes = [C.c_void_p, C.c_void_p]
     lib.gft_densify_stats.restype = C.c_int
     lib.gft_densify_stats.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8
     lib.gft_rows_rank_scratch_bytes.restype = C.c_size_t

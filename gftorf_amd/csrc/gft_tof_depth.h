@@ -14,3 +14,14 @@ __device__ __forceinline__ float depth_from_tof(float re, float im, float depth_
     phase = phase < 0.f ? phase + TOF_TWO_PI : phase;
     return phase * depth_range / TOF_FOUR_PI;
 }
+
+// torf_utils.py:53-57, the numpy variant render.py uses (k_present.hip): no clamp of the real part; every step one fp32
+// operation of its own, the division correctly rounded
+__device__ __forceinline__ float depth_from_tof_np(float re, float im, float depth_range, float phase_offset)
+{
+#pragma clang fp contract(off)
+    float phase = atan2f(im, re);
+    phase = __fsub_rn(phase, phase_offset);
+    phase = phase < 0.f ? __fadd_rn(phase, TOF_TWO_PI) : phase;
+    return __fdiv_rn(__fmul_rn(phase, depth_range), TOF_FOUR_PI);
+}

@@ -1,0 +1,340 @@
+"""A rendered view's display images on the device (``csrc/k_present.hip``, ``include/gftorf_present.h``).
+
+The reference's render program (``render.py:105-189`` ``render_set``; ``:43-54`` ``save_input`` for the ground truth; the
+``pipe.debug`` block of ``train.py:287-378``) copies every rasterizer output of a view to the host as float32 -- over a dozen
+blocking ``.cpu()`` calls, about 130 bytes per pixel -- and forms the images it writes in numpy: ``phasor2real_img_amp``,
+``normalize_im_gt``, ``normalize_im``, ``depth_from_tof``, ``depth / acc``, ``cm.magma(1 - (d - znear) / (zfar - znear))`` and
+``to8b``.  Here:
+
+``view_images(...)``  the uint8 images of one view (and the two derived float depths) as views into one device buffer, the
+    sheet: at most two launches, no host read, no atomic, no memset; 27 bytes per pixel leave the device.
+``PhasorRanges``  ``save_input``'s ``np.min`` / ``np.max`` over the whole ground-truth sequence as six floats on the device.
+``ViewSheets``  pinned staging: ``submit`` enqueues ``view_images`` and the sheet's asynchronous copy, ``ready`` hands out the
+    finished views as numpy arrays, so the host encodes view i while view i + 1 renders.
+``zplanes(depth_range)``  the colour map's planes of ``render.py:54``.
+
+The uint8 images equal the reference's bit for bit wherever its float32 statements are IEEE operations; the one exception is
+``arctan2`` in ``depth_tof``, whose last bits may differ (see tests/test_present.py).  Nothing here has a gradient and there is
+no CPU path.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+
+IMAGES = tuple(name for name, _, _, _ in _lib.PRESENT_IMAGES)       # the keys, in the order the images lie in a sheet
+_EVERY = (_lib.PRESENT_HAS_COLOR | _lib.PRESENT_HAS_PHASOR | _lib.PRESENT_HAS_QUAD | _lib.PRESENT_HAS_DEPTH | _lib.PRESENT_HAS_ACC |
+          _lib.PRESENT_HAS_DD)
+
+
+def zplanes(depth_range):
+    """``(0.05 * r * 0.9, 0.55 * r * 1.1)`` evaluated in float32, as ``render.py:54`` does with the camera's 0-d float32
+    ``depth_range``: (znear, zfar) as Python floats."""
+    r = np.asarray(depth_range, dtype=np.float32).reshape(())
+    return float(0.05 * r * 0.9), float(0.55 * r * 1.1)
+
+
+def magma_table():
+    """``to8b(cm.magma(.))`` as the kernel holds it: uint8 [257, 4], rows 0..255 the map's entries, row 256 a NaN's colour"""
+    ptr = _lib.load().gft_present_magma()
+    return np.ctypeslib.as_array(ptr, shape=(_lib.PRESENT_MAGMA_ROWS, 4)).copy()
+
+
+def blocks(pixels):
+    """workgroups of a launch over an image of `pixels` = rows of its partials; 0 for no pixel"""
+    return int(_lib.load().gft_present_blocks(int(pixels)))
+
+
+def sheet_layout(H, W, groups):
+    """(bytes of the sheet, {image name: byte offset}) of an H x W view with the ``_lib.PRESENT_HAS_*`` groups `groups`"""
+    offsets = (C.c_int64 * len(IMAGES))()
+    total = int(_lib.load().gft_present_sheet_bytes(int(H), int(W), int(groups), offsets))
+    if total < 1:
+        raise ValueError("gftorf_amd.present: no sheet for H=%d W=%d groups=%d" % (H, W, groups))
+    return total, {name: int(offsets[k]) for k, name in enumerate(IMAGES) if offsets[k] >= 0}
+
+
+def _tensor(t, name):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("gftorf_amd.present: %s must be a tensor, got %s" % (name, type(t).__name__))
+    if t.dtype != torch.float32:
+        raise TypeError("gftorf_amd.present: %s must be torch.float32, got %s" % (name, t.dtype))
+    return t.detach()
+
+
+def _devices(named):
+    """Shapes and dtypes are checked first, then the devices: every tensor on the first one's HIP device."""
+    dev = named[0][0].device
+    for t, name in named:
+        if t.device.type != "cuda":
+            raise RuntimeError("gftorf_amd.present: %s is on %s; the display kernels run on a HIP device only, there is no CPU path"
+                               % (name, t.device))
+        if t.device != dev:
+            raise RuntimeError("gftorf_amd.present: %s is on %s, %s on %s" % (name, t.device, named[0][1], dev))
+    return dev
+
+
+def _planes(t, name, least, most, size=None):
+    """A [C, H, W] image (`least` <= C <= `most`) as (tensor, plane stride): taken in place when every plane is contiguous
+    -- ``phasor[:3]`` of the 7-plane tensor --, else copied.  `size` = ((H, W), the name of the input that set it)."""
+    t = _tensor(t, name)
+    if t.dim() != 3 or not least <= t.shape[0] <= most or t.shape[1] < 1 or t.shape[2] < 1:
+        want = "%d" % least if least == most else ("%d..%d" % (least, most) if most < 1 << 30 else ">=%d" % least)
+        raise RuntimeError("gftorf_amd.present: %s must be [%s, H, W], got %s" % (name, want, list(t.shape)))
+    H, W = int(t.shape[1]), int(t.shape[2])
+    if size is not None and (H, W) != size[0]:
+        raise RuntimeError("gftorf_amd.present: %s is %d x %d, %s %d x %d: the inputs of one call have one size"
+                           % ((name, H, W, size[1]) + size[0]))
+    if not ((W == 1 or t.stride(2) == 1) and (H == 1 or t.stride(1) == W) and (t.shape[0] == 1 or t.stride(0) >= 0)):
+        t = t.contiguous()
+    return t, (int(t.stride(0)) if t.shape[0] > 1 else 0)
+
+
+def _scalar(v, name, named):
+    """(tensor or None, float): a one-element float32 device tensor is passed by address, a number by value"""
+    if isinstance(v, torch.Tensor):
+        v = _tensor(v, name)
+        if v.numel() != 1:
+            raise RuntimeError("gftorf_amd.present: %s must be a number or a one-element tensor, got %s" % (name, list(v.shape)))
+        named.append((v, name))
+        return v, 0.0
+    return None, float(v)
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _views(sheet, offsets, H, W):
+    out = {}
+    for name, bpp, dtype, shape in _lib.PRESENT_IMAGES:
+        if name in offsets:
+            n = bpp * H * W
+            part = sheet[offsets[name]:offsets[name] + n]
+            out[name] = (part.view(torch.float32) if dtype == "float32" else part).view(shape(H, W))
+    return out
+
+
+def view_images(image=None, phasor=None, depth=None, acc=None, dd=None, *, ranges=None, zplanes=None, depth_range=None,
+                phase_offset=0.0, tof_multiplier=1.0, quad=None, out=None, _partials=None):
+    """The display images of one view, ``render.py:129-184``, as a dict of device tensors that are views into one uint8
+    buffer (the sheet; every image starts on a 16-byte boundary of it).  All inputs are float32 on one HIP device and share
+    one H x W; a group that is not given produces no key:
+
+    ``image`` [3, H, W]: ``color`` uint8 [H, W, 3].
+    ``phasor`` [>= 3, H, W] (planes read in place through their stride): ``real``, ``imag`` uint8 [H, W, 3] and ``amp`` uint8
+        [H, W], of the planes times ``tof_multiplier`` normalised by ``ranges``; ``depth_tof`` uint8 [H, W, 4] and
+        ``depth_tof_f`` float32 [H, W], numpy's ``depth_from_tof`` of planes 0 and 1 (not multiplied) with ``depth_range`` and
+        ``phase_offset``; with exactly 7 planes also ``quad`` uint8 [4, H, W] (``quad=True`` demands it, ``quad=False``
+        leaves it out).
+    ``depth`` [1, H, W]: ``depth`` uint8 [H, W, 4]; with ``acc`` [1, H, W] also ``depth_norm`` and ``depth_norm_f``.
+    ``dd`` [1, H, W]: ``dd`` uint8 [H, W], normalised by its own min and max.
+
+    ``ranges``: the (lo, hi) of ``real``, ``imag`` and ``amp``: six numbers, or a float32 device tensor [6] read when the
+    kernel runs (``PhasorRanges.tensor``).  ``zplanes`` = (znear, zfar) of the colour map, by value (``zplanes()``).
+    ``depth_range``, ``phase_offset``: a number, or a one-element float32 device tensor read when the kernel runs.
+    ``out``: a uint8 device tensor of at least the sheet's size, 16-byte aligned, to write into; else a new one.
+    Nothing is read on the host; the call can be captured in a graph."""
+    lib = _lib.load()
+    named, size = [], None
+
+    def take(t, name, least, most):
+        nonlocal size
+        t, stride = _planes(t, name, least, most, size)
+        if size is None:
+            size = ((int(t.shape[1]), int(t.shape[2])), name)
+        named.append((t, name))
+        return t, stride
+
+    im = ph = d = a = dist = None
+    im_stride = ph_stride = planes = 0
+    if image is not None:
+        im, im_stride = take(image, "image", 3, 3)
+    if phasor is not None:
+        ph, ph_stride = take(phasor, "phasor", 3, 1 << 30)
+        planes = int(ph.shape[0])
+    if quad and planes != 7:
+        raise RuntimeError("gftorf_amd.present: quad needs a phasor of exactly 7 planes, got %s"
+                           % ("none" if ph is None else list(ph.shape)))
+    if acc is not None and depth is None:
+        raise ValueError("gftorf_amd.present: acc is given without depth: depth_norm is depth / acc")
+    if depth is not None:
+        d = take(depth, "depth", 1, 1)[0]
+    if acc is not None:
+        a = take(acc, "acc", 1, 1)[0]
+    if dd is not None:
+        dist = take(dd, "dd", 1, 1)[0]
+    if not named:
+        raise ValueError("gftorf_amd.present: nothing to show: give image, phasor, depth or dd")
+    rg_t, rg_host, dr_t, po_t = None, None, None, None
+    dr = po = 0.0
+    if ph is not None:
+        if ranges is None:
+            raise ValueError("gftorf_amd.present: real, imag and amp of phasor need ranges")
+        if depth_range is None:
+            raise ValueError("gftorf_amd.present: the ToF depth of phasor needs depth_range")
+        if isinstance(ranges, torch.Tensor):
+            rg_t = _tensor(ranges, "ranges")
+            if tuple(rg_t.shape) != (6,) or not rg_t.is_contiguous():
+                raise RuntimeError("gftorf_amd.present: ranges must be six numbers or a contiguous tensor [6], got %s" % list(rg_t.shape))
+            named.append((rg_t, "ranges"))
+        else:
+            vals = [float(x) for x in np.asarray(ranges, dtype=np.float32).reshape(-1)]
+            if len(vals) != 6:
+                raise RuntimeError("gftorf_amd.present: ranges must be six numbers or a contiguous tensor [6], got %d numbers" % len(vals))
+            rg_host = (C.c_float * 6)(*vals)
+        dr_t, dr = _scalar(depth_range, "depth_range", named)
+        po_t, po = _scalar(phase_offset, "phase_offset", named)
+    znear = zfar = 0.0
+    if ph is not None or d is not None:
+        if zplanes is None:
+            raise ValueError("gftorf_amd.present: the colour map of a depth needs zplanes = (znear, zfar)")
+        znear, zfar = (float(z) for z in zplanes)
+    dev = _devices(named)
+    (H, W) = size[0]
+    groups = ((_lib.PRESENT_HAS_COLOR if im is not None else 0) | (_lib.PRESENT_HAS_PHASOR if ph is not None else 0) |
+              (_lib.PRESENT_HAS_QUAD if planes == 7 and quad is not False else 0) | (_lib.PRESENT_HAS_DEPTH if d is not None else 0) |
+              (_lib.PRESENT_HAS_ACC if a is not None else 0) | (_lib.PRESENT_HAS_DD if dist is not None else 0))
+    # the C call shows quad for exactly 7 planes: fewer are declared when quad is left out
+    planes_arg = 7 if groups & _lib.PRESENT_HAS_QUAD else min(planes, 3)
+    total, offsets = sheet_layout(H, W, groups)
+    if out is None:
+        out = torch.empty((total,), device=dev, dtype=torch.uint8)
+    else:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous():
+            raise TypeError("gftorf_amd.present: out must be a contiguous one-dimensional torch.uint8 tensor")
+        if out.device != dev:
+            raise RuntimeError("gftorf_amd.present: the images are on %s, out on %s" % (dev, out.device))
+        if out.numel() < total or out.data_ptr() % _lib.PRESENT_ALIGN:
+            raise RuntimeError("gftorf_amd.present: out has %d bytes at an address %s 16-byte aligned, the sheet needs %d aligned bytes"
+                               % (out.numel(), "that is not" if out.data_ptr() % _lib.PRESENT_ALIGN else "that is", total))
+    partials = _partials
+    if dist is not None and partials is None:
+        partials = torch.empty((blocks(H * W), _lib.PRESENT_PARTIAL_WORDS), device=dev, dtype=torch.float32)
+    with _lib.on_device(dev):
+        _lib.check(lib.gft_present_view(_lib.raw_stream(dev), H, W, _ptr(im), im_stride, _ptr(ph), ph_stride, planes_arg, _ptr(d), _ptr(a),
+                                        _ptr(dist), _ptr(rg_t), rg_host, _ptr(dr_t), dr, _ptr(po_t), po, znear, zfar,
+                                        float(tof_multiplier), _ptr(partials) if dist is not None else None, out.data_ptr()))
+    return _views(out, offsets, H, W)
+
+
+class PhasorRanges:
+    """The normalisation ranges of ``real``, ``imag`` and ``amp``: ``save_input``'s ``np.min`` / ``np.max`` over the whole
+    ground-truth sequence (``render.py:46-47, 61``) as a float32 device tensor [6] = (lo, hi) three times::
+
+        ranges = present.PhasorRanges()
+        for view in views:
+            ranges.add(view.original_tof_image)               # no host read
+        present.view_images(..., ranges=ranges.tensor)
+
+    ``lo`` of ``real`` and ``imag`` is taken over the three channels of the red / blue images as the reference forms them (the
+    green one is 0), so it is 0 for finite input.  A NaN stays, as in numpy."""
+
+    def __init__(self, device=None):
+        lib = _lib.load()
+        device = torch.device("cuda" if device is None else device)
+        if device.type != "cuda":
+            raise RuntimeError("gftorf_amd.present: PhasorRanges lives on a HIP device, got %s; there is no CPU path" % device)
+        self.device = torch.device("cuda", torch.cuda.current_device() if device.index is None else device.index)
+        self.tensor = torch.empty((_lib.PRESENT_RANGE_WORDS,), device=self.device, dtype=torch.float32)
+        # the scratch of the largest launch there is, once: a graph captured by an earlier add keeps its address
+        self._partials = torch.empty((int(lib.gft_present_blocks(1 << 40)), _lib.PRESENT_RANGE_WORDS), device=self.device,
+                                     dtype=torch.float32)
+        self.reset()
+
+    def reset(self):
+        """(+inf, -inf) three times, by one kernel on the current stream"""
+        with _lib.on_device(self.device):
+            _lib.check(_lib.load().gft_present_ranges_reset(_lib.raw_stream(self.device), self.tensor.data_ptr()))
+
+    def add(self, gt_tof):
+        """Fold one ground-truth ToF image [>= 3, H, W] (planes 0..2 are read, in place) into the ranges: two launches"""
+        t, stride = _planes(gt_tof, "gt_tof", 3, 1 << 30)
+        if _devices([(t, "gt_tof")]) != self.device:
+            raise RuntimeError("gftorf_amd.present: gt_tof is on %s, the ranges on %s" % (t.device, self.device))
+        with _lib.on_device(self.device):
+            _lib.check(_lib.load().gft_present_ranges(_lib.raw_stream(self.device), int(t.shape[1] * t.shape[2]), t.data_ptr(), stride,
+                                                      self._partials.data_ptr(), self.tensor.data_ptr()))
+
+    def result(self):
+        """the six values as a float32 numpy array: the one blocking read"""
+        return self.tensor.cpu().numpy()
+
+
+class ViewSheets:
+    """Pinned staging for a render loop: the device forms view i + 1 while the host encodes view i::
+
+        sheets = present.ViewSheets(slots=2)
+        for vid, view in enumerate(views):
+            pkg = render_eval(view, ...)
+            sheets.submit(vid, image=pkg["render"], phasor=pkg["render_phasor"], ..., ranges=ranges.tensor, zplanes=zp, ...)
+            for tag, images in sheets.ready():                # the views whose copy has completed, oldest first
+                write_pngs(tag, images)                       # numpy arrays over pinned memory
+        for tag, images in sheets.ready(wait=True):
+            write_pngs(tag, images)
+
+    ``submit`` never waits: with every slot in flight or handed out it raises.  The arrays ``ready`` yields belong to their
+    slot, which is free again when the loop moves past them (or with the next ``ready`` call)."""
+
+    def __init__(self, slots=2):
+        _lib.load()
+        if int(slots) < 1:
+            raise ValueError("gftorf_amd.present: ViewSheets needs at least one slot, got %s" % slots)
+        self._slots = [dict(state="free", device=None, host=None, partials=None, event=None) for _ in range(int(slots))]
+        self._order = []          # slots in flight, oldest first
+        self._lent = []           # slots whose arrays the caller holds
+
+    def _release(self):
+        for s in self._lent:
+            s["state"] = "free"
+        self._lent = []
+
+    def submit(self, tag, **view):
+        """``view_images(**view)`` into a free slot, the sheet's copy to pinned memory and an event, all on the current stream"""
+        slot = next((s for s in self._slots if s["state"] == "free"), None)
+        if slot is None:
+            raise RuntimeError("gftorf_amd.present: all %d slots of this ViewSheets are in flight; take the finished views with ready()"
+                               % len(self._slots))
+        first = next((v for v in (view.get(k) for k in ("image", "phasor", "depth", "dd")) if isinstance(v, torch.Tensor)), None)
+        if first is None or first.dim() != 3:
+            raise ValueError("gftorf_amd.present: nothing to show: give image, phasor, depth or dd as [C, H, W] tensors")
+        H, W = int(first.shape[1]), int(first.shape[2])
+        # the largest sheet of this size: what the groups leave out is not copied
+        full = sheet_layout(H, W, _EVERY)[0]
+        if slot["device"] is None or slot["device"].numel() < full or slot["device"].device != first.device:
+            slot["device"] = torch.empty((full,), device=first.device, dtype=torch.uint8)
+            slot["host"] = torch.empty((full,), dtype=torch.uint8, pin_memory=True)
+            slot["partials"] = torch.empty((max(1, blocks(H * W)), _lib.PRESENT_PARTIAL_WORDS), device=first.device, dtype=torch.float32)
+            slot["event"] = torch.cuda.Event()
+        images = view_images(out=slot["device"], _partials=slot["partials"], **view)
+        last = max(images.values(), key=lambda t: t.data_ptr())
+        used = last.data_ptr() - slot["device"].data_ptr() + last.numel() * last.element_size()
+        slot["host"][:used].copy_(slot["device"][:used], non_blocking=True)
+        slot["event"].record()
+        host = slot["host"].numpy()
+        base = slot["device"].data_ptr()
+        arrays = {}
+        for name, t in images.items():
+            o = t.data_ptr() - base
+            raw = host[o:o + t.numel() * t.element_size()]
+            arrays[name] = (raw.view(np.float32) if t.dtype == torch.float32 else raw).reshape(tuple(t.shape))
+        slot.update(state="flight", tag=tag, arrays=arrays)
+        self._order.append(slot)
+
+    def ready(self, wait=False):
+        """Yields (tag, {name: numpy array}) of the submitted views whose copy has completed, oldest first, and stops at the
+        first that has not; ``wait=True`` waits for each instead, so every submitted view comes out."""
+        self._release()
+        while self._order:
+            slot = self._order[0]
+            if wait:
+                slot["event"].synchronize()
+            elif not slot["event"].query():
+                return
+            self._order.pop(0)
+            slot["state"] = "lent"
+            self._lent.append(slot)
+            yield slot["tag"], slot["arrays"]
+            self._release()
