@@ -148,6 +148,7 @@ EXPORTS = [
     "gft_image_loss_forward", "gft_image_loss_backward", "gft_pixel_loss_blocks", "gft_pixel_loss_forward", "gft_pixel_loss_backward",
     "gft_grad_norm_scratch_bytes", "gft_grad_norm", "gft_grad_scale",
     "gft_densify_stats", "gft_rows_rank_scratch_bytes", "gft_rows_rank", "gft_rows_rank_dev", "gft_rows_gather", "gft_rows_any_nonzero",
+    "gft_densify_plan_scratch_bytes", "gft_densify_classify", "gft_densify_layout", "gft_rows_remap",
 ]
 # include/gftorf_flow.h (the scene-flow term; no struct, so the ABI version is unchanged)
 FLOW_EXPORTS = ["gft_flow_loss_blocks", "gft_flow_loss_forward", "gft_flow_loss_backward", "gft_flow_points", "gft_flow_project",
@@ -382,6 +383,22 @@ def load():
     lib.gft_rows_any_nonzero.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.gft_rows_gather.restype = C.c_int
     lib.gft_rows_gather.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    lib.gft_densify_plan_scratch_bytes.restype = C.c_size_t
+    lib.gft_densify_plan_scratch_bytes.argtypes = [C.c_int64]
+    # stream, P, grad_norm, grad, max_scaling, max_grad, dense_threshold, row_class, clone_rows, split_rows, scratch, counts
+    lib.gft_densify_classify.restype = C.c_int
+    lib.gft_densify_classify.argtypes = ([C.c_void_p, C.c_int64] + [C.c_void_p] * 3 + [C.c_float, C.c_float] + [C.c_void_p] * 4 +
+                                         [C.POINTER(C.c_int64)])
+    # stream, P, C, S, N, row_class, clone_rows, split_rows, opacity, max_scaling, child_max_scaling, min_opacity, use_size,
+    # screen_dead, big_threshold, small_threshold, seg, seg_cols, source_row, kind, child, map_new, map_state, motion_mask,
+    # motion_rank, scratch, counts
+    lib.gft_densify_layout.restype = C.c_int
+    lib.gft_densify_layout.argtypes = ([C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32] + [C.c_void_p] * 6 +
+                                       [C.c_float, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_int32] +
+                                       [C.c_void_p] * 8 + [C.POINTER(C.c_int64)])
+    # stream, n_out, map, src, src_rows, extra, dst, row_bytes
+    lib.gft_rows_remap.restype = C.c_int
+    lib.gft_rows_remap.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]
     lib.gft_knn_scratch_bytes.restype = C.c_size_t
     lib.gft_knn_scratch_bytes.argtypes = [C.c_int32]
     lib.gft_knn_mean_dist2.restype = C.c_int

@@ -1,5 +1,6 @@
 // k_densify.hip -- per-Gaussian bookkeeping around the rasterizer (include/gftorf_densify.h): the
-// statistics update of every iteration and the order-preserving row compaction of `t[mask]`.
+// statistics update of every iteration, the order-preserving row compaction of `t[mask]`, and the plan and the
+// row mover of a whole densify_and_prune event.
 // HBM-bound byte work: coalesced reads, one pass.
 #include "gft_internal.h"
 #include "gftorf_densify.h"
@@ -63,7 +64,7 @@ __global__ __launch_bounds__(DN_BLOCK) void k_rows_count(RankArgs a)
 }
 
 // one workgroup: exclusive scan of the block sums in place, total
-__global__ __launch_bounds__(1024) void k_rows_scan(uint32_t* block_sum, int nblocks, uint32_t* total)
+__device__ __forceinline__ void scan_block_sums(uint32_t* block_sum, int nblocks, uint32_t* total)
 {
     __shared__ uint32_t part[1024];
     const int per = (nblocks + 1023) / 1024;
@@ -88,6 +89,11 @@ __global__ __launch_bounds__(1024) void k_rows_scan(uint32_t* block_sum, int nbl
             run += v;
         }
     if (threadIdx.x == 1023) *total = part[1023];
+}
+
+__global__ __launch_bounds__(1024) void k_rows_scan(uint32_t* block_sum, int nblocks, uint32_t* total)
+{
+    scan_block_sums(block_sum, nblocks, total);
 }
 
 __global__ __launch_bounds__(DN_BLOCK) void k_rows_rank(RankArgs a)
@@ -259,6 +265,277 @@ extern "C" int gft_rows_gather(void* hip_stream, int64_t P, const uint8_t* mask,
     const dim3 grid((unsigned)((total + DN_BLOCK - 1) / DN_BLOCK));
     if (wide) hipLaunchKernelGGL(k_rows_gather<uint4>, grid, dim3(DN_BLOCK), 0, s, P, (int)pieces, mask, rank, (const uint4*)src, (uint4*)dst);
     else hipLaunchKernelGGL(k_rows_gather<uint32_t>, grid, dim3(DN_BLOCK), 0, s, P, (int)pieces, mask, rank, (const uint32_t*)src, (uint32_t*)dst);
+    GFT_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- the fused densify_and_prune (gftorf_amd.densify.densify_and_prune_fused) ------------------------------------------
+// The event is a function of per-row quantities, so it is planned once and every tensor is then moved once.  Both plan
+// passes rank TWO flags of a row in the three launches of a ranking (count, scan, rank): a workgroup's two counts (at most
+// RK_ROWS each) travel through its prefix sum in the halves of one word.
+namespace {
+
+struct Rank2 {
+    uint32_t* block_sum;     // [2][blocks]: flag a's sums, then flag b's
+    int blocks;
+    uint32_t* totals;        // 2 words
+};
+
+// F: flags(row) -> bit 0 = flag a, bit 1 = flag b; emit(row, flags, rank a, rank b)
+template <typename F>
+__global__ __launch_bounds__(DN_BLOCK) void k_plan_count(F f, int64_t rows, Rank2 r)
+{
+    __shared__ uint32_t wsum[DN_BLOCK / 64];
+    const int64_t r0 = (int64_t)blockIdx.x * RK_ROWS + threadIdx.x * 16;
+    uint32_t c = 0;
+    for (int k = 0; k < 16; k++)
+        if (r0 + k < rows) {
+            const uint32_t fl = f.flags(r0 + k);
+            c += (fl & 1u) + ((fl & 2u) << 15);
+        }
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor((int)c, o);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t t = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        r.block_sum[blockIdx.x] = t & 0xffffu;
+        r.block_sum[r.blocks + blockIdx.x] = t >> 16;
+    }
+}
+
+// two workgroups: each scans one flag's block sums
+__global__ __launch_bounds__(1024) void k_plan_scan(Rank2 r)
+{
+    scan_block_sums(r.block_sum + (int64_t)blockIdx.x * r.blocks, r.blocks, r.totals + blockIdx.x);
+}
+
+template <typename F>
+__global__ __launch_bounds__(DN_BLOCK) void k_plan_rank(F f, int64_t rows, Rank2 r)
+{
+    __shared__ uint32_t wsum[DN_BLOCK / 64];
+    const int64_t r0 = (int64_t)blockIdx.x * RK_ROWS + threadIdx.x * 16;
+    uint32_t bits = 0, c = 0;                      // two flag bits per row of this thread
+    for (int k = 0; k < 16; k++)
+        if (r0 + k < rows) {
+            const uint32_t fl = f.flags(r0 + k) & 3u;
+            bits |= fl << (2 * k);
+            c += (fl & 1u) + ((fl & 2u) << 15);
+        }
+    uint32_t inc = c;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t v = (uint32_t)__shfl_up((int)inc, o);
+        if (lane >= o) inc += v;
+    }
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    uint32_t excl = inc - c;
+    for (int w = 0; w < wave; w++) excl += wsum[w];
+    uint32_t ra = r.block_sum[blockIdx.x] + (excl & 0xffffu);
+    uint32_t rb = r.block_sum[r.blocks + blockIdx.x] + (excl >> 16);
+    for (int k = 0; k < 16; k++)
+        if (r0 + k < rows) {
+            const uint32_t fl = (bits >> (2 * k)) & 3u;
+            f.emit(r0 + k, fl, ra, rb);
+            ra += fl & 1u;
+            rb += fl >> 1;
+        }
+}
+
+// classify: flag a = cloned, flag b = split (scene/gaussian_model.py:573-579, 605-608)
+struct PlanClassify {
+    const float* gnorm;      // [P] torch.norm(grads, dim=-1)
+    const float* g;          // [P] grads
+    const float* ms;         // [P] largest activated scaling
+    float max_grad, dense_thr;
+    uint8_t* cls;            // [P] 0 keep, 1 clone, 2 split
+    int32_t* clone_src;      // [C] the cloned rows in order
+    int32_t* split_src;      // [S] the split rows in order
+    __device__ __forceinline__ uint32_t flags(int64_t i) const
+    {
+        const float m = ms[i];
+        const uint32_t clone = (gnorm[i] >= max_grad) && (m <= dense_thr);
+        const uint32_t split = (g[i] >= max_grad) && (m > dense_thr);
+        return clone | (split << 1);
+    }
+    __device__ __forceinline__ void emit(int64_t i, uint32_t fl, uint32_t ra, uint32_t rb) const
+    {
+        cls[i] = (uint8_t)fl;
+        if (fl & 1u) clone_src[ra] = (int32_t)i;
+        if (fl & 2u) split_src[rb] = (int32_t)i;
+    }
+};
+
+// layout over the virtual rows (P originals, C clones, N * S children): flag a = survives, flag b = survives and is dynamic
+struct PlanLayout {
+    int64_t P, C, S;
+    const uint8_t* cls;
+    const int32_t* clone_src;
+    const int32_t* split_src;
+    const float* op;         // [P] activated opacity
+    const float* ms;         // [P]
+    const float* child_ms;   // [N * S] largest activated scaling of a child's own new scaling
+    float min_opacity, big_thr, small_thr;
+    int use_size, screen_dead;
+    const float* seg;        // [P, seg_cols] or NULL
+    int seg_cols;
+    int32_t* source_row;     // outputs, one entry per survivor
+    uint8_t* kind;
+    int32_t* child;
+    int32_t* map_new;        // source_row, a child redirected to P + its index
+    int32_t* map_state;      // source_row of a kept original, -1 for a new row
+    uint8_t* motion_mask;
+    int32_t* motion_rank;
+    __device__ __forceinline__ void where(int64_t v, int32_t& src, int32_t& kd, int32_t& ch) const
+    {
+        if (v < P) { src = (int32_t)v; kd = 0; ch = -1; }
+        else if (v < P + C) { src = clone_src[v - P]; kd = 1; ch = -1; }
+        else { ch = (int32_t)(v - P - C); src = split_src[ch % S]; kd = 2; }
+    }
+    __device__ __forceinline__ uint32_t flags(int64_t v) const
+    {
+        int32_t src, kd, ch;
+        where(v, src, kd, ch);
+        if (kd == 0 && cls[src] == 2) return 0;
+        bool dead = op[src] < min_opacity;
+        if (use_size) {
+            const float m = kd == 2 ? child_ms[ch] : ms[src];
+            dead = dead || screen_dead || (m > big_thr) || (m < small_thr);
+        }
+        if (dead) return 0;
+        return 1u | ((seg && seg[(int64_t)src * seg_cols] > 0.5f) ? 2u : 0u);
+    }
+    __device__ __forceinline__ void emit(int64_t v, uint32_t fl, uint32_t ra, uint32_t rb) const
+    {
+        if (!(fl & 1u)) return;
+        int32_t src, kd, ch;
+        where(v, src, kd, ch);
+        source_row[ra] = src;
+        kind[ra] = (uint8_t)kd;
+        child[ra] = ch;
+        map_new[ra] = kd == 2 ? (int32_t)(P + ch) : src;
+        map_state[ra] = kd == 0 ? src : -1;
+        if (seg) {
+            motion_mask[ra] = (uint8_t)(fl >> 1);
+            motion_rank[ra] = (int32_t)rb;
+        }
+    }
+};
+
+template <typename F>
+int plan_rank(hipStream_t s, const F& f, int64_t rows, void* scratch, int64_t* counts)
+{
+    const int blocks = (int)((rows + RK_ROWS - 1) / RK_ROWS);
+    Rank2 r;
+    r.block_sum = (uint32_t*)scratch;
+    r.blocks = blocks;
+    r.totals = r.block_sum + 2 * (int64_t)blocks;
+    hipLaunchKernelGGL(k_plan_count<F>, dim3(blocks), dim3(DN_BLOCK), 0, s, f, rows, r);
+    hipLaunchKernelGGL(k_plan_scan, dim3(2), dim3(1024), 0, s, r);
+    hipLaunchKernelGGL(k_plan_rank<F>, dim3(blocks), dim3(DN_BLOCK), 0, s, f, rows, r);
+    GFT_CHECK_HIP(hipGetLastError());
+    uint32_t host[2] = {0, 0};
+    GFT_CHECK_HIP(hipMemcpyAsync(host, r.totals, sizeof(host), hipMemcpyDeviceToHost, s));
+    GFT_CHECK_HIP(hipStreamSynchronize(s));
+    counts[0] = host[0];
+    counts[1] = host[1];
+    return 0;
+}
+
+// dst[r] = row map[r] of src (map[r] < src_rows), row map[r] - src_rows of extra, or zero (map[r] < 0)
+template <typename T>
+__global__ __launch_bounds__(DN_BLOCK) void k_rows_remap(int64_t total, int pieces /* per row */, const int32_t* __restrict__ map,
+                                                         const T* __restrict__ src, int64_t src_rows, const T* __restrict__ extra,
+                                                         T* __restrict__ dst)
+{
+    const int64_t e = (int64_t)blockIdx.x * DN_BLOCK + threadIdx.x;
+    if (e >= total) return;
+    // (a 32-bit division where the element index allows: the 64-bit one is a long instruction sequence)
+    const int64_t row = total <= 0xffffffffll ? (int64_t)((uint32_t)e / (uint32_t)pieces) : e / pieces;
+    const int piece = (int)(e - row * pieces);
+    const int64_t m = map[row];
+    T v = {};
+    if (m >= 0) {
+        if (m < src_rows) v = src[m * pieces + piece];
+        else if (extra) v = extra[(m - src_rows) * pieces + piece];
+    }
+    dst[e] = v;
+}
+
+}  // namespace
+
+extern "C" size_t gft_densify_plan_scratch_bytes(int64_t rows)
+{
+    const int64_t blocks = rows <= 0 ? 0 : (rows + RK_ROWS - 1) / RK_ROWS;
+    return (size_t)(2 * blocks + 64) * sizeof(uint32_t);
+}
+
+extern "C" int gft_densify_classify(void* hip_stream, int64_t P, const float* grad_norm, const float* grad, const float* max_scaling,
+                                    float max_grad, float dense_threshold, uint8_t* row_class, int32_t* clone_rows, int32_t* split_rows,
+                                    void* scratch, int64_t* counts)
+{
+    if (!counts) return gft_fail("gft_densify_classify: counts is NULL");
+    counts[0] = counts[1] = 0;
+    if (P < 0 || P > 0x7fffffffll) return gft_fail("gft_densify_classify: bad row count");
+    if (P == 0) return 0;
+    if (!grad_norm || !grad || !max_scaling || !row_class || !clone_rows || !split_rows || !scratch)
+        return gft_fail("gft_densify_classify: NULL argument");
+    PlanClassify f;
+    f.gnorm = grad_norm; f.g = grad; f.ms = max_scaling;
+    f.max_grad = max_grad; f.dense_thr = dense_threshold;
+    f.cls = row_class; f.clone_src = clone_rows; f.split_src = split_rows;
+    return plan_rank((hipStream_t)hip_stream, f, P, scratch, counts);
+}
+
+extern "C" int gft_densify_layout(void* hip_stream, int64_t P, int64_t C, int64_t S, int32_t N, const uint8_t* row_class,
+                                  const int32_t* clone_rows, const int32_t* split_rows, const float* opacity, const float* max_scaling,
+                                  const float* child_max_scaling, float min_opacity, int32_t use_size, int32_t screen_dead,
+                                  float big_threshold, float small_threshold, const float* seg, int32_t seg_cols, int32_t* source_row,
+                                  uint8_t* kind, int32_t* child, int32_t* map_new, int32_t* map_state, uint8_t* motion_mask,
+                                  int32_t* motion_rank, void* scratch, int64_t* counts)
+{
+    if (!counts) return gft_fail("gft_densify_layout: counts is NULL");
+    counts[0] = counts[1] = 0;
+    if (P < 0 || C < 0 || S < 0 || N < 1 || C > P || S > P) return gft_fail("gft_densify_layout: bad row counts");
+    const int64_t V = P + C + (int64_t)N * S;
+    if (V > 0x7fffffffll) return gft_fail("gft_densify_layout: more than 2^31 - 1 virtual rows");
+    if (V == 0) return 0;
+    if (!row_class || !opacity || !max_scaling || !source_row || !kind || !child || !map_new || !map_state || !scratch ||
+        (C && !clone_rows) || (S && (!split_rows || (use_size && !child_max_scaling))))
+        return gft_fail("gft_densify_layout: NULL argument");
+    if (seg && (seg_cols < 1 || !motion_mask || !motion_rank)) return gft_fail("gft_densify_layout: seg without its outputs");
+    PlanLayout f;
+    f.P = P; f.C = C; f.S = S;
+    f.cls = row_class; f.clone_src = clone_rows; f.split_src = split_rows;
+    f.op = opacity; f.ms = max_scaling; f.child_ms = child_max_scaling;
+    f.min_opacity = min_opacity; f.big_thr = big_threshold; f.small_thr = small_threshold;
+    f.use_size = use_size != 0; f.screen_dead = screen_dead != 0;
+    f.seg = seg; f.seg_cols = seg_cols;
+    f.source_row = source_row; f.kind = kind; f.child = child; f.map_new = map_new; f.map_state = map_state;
+    f.motion_mask = motion_mask; f.motion_rank = motion_rank;
+    return plan_rank((hipStream_t)hip_stream, f, V, scratch, counts);
+}
+
+extern "C" int gft_rows_remap(void* hip_stream, int64_t n_out, const int32_t* map, const void* src, int64_t src_rows, const void* extra,
+                              void* dst, int64_t row_bytes)
+{
+    if (n_out < 0 || row_bytes < 0 || src_rows < 0) return gft_fail("gft_rows_remap: negative size");
+    if (row_bytes % 4) return gft_fail("gft_rows_remap: row_bytes must be a multiple of 4");
+    if (n_out == 0 || row_bytes == 0) return 0;
+    if (src_rows > 0x7fffffffll) return gft_fail("gft_rows_remap: too many source rows");
+    if (!map || !dst || (src_rows && !src)) return gft_fail("gft_rows_remap: NULL argument");
+    const uintptr_t all = (uintptr_t)src | (uintptr_t)extra | (uintptr_t)dst;
+    if (all & 3) return gft_fail("gft_rows_remap: pointers must be 4-byte aligned");
+    hipStream_t s = (hipStream_t)hip_stream;
+    const bool wide = row_bytes % 16 == 0 && (all & 15) == 0;
+    const int64_t pieces = row_bytes / (wide ? 16 : 4);
+    const int64_t total = n_out * pieces;
+    if (pieces > 0x7fffffffll || (total + DN_BLOCK - 1) / DN_BLOCK > 0x7fffffffll) return gft_fail("gft_rows_remap: too large");
+    const dim3 grid((unsigned)((total + DN_BLOCK - 1) / DN_BLOCK));
+    if (wide) hipLaunchKernelGGL(k_rows_remap<uint4>, grid, dim3(DN_BLOCK), 0, s, total, (int)pieces, map, (const uint4*)src, src_rows,
+                                 (const uint4*)extra, (uint4*)dst);
+    else hipLaunchKernelGGL(k_rows_remap<uint32_t>, grid, dim3(DN_BLOCK), 0, s, total, (int)pieces, map, (const uint32_t*)src, src_rows,
+                            (const uint32_t*)extra, (uint32_t*)dst);
     GFT_CHECK_HIP(hipGetLastError());
     return 0;
 }

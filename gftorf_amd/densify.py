@@ -16,6 +16,9 @@ gather or scatter, which at 1 M Gaussians costs more per iteration than the rast
   bodies a maintainer replaces by one call each.  Selection masks are the reference's own torch expressions, the
   split's ``torch.normal`` draw is torch's (same generator, same samples); every ``t[mask]`` is a row compaction
   with one rank computation per mask.
+* :func:`densify_and_prune_fused` -- the whole ``densify_and_prune`` event as one plan and one pass over every tensor (two
+  host reads instead of four, every parameter and moment read once and written once), with the same result as the composite;
+  its :class:`DensifyResult` carries the new motion mask, a ready ``DeformQuery`` and any caller tensor across the event.
 
 Kernels: ``csrc/k_densify.hip`` behind ``include/gftorf_densify.h``; no CPU path.
 """
@@ -296,3 +299,207 @@ def densify_and_prune(pc, max_grad, min_opacity, extent, max_screen_size=20):
 def prune(pc, min_opacity):
     """``GaussianModel.prune`` (gaussian_model.py:642-646)."""
     prune_points(pc, (pc.get_opacity < min_opacity).squeeze())
+
+
+# ---- the whole event as one plan and one pass over every tensor ----------------------------------------------------------
+def _remap(lib, dev, n_out, row_map, src, extra=None):
+    """``gft_rows_remap``: a new tensor of ``n_out`` rows, row r = row ``row_map[r]`` of ``src``, row ``row_map[r] -
+    src.size(0)`` of ``extra``, or zeros for -1."""
+    src = src.detach().contiguous()
+    rows = src.size(0)
+    row_bytes = (src.numel() // rows if rows else int(torch.Size(src.shape[1:]).numel())) * src.element_size()
+    if row_bytes % 4:
+        raise RuntimeError("gftorf_amd.densify: rows of %d bytes (%s %s) are not a multiple of 4 bytes"
+                           % (row_bytes, src.dtype, tuple(src.shape[1:])))
+    if extra is not None:
+        extra = extra.detach().contiguous()
+        if extra.dtype != src.dtype or tuple(extra.shape[1:]) != tuple(src.shape[1:]):
+            raise RuntimeError("gftorf_amd.densify: the extra rows are %s %s, the tensor's %s %s"
+                               % (extra.dtype, tuple(extra.shape[1:]), src.dtype, tuple(src.shape[1:])))
+    dst = torch.empty((n_out,) + tuple(src.shape[1:]), device=dev, dtype=src.dtype)
+    if n_out and row_bytes:
+        with _lib.on_device(dev):
+            _lib.check(lib.gft_rows_remap(_lib.raw_stream(dev), n_out, row_map.data_ptr(), src.data_ptr() if rows else None, rows,
+                                          extra.data_ptr() if extra is not None and extra.numel() else None, dst.data_ptr(),
+                                          row_bytes))
+    return dst
+
+
+class DensifyResult:
+    """What :func:`densify_and_prune_fused` did, and the means to carry further per-Gaussian tensors across it.
+
+    ``P_before`` / ``P``: rows before and after; ``cloned`` / ``split``: rows selected for either; ``pruned``: rows the final
+    prune removed beside the split originals (originals, clones and children).  Per row of the new model, on the device:
+    ``source_row`` (int32: the original row it is, or was copied or split from), ``kind`` (uint8: 0 kept original, 1 clone,
+    2 child), ``child`` (int32: the child's index k * split + j, -1 otherwise) and ``motion_mask`` (bool,
+    ``pc.get_motion_mask`` of the new model; None for a model without seg colours).  After a call that went through the
+    composite (``max_grad <= 0``) only the row counts are known: the per-row tensors and the other counts are None."""
+
+    def __init__(self, P_before, P, cloned=None, split=None, pruned=None, source_row=None, kind=None, child=None, map_state=None,
+                 motion_mask=None, motion_rank=None, dynamic=None):
+        self.P_before, self.P, self.cloned, self.split, self.pruned = P_before, P, cloned, split, pruned
+        self.source_row, self.kind, self.child, self.motion_mask = source_row, kind, child, motion_mask
+        self._map_state, self._motion_rank, self._dynamic = map_state, motion_rank, dynamic
+
+    def remap(self, t, new_rows="zero"):
+        """A tensor with one row per Gaussian of the model BEFORE the event, carried across it (``gft_rows_remap``, one
+        launch): kept originals keep their row; clones and children get zeros (``"zero"``, as the Adam moments do) or their
+        parent's row (``"parent"``, as the parameters do)."""
+        if new_rows not in ("zero", "parent"):
+            raise ValueError("DensifyResult.remap: new_rows must be 'zero' or 'parent', got %r" % (new_rows,))
+        if self.source_row is None:
+            raise RuntimeError("DensifyResult.remap: this event went through the composite (max_grad <= 0) and has no row map")
+        _dev_check(t, "DensifyResult.remap")
+        if t.size(0) != self.P_before or t.device != self.source_row.device:
+            raise RuntimeError("DensifyResult.remap: tensor with %d rows on %s, the model had %d rows on %s"
+                               % (t.size(0), t.device, self.P_before, self.source_row.device))
+        return _remap(_lib.load(), t.device, self.P, self.source_row if new_rows == "parent" else self._map_state, t)
+
+    def deform_query(self):
+        """The ``DeformQuery`` of the new model's motion mask, from the rank the layout pass already formed: no further
+        ranking, no host read."""
+        from .query import DeformQuery
+        if self.motion_mask is None:
+            raise RuntimeError("DensifyResult.deform_query: the model has no seg colours, so no motion mask")
+        return DeformQuery.from_rank(self.motion_mask, self._motion_rank, self._dynamic)
+
+
+def _f32_positive(x):
+    """``x`` rounded to float32, as a kernel argument and torch's comparison with a float32 tensor take it, is > 0."""
+    return C.c_float(float(x)).value > 0.0
+
+
+def densify_and_prune_fused(pc, max_grad, min_opacity, extent, max_screen_size=20, N=2):
+    """``GaussianModel.densify_and_prune`` (gaussian_model.py:624-640) as one plan and one pass over every tensor: leaves
+    ``pc`` and its optimizer exactly as :func:`densify_and_prune` does under the same torch generator state (every
+    parameter, both moments of every group, ``step``, the order of ``param_groups``, the three statistics), and returns a
+    :class:`DensifyResult`.  ``N``: children per split Gaussian (the reference's ``densify_and_split`` default, 2).
+
+    The event is a function of per-row quantities.  ``gft_densify_classify`` marks the cloned and the split rows (the
+    reference's two selections over ``grads``, ``torch.norm(grads, dim=-1)`` and ``get_scaling.max(1)``, which torch forms,
+    against thresholds passed as float32, as torch compares them); the children's ``xyz`` and ``scaling`` are the
+    reference's own torch statements on the S split rows (``torch.normal`` with the same shapes in the same order: same
+    generator consumption, same bits); ``gft_densify_layout`` applies the final prune to the P + C + N * S virtual rows
+    (originals, clones, children) and says where each survivor lands; ``gft_rows_remap`` then writes each new tensor in one
+    launch.  By construction:
+
+    * two blocking host reads per call: the numbers of cloned and split rows (``torch.normal`` needs the shape), then the
+      new row count together with the number of dynamic rows;
+    * every parameter and moment tensor is read once and written once (the S split rows of ``xyz``, ``rotation`` and the
+      activated scaling are read once more, for the children);
+    * the moments' new rows are written as zeros by the kernel that moves the kept ones: no ``torch.zeros`` plus copy;
+    * the statistics are three ``zeros(P')``.
+
+    A clone is never split because its padded gradient is 0, which needs ``max_grad > 0`` (as float32): for ``max_grad <=
+    0`` the call goes through :func:`densify_and_prune` (``N`` must then be 2) and the result carries row counts only."""
+    xyz = pc.get_xyz
+    _dev_check(xyz, "densify_and_prune_fused")
+    lib = _lib.load()
+    dev = xyz.device
+    P = int(xyz.shape[0])
+    N = int(N)
+    if N < 1:
+        raise ValueError("densify_and_prune_fused: N must be at least 1, got %d" % N)
+    if not _f32_positive(max_grad):
+        if N != 2:
+            raise ValueError("densify_and_prune_fused: max_grad <= 0 goes through densify_and_prune, which splits into 2 (N = %d)" % N)
+        densify_and_prune(pc, max_grad, min_opacity, extent, max_screen_size)
+        return DensifyResult(P, int(pc.get_xyz.shape[0]))
+    with torch.no_grad():
+        grads = pc.xyz_gradient_accum / pc.denom
+        grads[grads.isnan()] = 0.0
+        grad_norm = torch.norm(grads, dim=-1).contiguous()
+        grads = grads.reshape(-1).contiguous()
+        scaling = pc.get_scaling
+        max_scaling = torch.max(scaling, dim=1).values.contiguous()
+        opacity = pc.get_opacity.reshape(-1).contiguous()
+    for t, name in ((grad_norm, "xyz_gradient_accum / denom"), (max_scaling, "get_scaling"), (opacity, "get_opacity")):
+        if t.dtype != torch.float32 or t.numel() != P or t.device != dev:
+            raise RuntimeError("densify_and_prune_fused: %s must give one float32 value per Gaussian (%d) on %s" % (name, P, dev))
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    stream = _lib.raw_stream(dev)
+    counts = (C.c_int64 * 2)()
+
+    # plan, first half: which rows are cloned, which are split (host read 1: C and S)
+    row_class = torch.empty((P,), device=dev, dtype=torch.uint8)
+    clone_rows = torch.empty((P,), device=dev, dtype=torch.int32)
+    split_rows = torch.empty((P,), device=dev, dtype=torch.int32)
+    scratch = torch.empty((lib.gft_densify_plan_scratch_bytes(P),), device=dev, dtype=torch.uint8)
+    with _lib.on_device(dev):
+        _lib.check(lib.gft_densify_classify(stream, P, ptr(grad_norm), ptr(grads), ptr(max_scaling), float(max_grad),
+                                            float(pc.percent_dense * extent), ptr(row_class), ptr(clone_rows), ptr(split_rows),
+                                            ptr(scratch), counts))
+    n_clone, n_split = int(counts[0]), int(counts[1])
+
+    # the children's positions and scalings: densify_and_split's statements on the split rows
+    with torch.no_grad():
+        take = lambda t: _remap(lib, dev, n_split, split_rows, t)
+        scaling_sel = take(scaling)
+        stds = scaling_sel.repeat(N, 1)
+        means = torch.zeros((stds.size(0), 3), device=dev)
+        samples = torch.normal(mean=means, std=stds)
+        rots = _rotation_matrices(take(pc._rotation)).repeat(N, 1, 1)
+        new_xyz = torch.bmm(rots, samples.unsqueeze(-1)).squeeze(-1) + take(xyz).repeat(N, 1)
+        if getattr(pc, "isotropic", False):
+            new_scaling = pc.scaling_inverse_activation(pc.scaling_activation(take(pc._scaling)).repeat(N, 1) / (0.8 * N))
+        else:
+            new_scaling = pc.scaling_inverse_activation(scaling_sel.repeat(N, 1) / (0.8 * N))
+        child_max_scaling = pc.scaling_activation(new_scaling).max(dim=1).values.contiguous()
+    extra = {"xyz": new_xyz, "scaling": new_scaling}
+
+    # plan, second half: the final prune over the virtual rows and every survivor's place (host read 2: P' and n')
+    V = P + n_clone + N * n_split
+    seg = getattr(pc, "_features_seg_color", None)
+    if seg is not None and (seg.dim() != 2 or seg.size(0) != P or seg.dtype != torch.float32 or seg.size(1) < 1):
+        seg = None
+    seg_c = seg.detach().contiguous() if seg is not None else None
+    i32 = lambda: torch.empty((V,), device=dev, dtype=torch.int32)
+    u8 = lambda: torch.empty((V,), device=dev, dtype=torch.uint8)
+    source_row, child, map_new, map_state, kind = i32(), i32(), i32(), i32(), u8()
+    motion_mask, motion_rank = (u8(), i32()) if seg_c is not None else (None, None)
+    scratch = torch.empty((lib.gft_densify_plan_scratch_bytes(V),), device=dev, dtype=torch.uint8)
+    use_size = bool(max_screen_size)
+    with _lib.on_device(dev):
+        _lib.check(lib.gft_densify_layout(
+            stream, P, n_clone, n_split, N, ptr(row_class), ptr(clone_rows), ptr(split_rows), ptr(opacity), ptr(max_scaling),
+            ptr(child_max_scaling), float(min_opacity), int(use_size),
+            int(use_size and C.c_float(0.0).value > C.c_float(float(max_screen_size)).value),      # max_radii2D is all zeros there
+            float(0.05 * extent) if use_size else 0.0, float(0.001 * extent) if use_size else 0.0, ptr(seg_c),
+            int(seg_c.size(1)) if seg_c is not None else 0, ptr(source_row), ptr(kind), ptr(child), ptr(map_new), ptr(map_state),
+            ptr(motion_mask), ptr(motion_rank), ptr(scratch), counts))
+    P_new, n_dynamic = int(counts[0]), int(counts[1])
+    source_row, child, map_new, map_state, kind = (t[:P_new] for t in (source_row, child, map_new, map_state, kind))
+
+    # one launch per tensor: parameters by their source row (xyz and scaling: children from their new values), moments by
+    # the map whose new rows are -1
+    tensors = {}
+    for group in pc.optimizer.param_groups:
+        name = group["name"]
+        if name in _SKIP:
+            continue
+        assert len(group["params"]) == 1
+        p = group["params"][0]
+        state = pc.optimizer.state.get(p, None)
+        if name in extra:
+            moved = _remap(lib, dev, P_new, map_new, p, extra[name])
+        else:
+            moved = _remap(lib, dev, P_new, source_row, p)
+        new_p = nn.Parameter(moved.requires_grad_(True))
+        if state is not None:
+            state["exp_avg"] = _remap(lib, dev, P_new, map_state, state["exp_avg"])
+            state["exp_avg_sq"] = _remap(lib, dev, P_new, map_state, state["exp_avg_sq"])
+            del pc.optimizer.state[p]
+            group["params"][0] = new_p
+            pc.optimizer.state[new_p] = state
+        else:
+            group["params"][0] = new_p
+        tensors[name] = new_p
+    _adopt(pc, tensors)
+    pc.xyz_gradient_accum = torch.zeros((P_new, 1), device=dev)
+    pc.denom = torch.zeros((P_new, 1), device=dev)
+    pc.max_radii2D = torch.zeros((P_new,), device=dev)
+    return DensifyResult(P, P_new, cloned=n_clone, split=n_split, pruned=V - n_split - P_new, source_row=source_row, kind=kind,
+                         child=child, map_state=map_state,
+                         motion_mask=motion_mask[:P_new].view(torch.bool) if motion_mask is not None else None,
+                         motion_rank=motion_rank[:P_new] if motion_rank is not None else None,
+                         dynamic=n_dynamic if motion_mask is not None else None)

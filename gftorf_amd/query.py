@@ -129,6 +129,37 @@ class DeformQuery:
         self.n = int(n.value)
         self.count.fill_(self.n)
 
+    @classmethod
+    def from_rank(cls, motion_mask, rank, n):
+        """The plan of a mask that has been ranked already: adopts ``motion_mask`` (contiguous bool [P] on the HIP device),
+        its exclusive ``rank`` (contiguous int32 [P]: the number of set entries before each row) and its count ``n`` without
+        ranking again and without a host read -- what ``gftorf_amd.densify.densify_and_prune_fused`` leaves behind
+        (``DensifyResult.deform_query``).  Both tensors are kept by reference."""
+        if not isinstance(motion_mask, torch.Tensor) or not isinstance(rank, torch.Tensor):
+            raise TypeError("gftorf_amd.query: motion_mask and rank must be tensors")
+        if motion_mask.dtype != torch.bool or rank.dtype != torch.int32:
+            raise TypeError("gftorf_amd.query: motion_mask must be torch.bool and rank torch.int32, got %s and %s"
+                            % (motion_mask.dtype, rank.dtype))
+        if motion_mask.dim() != 1 or not motion_mask.is_contiguous() or rank.shape != motion_mask.shape or not rank.is_contiguous():
+            raise RuntimeError("gftorf_amd.query: motion_mask and rank must be contiguous [P] tensors, got %s and %s"
+                               % (list(motion_mask.shape), list(rank.shape)))
+        _device_only(motion_mask, "motion_mask")
+        if rank.device != motion_mask.device:
+            raise RuntimeError("gftorf_amd.query: rank is on %s, motion_mask on %s" % (rank.device, motion_mask.device))
+        P = int(motion_mask.shape[0])
+        n = int(n)
+        if not 0 <= n <= P:
+            raise ValueError("gftorf_amd.query: n must be the number of set mask entries (0..%d), got %d" % (P, n))
+        self = cls(None)
+        dev = motion_mask.device
+        self.P, self.n = P, n
+        self.motion_mask = motion_mask
+        self.mask = motion_mask.view(torch.uint8)
+        self.rank = rank
+        self._scratch = torch.empty((_lib.load().gft_rows_rank_scratch_bytes(P),), device=dev, dtype=torch.uint8)      # refresh()
+        self.count = torch.full((1,), n, device=dev, dtype=torch.int32)
+        return self
+
     def refresh(self):
         """Re-derives the dynamic rows on the device from the mask's current contents (``gft_rows_rank_dev``): nothing is read
         on the host, ``n`` stays, the call can be captured.  Call it after every in-place edit of the mask, before the next

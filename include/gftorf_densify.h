@@ -59,6 +59,49 @@ int gft_rows_any_nonzero(void* hip_stream, int64_t P, int32_t row_floats_a, cons
 int gft_rows_gather(void* hip_stream, int64_t P, const uint8_t* mask, const int32_t* rank, const void* src, void* dst,
                     int64_t row_bytes);
 
+/* ---- one densify_and_prune event as one plan and one pass over every tensor (scene/gaussian_model.py:571-640) ----
+ * The event is a function of per-row quantities.  Its result lives in a virtual row space of V = P + C + N * S rows:
+ * the P originals, the C clones in the order of their sources, the N * S children (child k * S + j belongs to the j-th
+ * split row: `repeat(N, ...)` tiles the whole block).  Both plan calls rank two flags of a row in the three launches of
+ * one ranking and block until their two counts have reached the host: two host reads per event.
+ * scratch of either call: gft_densify_plan_scratch_bytes(rows) bytes, rows = P (classify) or V (layout). */
+size_t gft_densify_plan_scratch_bytes(int64_t rows);
+
+/* row_class[i] (one byte) = 1 cloned: grad_norm[i] >= max_grad and max_scaling[i] <= dense_threshold,
+ *                           2 split:  grad[i] >= max_grad and max_scaling[i] > dense_threshold, 0 otherwise;
+ * clone_rows [C] / split_rows [S] (int32, room for P entries each): the cloned / split rows in increasing order;
+ * counts (host, 2 values) = C, S.  grad_norm / grad / max_scaling: float [P] (`torch.norm(grads, dim=-1)`, `grads`,
+ * `get_scaling.max(1)`); the thresholds as float, the way torch compares a Python number with a float32 tensor. */
+int gft_densify_classify(void* hip_stream, int64_t P, const float* grad_norm, const float* grad, const float* max_scaling,
+                         float max_grad, float dense_threshold, uint8_t* row_class, int32_t* clone_rows, int32_t* split_rows,
+                         void* scratch, int64_t* counts);
+
+/* The final prune over the V virtual rows and where every survivor lands (survivors keep their virtual order).  A row
+ * dies if it is a split original, if opacity < min_opacity (a clone's and a child's: their source's), or, with use_size,
+ * if screen_dead or its largest scaling is > big_threshold or < small_threshold (a clone's: its source's max_scaling, a
+ * child's: child_max_scaling [N * S] of its own new scaling).  Per survivor r (room for V entries each):
+ *   source_row[r] int32  the original row it is, or was copied or split from
+ *   kind[r]       uint8  0 kept original, 1 clone, 2 child
+ *   child[r]      int32  the child's index k * S + j, -1 for the other kinds
+ *   map_new[r]    int32  source_row[r], a child's P + child[r]      (gft_rows_remap of xyz / scaling with the children as extra)
+ *   map_state[r]  int32  source_row[r] of a kept original, else -1  (gft_rows_remap of the Adam moments)
+ * and with seg ([P, seg_cols] floats, may be NULL): motion_mask[r] (one byte) = seg[source_row[r], 0] > 0.5 and
+ * motion_rank[r] (int32) = the number of set motion_mask bytes before r.  counts (host, 2 values) = number of survivors,
+ * number of set motion_mask bytes.  P + C + N * S <= 2^31 - 1; any of P, C, S and the survivors may be 0. */
+int gft_densify_layout(void* hip_stream, int64_t P, int64_t C, int64_t S, int32_t N, const uint8_t* row_class,
+                       const int32_t* clone_rows, const int32_t* split_rows, const float* opacity, const float* max_scaling,
+                       const float* child_max_scaling, float min_opacity, int32_t use_size, int32_t screen_dead,
+                       float big_threshold, float small_threshold, const float* seg, int32_t seg_cols, int32_t* source_row,
+                       uint8_t* kind, int32_t* child, int32_t* map_new, int32_t* map_state, uint8_t* motion_mask,
+                       int32_t* motion_rank, void* scratch, int64_t* counts);
+
+/* dst[r] = row map[r] of src when 0 <= map[r] < src_rows, row map[r] - src_rows of extra when map[r] >= src_rows (a zero
+ * row when extra is NULL), a zero row when map[r] < 0; r < n_out, map int32.  One launch, every dst row written once;
+ * rows are row_bytes long (a multiple of 4), the pointers 4-byte aligned (16-byte accesses are used when the rows and
+ * all pointers allow). */
+int gft_rows_remap(void* hip_stream, int64_t n_out, const int32_t* map, const void* src, int64_t src_rows, const void* extra,
+                   void* dst, int64_t row_bytes);
+
 #ifdef __cplusplus
 }
 #endif
