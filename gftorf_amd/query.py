@@ -231,7 +231,8 @@ class DeformQuery:
         d_xyz_k``.  ``outs`` is a tuple of M [n, 3] tensors.  ``sh_of=k`` also returns the ``d_sh`` [n, 16, 3] of time k,
         with its gradient (the ``d_sh`` rows of the other times are computed and dropped); with None ``d_sh`` is None, the
         network's backward receives no ``d_sh`` gradient at all and the ``r`` / ``g`` / ``b`` heads get none, as under the
-        reference's autograd when ``d_sh`` is discarded (``train.py:171``).  Gradients reach the network's parameters only."""
+        reference's autograd when ``d_sh`` is discarded (``train.py:171``).  Gradients reach the network's parameters only.
+        With no dynamic row (``n == 0``) the network is not run: the outputs are empty tensors without a gradient function."""
         if not isinstance(net, DeformNetwork):
             raise TypeError("gftorf_amd.query: net must be a gftorf_amd.DeformNetwork, got %s" % type(net).__name__)
         t_dev, t_host, K = self._checked(xyz, times)
@@ -246,8 +247,14 @@ class DeformQuery:
         if sh_of is not None and not (isinstance(sh_of, int) and 0 <= sh_of < K):
             raise ValueError("gftorf_amd.query: sh_of must be None or an index into the %d times, got %r" % (K, sh_of))
         dev = self._on_device(xyz, ((t_dev, "times"), (c_dev, "combine")))
+        n = int(xyz.shape[0]) if self.mask is None else self.n
+        if n == 0:
+            # no dynamic row (every one pruned): nothing is queried.  The empty outputs hang on no parameter, so the network
+            # gets no gradient at all -- not 2 MB of zeros -- and its optimizer, which skips a parameter without one, neither
+            # counts a step nor moves the weights on their momentum alone.
+            empty = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
+            return tuple(empty(0, 3) for _ in range(M)), (None if sh_of is None else empty(0, 16, 3))
         x, t = self._inputs(xyz, scene_extent, t_dev, t_host, K, dev)
-        n = x.shape[0] // K
         if not hasattr(net, "_save_state"):
             net._save_state = {"fraction": None, "pending": None, "pin": None}
         params = _param_list(net)

@@ -9,7 +9,8 @@ CPU restatement (numpy) of ``utils/time_utils.py`` of the reference:
   heads ``xyz_warp`` and ``r``/``g``/``b`` (stacked on the last axis); ``d_rot`` and ``d_sh_p`` are
   returned as ZEROS by the reference (time_utils.py:127), the ``rot`` and ``a`` heads never reach an output.
 * :func:`backward`     -- the adjoint of the above, written out by hand (chain rule of Linear / ReLU);
-  inputs are not differentiated (the reference detaches them, scene/gaussian_model.py:172).
+  inputs are not differentiated (the reference detaches them, scene/gaussian_model.py:172).  :func:`relu_margin` and
+  :func:`relu_edges` say where a pre-activation is within rounding of zero and the gradient is not one value.
 
 Parameters are a dict with the reference's ``state_dict`` names (``linear.0.weight`` ... ``b.bias``), numpy
 arrays in torch's ``[out, in]`` layout.  ``dtype=np.float64`` gives the accuracy reference of the float32
@@ -185,6 +186,20 @@ def relu_margin(params, x, t):
     return margin
 
 
+def relu_edges(params, x, t, eps):
+    """The units whose pre-activation is within ``eps`` of zero (float64), as (layer, point, unit) triples: where another
+    arithmetic may take the ReLU on its other side (:func:`relu_margin`); :func:`backward` takes them as ``flip``."""
+    emb = embed(x, t, np.float64, arch_of(params)[1])
+    h = emb
+    edges = []
+    for i in range(D):
+        z = h @ params["linear.%d.weight" % i].astype(np.float64).T + params["linear.%d.bias" % i].astype(np.float64)
+        edges += [(i, int(r), int(u)) for r, u in zip(*np.nonzero(np.abs(z) < eps))]
+        a = np.maximum(z, 0)
+        h = np.concatenate([emb, a], axis=-1) if i == SKIP else a
+    return edges
+
+
 def forward(params, x, t, dtype=np.float32):
     """Returns (d_xyz[n,3], d_rot[n,4] = 0, d_sh[n,16,3], d_sh_p[n,16,2] = 0) (time_utils.py:115-127)."""
     _, _, _, h = _trunk(params, x, t, dtype)
@@ -195,10 +210,14 @@ def forward(params, x, t, dtype=np.float32):
     return d_xyz, np.zeros((n, 4), dtype), d_sh, np.zeros((n, NUM_SHS, 2), dtype)
 
 
-def backward(params, x, t, g_dxyz, g_dsh, dtype=np.float32):
+def backward(params, x, t, g_dxyz, g_dsh, dtype=np.float32, flip=()):
     """Gradients of sum(d_xyz * g_dxyz) + sum(d_sh * g_dsh) w.r.t. every parameter that reaches an output;
-    the ``rot`` / ``a`` heads get None as under the reference's autograd."""
+    the ``rot`` / ``a`` heads get None as under the reference's autograd.  ``flip``: (layer, point, unit) triples whose
+    ReLU derivative is taken on the other side of zero (:func:`relu_edges`; the activation itself, about 0 there, stays)."""
     emb, inputs, outs, h = _trunk(params, x, t, dtype)
+    on = [o > 0 for o in outs]
+    for i, r, u in flip:
+        on[i][r, u] = not on[i][r, u]
     g = {n + s: None for n in UNUSED for s in (".weight", ".bias")}
     g_dxyz = np.asarray(g_dxyz, dtype)
     g_dsh = np.asarray(g_dsh, dtype)
@@ -208,7 +227,7 @@ def backward(params, x, t, g_dxyz, g_dsh, dtype=np.float32):
         g[name + ".bias"] = go.sum(axis=0)
         dh = dh + go @ params[name + ".weight"].astype(dtype)
     for i in reversed(range(D)):
-        dz = dh * (outs[i] > 0)
+        dz = dh * on[i]
         g["linear.%d.weight" % i] = dz.T @ inputs[i]
         g["linear.%d.bias" % i] = dz.sum(axis=0)
         dh = dz @ params["linear.%d.weight" % i].astype(dtype)

@@ -1,7 +1,8 @@
-"""Helpers of tests/test_loop_densify.py: the pieces of the teacher-forced training loop that need no device -- the model from
+"""Helpers of tests/test_loop_densify.py and tests/test_loop_dynamic.py: the pieces of the teacher-forced training loop that need no device -- the model from
 a scene, the learning-rate schedule, the thresholds an event is given, the torch.optim.Adam twin of one step and the composed
 reference of one iteration (eager activations under CPU autograd, the C oracle of the rasterizer, its gradients pushed back
-through autograd: the reference tests/test_train_step.py uses)."""
+through autograd: the reference tests/test_train_step.py uses), with a motion mask and the deformation network's offsets in
+:func:`composed_reference_dynamic`."""
 import numpy as np
 import torch
 
@@ -38,8 +39,24 @@ def perturbed(gaussians, seed=3):
     return g
 
 
-def make_model(gaussians, dev, optimizer_cls, **optimizer_kw):
-    return densify_ref.EagerGaussians.from_scene(perturbed(gaussians), dev, optimizer_cls, LRS, **optimizer_kw)
+def make_model(gaussians, dev, optimizer_cls, cls=densify_ref.EagerGaussians, **optimizer_kw):
+    return cls.from_scene(perturbed(gaussians), dev, optimizer_cls, LRS, **optimizer_kw)
+
+
+class DynamicGaussians(densify_ref.EagerGaussians):
+    """The model with the reference's motion mask: a Gaussian is dynamic where the first seg colour is above one half."""
+    get_motion_mask = property(lambda self: (self._features_seg_color[:, 0] > 0.5).detach())      # gaussian_model.py:160-161
+
+
+def seg_colors(P, share=0.35, on_threshold=(3, 40, 41, 700), seed=4):
+    """Seg colours [P, 3] whose first column makes about `share` of the rows dynamic (1.0 against 0.0) and puts the rows
+    `on_threshold` exactly on 0.5: `> 0.5` leaves them static."""
+    rng = np.random.default_rng(seed)
+    seg = np.zeros((P, 3), np.float32)
+    seg[:, 0] = rng.random(P) < share
+    seg[:, 1:] = rng.random((P, 2))
+    seg[[r for r in on_threshold if r < P], 0] = 0.5
+    return torch.tensor(seg)
 
 
 # ---- events --------------------------------------------------------------------------------------------------------------
@@ -151,15 +168,52 @@ def composed_reference(oracle, scene, raw, up_color, up_phasor):
     a = assemble_ref.assemble_eager(cl["xyz"], ssp, torch.sigmoid(cl["opacity"]), torch.exp(cl["scaling"]),
                                     torch.nn.functional.normalize(cl["rotation"]), cl["rotation"], fc, fp,
                                     torch.zeros((P,), dtype=torch.bool), render_regions=("static",))
+    f = _through_the_rasterizer(oracle, scene, a, up_color, up_phasor)
+    out = {k: v.grad.numpy() for k, v in cl.items()}
+    out["ssp"] = ssp.grad.numpy()
+    return f, out
+
+
+def _through_the_rasterizer(oracle, scene, a, up_color, up_phasor):
+    """The C oracle of the rasterizer on the assembled inputs `a` (CPU tensors under autograd) under the upstream gradients
+    `up_color` / `up_phasor`; its gradients are pushed back through `a`.  Returns the oracle's forward."""
     inputs = dict(means3D=a[0].detach().numpy(), opacities=a[2].detach().numpy(), scales=a[3].detach().numpy(),
                   rotations=a[4].detach().numpy(), shs=a[5].detach().numpy(), shs_p=a[6].detach().numpy())
     grads = {k: np.zeros_like(v) for k, v in scene["grads"].items()}
     grads["color"], grads["phasor"] = up_color, up_phasor
     sc = dict(scene, grads=grads)
-    sc["cfg"] = dict(scene["cfg"], P=P)
+    sc["cfg"] = dict(scene["cfg"], P=a[0].shape[0])
     f, b = helpers.run_oracle(oracle, sc, inputs=inputs)
     up = [b["dL_dmeans3D"], b["dL_dmeans2D"], b["dL_dopacity"], b["dL_dscales"], b["dL_drotations"], b["dL_dsh"], b["dL_dsh_p"]]
     torch.autograd.backward(list(a), [torch.tensor(np.asarray(u, np.float32).reshape(tuple(o.shape))) for u, o in zip(up, a)])
-    out = {k: v.grad.numpy() for k, v in cl.items()}
-    out["ssp"] = ssp.grad.numpy()
-    return f, out
+    return f
+
+
+def dynamic_inputs(raw, mask, d_xyz=None, d_sh=None, render_regions=("static", "dynamic")):
+    """The rasterizer's inputs of a model with a motion mask, under CPU autograd: clones of the raw parameters `raw` (group
+    name -> CPU tensor) and of the network's offsets `d_xyz` [n, 3] / `d_sh` [n, 16, 3] (arrays; None: the scalar 0.0 of
+    train.py:164) as leaves, pc.get_* eagerly (scene/gaussian_model.py:123-153), then the reference's assembly
+    (gaussian_renderer/__init__.py:81-105; d_rot and d_sh_p are the zeros the network returns).  Returns (assembled
+    tensors, leaves by group name + "ssp" + "d_xyz" + "d_sh")."""
+    cl = {k: v.detach().clone().requires_grad_(True) for k, v in raw.items() if k != "f_seg_color"}
+    P = cl["xyz"].shape[0]
+    cl["ssp"] = torch.zeros((P, 3), requires_grad=True)
+    for k, d in (("d_xyz", d_xyz), ("d_sh", d_sh)):
+        if d is not None:
+            cl[k] = torch.tensor(np.asarray(d, np.float32), requires_grad=True)
+    fc = torch.cat((cl["f_dc_color"], cl["f_rest_color"]), dim=1)
+    fp = torch.cat((torch.cat((cl["phase_f_dc"], cl["phase_f_rest"]), dim=1), torch.cat((cl["amp_f_dc"], cl["amp_f_rest"]), dim=1)), dim=2)
+    a = assemble_ref.assemble_eager(cl["xyz"], cl["ssp"], torch.sigmoid(cl["opacity"]), torch.exp(cl["scaling"]),
+                                    torch.nn.functional.normalize(cl["rotation"]), cl["rotation"], fc, fp,
+                                    torch.as_tensor(mask, dtype=torch.bool), cl.get("d_xyz", 0.0), 0.0, cl.get("d_sh", 0.0), 0.0,
+                                    render_regions=render_regions)
+    return a, cl
+
+
+def composed_reference_dynamic(oracle, scene, raw, mask, d_xyz, d_sh, up_color, up_phasor, render_regions=("static", "dynamic")):
+    """:func:`composed_reference` for a model with a motion mask `mask` [P] and the network's offsets on its dynamic rows
+    (:func:`dynamic_inputs`).  Returns (oracle forward, gradients by group name + "ssp" + "d_xyz" (+ "d_sh")); a leaf that
+    nothing reached (the offsets of no dynamic row) has a zero gradient."""
+    a, cl = dynamic_inputs(raw, mask, d_xyz, d_sh, render_regions)
+    f = _through_the_rasterizer(oracle, scene, a, up_color, up_phasor)
+    return f, {k: (v.grad.numpy() if v.grad is not None else np.zeros(tuple(v.shape), np.float32)) for k, v in cl.items()}

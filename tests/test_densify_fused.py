@@ -343,17 +343,13 @@ def test_optimizer_continuity(optimizer):
     assert not torch.equal(a._xyz.detach(), moved_from)           # (the step moved something)
 
 
-class _Dynamic(densify_ref.EagerGaussians):
-    get_motion_mask = property(lambda self: (self._features_seg_color[:, 0] > 0.5).detach())      # gaussian_model.py:160-161
-
-
 @pytest.mark.gpu
 def test_motion_mask_and_side_tensors_stay_in_step():
     from gftorf_amd import densify
     from gftorf_amd.query import DeformQuery
     dev = torch.device("cuda:0")
     P = 20000
-    a = _Dynamic(P, dev, seed=5)
+    a = L.DynamicGaussians(P, dev, seed=5)
     g = torch.Generator().manual_seed(2)
     seg = 0.5 + 0.01 * torch.randn((P, 3), generator=g)
     seg[::7, 0] = 0.5                                            # exactly on the threshold: static

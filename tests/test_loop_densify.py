@@ -12,8 +12,9 @@ TEACHER FORCING: there is one trajectory, the product's.  Each checked step is c
 evaluated on the product's own state just before that step (Adam turns rounding noise into whole steps and a threshold
 turns it into another P: two free-running trajectories cannot be compared tightly enough to see a stale buffer).
 
-Not covered: the deformation network and a motion mask (keeping a mask in step with densification is a separate piece of
-work: every Gaussian is static here), the SH degree schedule, and the length of a real run (38 iterations, not 7 000).
+Every Gaussian is static here; the deformation network and a motion mask that densification keeps in step are carried through
+the same kind of loop by tests/test_loop_dynamic.py.  Not covered: the SH degree schedule, and the length of a real run (38
+iterations, not 7 000).
 
 CPU tests: the restated reset_opacity / replace_tensor_to_optimizer against a per-row loop, the twin copy, the thresholds."""
 import numpy as np
