@@ -157,6 +157,12 @@ ImgView gft_img_view(void* base, const gft_layout& L);
 BinView gft_bin_view(void* base, const gft_layout& L);
 
 int gft_fail(const char* fmt, ...);
+// after a function's launches: 0, or gft_fail with the launch error
+inline int gft_launched(const char* who)
+{
+    const hipError_t err = hipGetLastError();
+    return err == hipSuccess ? 0 : gft_fail("%s: %s", who, hipGetErrorString(err));
+}
 // zero fill by a kernel (gft_api.hip: hipMemsetAsync nodes misbehave in replayed graphs on this platform)
 hipError_t gft_zero_async(void* ptr, size_t bytes, hipStream_t s);
 #define GFT_CHECK_HIP(expr)                                                          \

@@ -5,6 +5,10 @@
 
 constexpr float TOF_TWO_PI = 6.283185307179586f, TOF_FOUR_PI = 12.566370614359172f, TOF_TINY = 1e-6f;
 
+// depth_range / phase_offset: the device's value when there is one, else the one passed by value (a reference, so that
+// a kernel argument is read only when it is the one taken)
+__device__ __forceinline__ float gft_dev_or(const float* dev, const float& v) { return dev ? *dev : v; }
+
 // torf_utils.py:60-64 in fp32, in its order
 __device__ __forceinline__ float depth_from_tof(float re, float im, float depth_range, float phase_offset)
 {

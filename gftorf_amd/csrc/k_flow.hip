@@ -1,9 +1,10 @@
 // k_flow.hip -- the F-ToRF scene-flow term, forward and backward, one launch each (include/gftorf_flow.h;
 // scene/torf_utils.py:80-124 as train.py:243-261 composes it), and the drop-ins distance_to_points3d / project_points /
-// project_flow through the same device helpers.  A grid-stride loop over the H*W pixels, wave64 shuffles and 4 LDS slots
-// reduce to one partial per workgroup and direction: the partial count depends on the shape alone, so sums are bit-reproducible.
+// project_flow through the same device helpers.  A grid-stride loop over the H*W pixels; stage one of gft_reduce.h gives one
+// partial per workgroup and direction.
 // Every camera matrix is read on the device at kernel entry; the 4x4 inverse is formed there, by every lane, in double.
 #include "gft_internal.h"
+#include "gft_reduce.h"
 #include "gftorf_flow.h"
 
 namespace {
@@ -13,11 +14,7 @@ namespace {
 constexpr int FLOW_THREADS = 256, FLOW_PER_THREAD = 1, FLOW_MAX_BLOCKS = 1024;
 constexpr float FLOW_EPS = 1e-7f;       // project_points' xy / (z + 1e-7): no clamp, no sign guard
 
-int flow_blocks(int64_t pixels)
-{
-    const int64_t b = (pixels + FLOW_THREADS * FLOW_PER_THREAD - 1) / (FLOW_THREADS * FLOW_PER_THREAD);
-    return (int)(b < 1 ? 1 : (b > FLOW_MAX_BLOCKS ? FLOW_MAX_BLOCKS : b));
-}
+int flow_blocks(int64_t pixels) { return (int)gft_grid_blocks(pixels, FLOW_THREADS, FLOW_PER_THREAD, FLOW_MAX_BLOCKS); }
 
 struct FlowArgs {
     int W, HW;
@@ -168,18 +165,9 @@ __global__ __launch_bounds__(FLOW_THREADS) void k_flow_fwd(FlowArgs p)
             s[k] += ex * ex + ey * ey;
         }
     }
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-        for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_xor(s[k], o);
-        if ((threadIdx.x & 63) == 0) sRed[k][threadIdx.x >> 6] = s[k];
-    }
+    gft_fold_store<FLOW_THREADS>(s, sRed);
     __syncthreads();
-    if (threadIdx.x < 2) {
-        const int k = threadIdx.x;
-        float t = 0.f;
-        for (int w = 0; w < FLOW_THREADS / 64; w++) t += sRed[k][w];
-        p.partials[blockIdx.x * 2 + k] = t * p.scale;
-    }
+    if (threadIdx.x < 2) p.partials[blockIdx.x * 2 + threadIdx.x] = gft_waves_total<FLOW_THREADS>(sRed[threadIdx.x]) * p.scale;
 }
 
 __global__ __launch_bounds__(FLOW_THREADS) void k_flow_bwd(FlowArgs p)
@@ -253,12 +241,6 @@ int flow_sizes(FlowArgs& p, int32_t H, int32_t W, const char* who)
     return 0;
 }
 
-int launched(const char* who)
-{
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : gft_fail("%s: %s", who, hipGetErrorString(err));
-}
-
 }  // namespace
 
 extern "C" int64_t gft_flow_loss_blocks(int32_t H, int32_t W)
@@ -281,7 +263,7 @@ extern "C" int gft_flow_loss_forward(void* hip_stream, int32_t H, int32_t W, con
     p.flow[0] = flow3d_fwd; p.flow[1] = flow3d_bwd; p.gt[0] = gt_fwd; p.gt[1] = gt_bwd;
     p.scale = scale; p.partials = partials;
     hipLaunchKernelGGL(k_flow_fwd, dim3(flow_blocks(p.HW)), dim3(FLOW_THREADS), 0, (hipStream_t)hip_stream, p);
-    return launched(who);
+    return gft_launched(who);
 }
 
 extern "C" int gft_flow_loss_backward(void* hip_stream, int32_t H, int32_t W, const float* depth, const float* K,
@@ -300,7 +282,7 @@ extern "C" int gft_flow_loss_backward(void* hip_stream, int32_t H, int32_t W, co
     p.grad[0] = flow3d_fwd ? grad_fwd : nullptr; p.grad[1] = flow3d_bwd ? grad_bwd : nullptr;
     if (!p.grad[0] && !p.grad[1]) return 0;
     hipLaunchKernelGGL(k_flow_bwd, dim3(flow_blocks(p.HW)), dim3(FLOW_THREADS), 0, (hipStream_t)hip_stream, p);
-    return launched(who);
+    return gft_launched(who);
 }
 
 extern "C" int gft_flow_points(void* hip_stream, int32_t H, int32_t W, const float* depth, const float* K, const float* w2v,
@@ -313,7 +295,7 @@ extern "C" int gft_flow_points(void* hip_stream, int32_t H, int32_t W, const flo
     if (points2d && (!K_tof || !w2v_tof)) return gft_fail("%s: points2d needs K_tof and w2v_tof", who);
     p.depth = depth; p.K = K; p.w2v = w2v; p.K_tof = K_tof; p.w2v_tof = w2v_tof; p.out3d = points3d; p.out2d = points2d;
     hipLaunchKernelGGL(k_flow_points, dim3(flow_blocks(p.HW)), dim3(FLOW_THREADS), 0, (hipStream_t)hip_stream, p);
-    return launched(who);
+    return gft_launched(who);
 }
 
 extern "C" int gft_flow_project(void* hip_stream, int32_t H, int32_t W, const float* K_tof, const float* w2v_tof,
@@ -325,7 +307,7 @@ extern "C" int gft_flow_project(void* hip_stream, int32_t H, int32_t W, const fl
     if (!K_tof || !w2v_tof || !points3d || !out) return gft_fail("%s: NULL argument", who);
     p.K_tof = K_tof; p.w2v_tof = w2v_tof; p.points3d = points3d; p.flow[0] = flow3d; p.points2d = points2d_curr; p.out2d = out;
     hipLaunchKernelGGL(k_flow_project, dim3(flow_blocks(p.HW)), dim3(FLOW_THREADS), 0, (hipStream_t)hip_stream, p);
-    return launched(who);
+    return gft_launched(who);
 }
 
 extern "C" int gft_flow_project_backward(void* hip_stream, int32_t H, int32_t W, const float* K_tof, const float* w2v_tof,
@@ -338,5 +320,5 @@ extern "C" int gft_flow_project_backward(void* hip_stream, int32_t H, int32_t W,
     p.K_tof = K_tof; p.w2v_tof = w2v_tof; p.points3d = points3d; p.flow[0] = flow3d; p.grad_out = grad_out;
     p.grad[0] = grad_flow3d;
     hipLaunchKernelGGL(k_flow_project_bwd, dim3(flow_blocks(p.HW)), dim3(FLOW_THREADS), 0, (hipStream_t)hip_stream, p);
-    return launched(who);
+    return gft_launched(who);
 }

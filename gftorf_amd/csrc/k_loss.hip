@@ -3,6 +3,7 @@
 // zero padding outside the image) goes through LDS, the window is applied as its two 1-D factors (rows, then columns).  The
 // pixel term is a template parameter (GFT_PIXEL_*); the pixel-only kernels at the end are for a term without SSIM.
 #include "gft_internal.h"
+#include "gft_reduce.h"
 #include "gftorf_loss.h"
 
 #include <type_traits>
@@ -40,8 +41,6 @@ __device__ __forceinline__ float pixel_weight(const float* __restrict__ a, size_
         return 1.f;
     }
 }
-
-__device__ __forceinline__ float sign_of(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }
 
 // value of the term for d = a - b and weight wt
 template <int KIND>
@@ -137,14 +136,12 @@ __global__ __launch_bounds__(TS * TS) void k_ssim_pix_fwd(LossArgs p)
             p.maps[2 * N + o] = ds12;
         }
     }
-    for (int o = 32; o > 0; o >>= 1) { ssim += __shfl_xor(ssim, o); sq += __shfl_xor(sq, o); }
-    if ((tid & 63) == 0) { sRed[0][tid >> 6] = ssim; sRed[1][tid >> 6] = sq; }
+    float s[2] = {ssim, sq};
+    gft_fold_store<TS * TS>(s, sRed);          // the two sums of this tile in the order of gft_reduce.h
     __syncthreads();
     if (tid == 0) {
-        float s0 = 0.f, s1 = 0.f;
-        for (int k = 0; k < TS * TS / 64; k++) { s0 += sRed[0][k]; s1 += sRed[1][k]; }
-        p.partials[2 * (size_t)blockIdx.x] = s0;
-        p.partials[2 * (size_t)blockIdx.x + 1] = s1;
+        p.partials[2 * (size_t)blockIdx.x] = gft_waves_total<TS * TS>(sRed[0]);
+        p.partials[2 * (size_t)blockIdx.x + 1] = gft_waves_total<TS * TS>(sRed[1]);
     }
 }
 
@@ -191,14 +188,10 @@ __global__ __launch_bounds__(TS * TS) void k_ssim_pix_bwd(LossArgs p)
 }
 
 // Pixel term alone: a grid-stride loop over the pixels, no LDS patch, no halo, no maps.  Each thread takes the first n channels
-// of its pixels (one weight per pixel for WEIGHTED_L1), wave64 shuffles and 4 LDS slots reduce to one partial per workgroup.
+// of its pixels (one weight per pixel for WEIGHTED_L1); stage one of gft_reduce.h gives one partial per workgroup.
 constexpr int PIX_THREADS = 256, PIX_PER_THREAD = 4, PIX_MAX_BLOCKS = 1024;
 
-int pix_blocks(int64_t pixels)
-{
-    const int64_t b = (pixels + PIX_THREADS * PIX_PER_THREAD - 1) / (PIX_THREADS * PIX_PER_THREAD);
-    return (int)(b < 1 ? 1 : (b > PIX_MAX_BLOCKS ? PIX_MAX_BLOCKS : b));
-}
+int pix_blocks(int64_t pixels) { return (int)gft_grid_blocks(pixels, PIX_THREADS, PIX_PER_THREAD, PIX_MAX_BLOCKS); }
 
 struct PixArgs {
     int C, n;
@@ -226,14 +219,9 @@ __global__ __launch_bounds__(PIX_THREADS) void k_pix_fwd(PixArgs p)
             s += pixel_value<KIND>(va - vb, wt);
         }
     }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if ((threadIdx.x & 63) == 0) sRed[threadIdx.x >> 6] = s;
+    gft_fold_store<PIX_THREADS>(s, sRed);
     __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = 0.f;
-        for (int k = 0; k < PIX_THREADS / 64; k++) t += sRed[k];
-        p.partials[blockIdx.x] = t * p.scale;
-    }
+    if (threadIdx.x == 0) p.partials[blockIdx.x] = gft_waves_total<PIX_THREADS>(sRed) * p.scale;
 }
 
 // grad over all C channels: the term's gradient on the first n, 0 on the rest
@@ -279,7 +267,7 @@ int check_kind(int32_t kind, int32_t C, int32_t n, const char* who)
 
 // f(std::integral_constant<int, KIND>) for the kind: one instantiation per kind of each kernel
 template <typename F>
-hipError_t by_kind(int32_t kind, F&& f)
+void by_kind(int32_t kind, F&& f)
 {
     switch (kind) {
     case GFT_PIXEL_L2: f(std::integral_constant<int, GFT_PIXEL_L2>{}); break;
@@ -288,7 +276,6 @@ hipError_t by_kind(int32_t kind, F&& f)
     case GFT_PIXEL_WEIGHTED_L1_QUAD: f(std::integral_constant<int, GFT_PIXEL_WEIGHTED_L1_QUAD>{}); break;
     default: f(std::integral_constant<int, GFT_PIXEL_WEIGHTED_L2_QUAD>{}); break;
     }
-    return hipGetLastError();
 }
 
 int image_forward(void* hip_stream, int32_t kind, int32_t C, int32_t H, int32_t W, int32_t n, float e, const float* img1,
@@ -300,10 +287,10 @@ int image_forward(void* hip_stream, int32_t kind, int32_t C, int32_t H, int32_t 
     p.n = n; p.e = e; p.maps = maps; p.partials = partials;
     const int64_t blocks = gft_ssim_blocks(C, H, W);
     if (blocks > 0x7fffffffll) return gft_fail("%s: image too large", who);
-    const hipError_t err = by_kind(kind, [&](auto k) {
+    by_kind(kind, [&](auto k) {
         hipLaunchKernelGGL(k_ssim_pix_fwd<decltype(k)::value>, dim3((unsigned)blocks), dim3(TS * TS), 0, (hipStream_t)hip_stream, p);
     });
-    return err == hipSuccess ? 0 : gft_fail("%s: %s", who, hipGetErrorString(err));
+    return gft_launched(who);
 }
 
 int image_backward(void* hip_stream, int32_t kind, int32_t C, int32_t H, int32_t W, int32_t n, float e, const float* img1,
@@ -318,10 +305,10 @@ int image_backward(void* hip_stream, int32_t kind, int32_t C, int32_t H, int32_t
     p.grad = grad_img1;
     const int64_t blocks = gft_ssim_blocks(C, H, W);
     if (blocks > 0x7fffffffll) return gft_fail("%s: image too large", who);
-    const hipError_t err = by_kind(kind, [&](auto k) {
+    by_kind(kind, [&](auto k) {
         hipLaunchKernelGGL(k_ssim_pix_bwd<decltype(k)::value>, dim3((unsigned)blocks), dim3(TS * TS), 0, (hipStream_t)hip_stream, p);
     });
-    return err == hipSuccess ? 0 : gft_fail("%s: %s", who, hipGetErrorString(err));
+    return gft_launched(who);
 }
 
 }  // namespace
@@ -384,10 +371,10 @@ extern "C" int gft_pixel_loss_forward(void* hip_stream, int32_t kind, int32_t C,
     if (pix_fill(p, kind, C, H, W, n, e, scale, img1, img2, "gft_pixel_loss_forward")) return 1;
     if (!partials) return gft_fail("gft_pixel_loss_forward: partials is NULL");
     p.partials = partials;
-    const hipError_t err = by_kind(kind, [&](auto k) {
+    by_kind(kind, [&](auto k) {
         hipLaunchKernelGGL(k_pix_fwd<decltype(k)::value>, dim3(pix_blocks(p.HW)), dim3(PIX_THREADS), 0, (hipStream_t)hip_stream, p);
     });
-    return err == hipSuccess ? 0 : gft_fail("gft_pixel_loss_forward: %s", hipGetErrorString(err));
+    return gft_launched("gft_pixel_loss_forward");
 }
 
 extern "C" int gft_pixel_loss_backward(void* hip_stream, int32_t kind, int32_t C, int32_t H, int32_t W, int32_t n, float e,
@@ -398,8 +385,8 @@ extern "C" int gft_pixel_loss_backward(void* hip_stream, int32_t kind, int32_t C
     if (pix_fill(p, kind, C, H, W, n, e, scale, img1, img2, "gft_pixel_loss_backward")) return 1;
     if (!g_pixel || !grad_img1) return gft_fail("gft_pixel_loss_backward: NULL argument");
     p.g = g_pixel; p.grad = grad_img1;
-    const hipError_t err = by_kind(kind, [&](auto k) {
+    by_kind(kind, [&](auto k) {
         hipLaunchKernelGGL(k_pix_bwd<decltype(k)::value>, dim3(pix_blocks(p.HW)), dim3(PIX_THREADS), 0, (hipStream_t)hip_stream, p);
     });
-    return err == hipSuccess ? 0 : gft_fail("gft_pixel_loss_backward: %s", hipGetErrorString(err));
+    return gft_launched("gft_pixel_loss_backward");
 }

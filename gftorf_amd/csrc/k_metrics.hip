@@ -1,11 +1,11 @@
 // k_metrics.hip -- a view's evaluation metrics (include/gftorf_metrics.h; train.py:535-579).  k_metrics_sums: one grid-stride
-// loop in the shape of k_tof_log_sums (k_tof.hip) over the pixels of up to eight plane pairs in two groups with pixel counts
-// of their own, the loop running to the larger count and every group guarded: per-lane fp32 sums of |a - b| and (a - b)^2,
-// widened to double for the wave64 shuffles and the 4 LDS slots that give one row of partials per workgroup (a lane sums two
-// pixels of a 640x480 view; the 256 lanes' sums are then added without a rounding of their own).  k_metrics_finish adds the rows in a fixed order in
-// double, forms the eight values, writes the row and lets one thread add them into the accumulator.  No atomics, no memset,
-// scalar loads only (each coalesced across the wave; the pass moves 8 bytes per pixel and pair).
+// loop over the pixels of up to eight plane pairs in two groups with pixel counts of their own, the loop running to the larger
+// count and every group guarded: per-lane fp32 sums of |a - b| and (a - b)^2, widened to double for the two stages of
+// gft_reduce.h (a lane sums two pixels of a 640x480 view; the 256 lanes' sums are then added without a rounding of their
+// own).  k_metrics_finish forms the eight values, writes the row and lets one thread add them into the accumulator.  Scalar
+// loads only (each coalesced across the wave; the pass moves 8 bytes per pixel and pair).
 #include "gft_internal.h"
+#include "gft_reduce.h"
 #include "gft_tof_depth.h"
 #include "gftorf_metrics.h"
 
@@ -37,11 +37,7 @@ struct MetArgs {
     uint32_t* accum;                            // [GFT_METRICS_ACC_WORDS] or NULL
 };
 
-int64_t met_blocks(int64_t total)
-{
-    const int64_t b = (total + MET_THREADS - 1) / MET_THREADS;
-    return b < 1 ? 1 : (b > MET_MAX_BLOCKS ? MET_MAX_BLOCKS : b);
-}
+int64_t met_blocks(int64_t total) { return gft_grid_blocks(total, MET_THREADS, 1, MET_MAX_BLOCKS); }
 
 __global__ __launch_bounds__(MET_THREADS) void k_metrics_sums(MetArgs p)
 {
@@ -49,8 +45,7 @@ __global__ __launch_bounds__(MET_THREADS) void k_metrics_sums(MetArgs p)
     float s[MET_SUMS];
 #pragma unroll
     for (int k = 0; k < MET_SUMS; k++) s[k] = 0.f;
-    const float dr = p.depth_range_dev ? *p.depth_range_dev : p.depth_range;
-    const float off = p.phase_offset_dev ? *p.phase_offset_dev : p.phase_offset;
+    const float dr = gft_dev_or(p.depth_range_dev, p.depth_range), off = gft_dev_or(p.phase_offset_dev, p.phase_offset);
     const int64_t total = p.pixels_a > p.pixels_b ? p.pixels_a : p.pixels_b;
     for (int64_t i = (int64_t)blockIdx.x * MET_THREADS + threadIdx.x; i < total; i += (int64_t)gridDim.x * MET_THREADS) {
         const bool in_a = i < p.pixels_a, in_b = i < p.pixels_b;
@@ -71,21 +66,9 @@ __global__ __launch_bounds__(MET_THREADS) void k_metrics_sums(MetArgs p)
     double w[MET_SUMS];
 #pragma unroll
     for (int k = 0; k < MET_SUMS; k++) w[k] = (double)s[k];
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int k = 0; k < MET_SUMS; k++) w[k] += __shfl_xor(w[k], o);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < MET_SUMS; k++) sRed[k][threadIdx.x >> 6] = w[k];
-    }
+    gft_fold_store<MET_THREADS>(w, sRed);
     __syncthreads();
-    if (threadIdx.x < MET_SUMS) {
-        const int k = threadIdx.x;
-        double t = sRed[k][0];
-        for (int v = 1; v < MET_THREADS / 64; v++) t += sRed[k][v];
-        p.partials[(size_t)blockIdx.x * MET_SUMS + k] = t;
-    }
+    if (threadIdx.x < MET_SUMS) p.partials[(size_t)blockIdx.x * MET_SUMS + threadIdx.x] = gft_waves_total<MET_THREADS>(sRed[threadIdx.x]);
 }
 
 // utils/image_utils.py:18-19 on one plane's mse, in double: +inf at 0
@@ -110,14 +93,7 @@ __global__ __launch_bounds__(MET_THREADS) void k_metrics_finish(MetArgs p)
     }
 #pragma unroll
     for (int k = 0; k < MET_SUMS; k++) sSum[k][tid] = s[k];
-    __syncthreads();
-    for (int h = MET_THREADS / 2; h > 0; h >>= 1) {
-        if (tid < h) {
-#pragma unroll
-            for (int k = 0; k < MET_SUMS; k++) sSum[k][tid] += sSum[k][tid + h];
-        }
-        __syncthreads();
-    }
+    gft_tree_sum<MET_THREADS>(sSum);
     if (tid != 0) return;
     const double na = (double)p.pixels_a, nb = (double)p.pixels_b;
     const int n_planes = p.n_mem + (p.phasor ? 1 : 0);
@@ -230,14 +206,12 @@ extern "C" int gft_view_metrics(void* hip_stream, int64_t pixels_a, int32_t chan
     hipStream_t s = (hipStream_t)hip_stream;
     hipLaunchKernelGGL(k_metrics_sums, dim3(p.blocks), dim3(MET_THREADS), 0, s, p);
     hipLaunchKernelGGL(k_metrics_finish, dim3(1), dim3(MET_THREADS), 0, s, p);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : gft_fail("gft_view_metrics: %s", hipGetErrorString(err));
+    return gft_launched("gft_view_metrics");
 }
 
 extern "C" int gft_metrics_reset(void* hip_stream, void* accum)
 {
     if (!accum || ((uintptr_t)accum & 7u)) return gft_fail("gft_metrics_reset: accum is NULL or not 8-byte aligned");
     hipLaunchKernelGGL(k_metrics_reset, dim3(1), dim3(64), 0, (hipStream_t)hip_stream, static_cast<uint32_t*>(accum));
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : gft_fail("gft_metrics_reset: %s", hipGetErrorString(err));
+    return gft_launched("gft_metrics_reset");
 }

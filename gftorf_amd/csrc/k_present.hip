@@ -10,6 +10,7 @@
 // The arithmetic is numpy's float32 sequence operation for operation: nothing here may contract into a multiply-add, and
 // every division is the correctly rounded one (hipcc's default for fp32 `/`).  min and max propagate a NaN as np.min / np.max.
 #include "gft_internal.h"
+#include "gft_reduce.h"
 #include "gft_tof_depth.h"
 #include "gft_present_magma.h"
 #include "gftorf_present.h"
@@ -47,11 +48,7 @@ struct PresentArgs {
     uint8_t* out[PRS_IMAGES];                   // NULL for an image the groups do not produce
 };
 
-int64_t prs_blocks(int64_t pixels)
-{
-    const int64_t b = (pixels + PRS_THREADS - 1) / PRS_THREADS;
-    return b < 1 ? 1 : (b > PRS_MAX_BLOCKS ? PRS_MAX_BLOCKS : b);
-}
+int64_t prs_blocks(int64_t pixels) { return gft_grid_blocks(pixels, PRS_THREADS, 1, PRS_MAX_BLOCKS); }
 
 // np.minimum / np.maximum: a NaN on either side is the result
 __device__ __forceinline__ float nmin(float a, float b) { return a != a ? a : (b != b ? b : (b < a ? b : a)); }
@@ -163,8 +160,7 @@ __global__ __launch_bounds__(PRS_THREADS) void k_present_view(PresentArgs p)
 #pragma unroll
     for (int k = 0; k < GFT_PRESENT_RANGE_WORDS; k++) rg[k] = p.ranges_dev ? p.ranges_dev[k] : p.ranges[k];
     const float re_lo = rg[0], re_span = rg[1] - rg[0], im_lo = rg[2], im_span = rg[3] - rg[2], am_lo = rg[4], am_span = rg[5] - rg[4];
-    const float dr = p.depth_range_dev ? *p.depth_range_dev : p.depth_range;
-    const float off = p.phase_offset_dev ? *p.phase_offset_dev : p.phase_offset;
+    const float dr = gft_dev_or(p.depth_range_dev, p.depth_range), off = gft_dev_or(p.phase_offset_dev, p.phase_offset);
     const float span = p.zfar - p.znear;
     const bool quad = p.out[GFT_PRESENT_QUAD] != nullptr;
     __syncthreads();
@@ -363,8 +359,7 @@ extern "C" int gft_present_view(void* hip_stream, int32_t H, int32_t W, const fl
     hipStream_t s = (hipStream_t)hip_stream;
     if (dd) hipLaunchKernelGGL(k_present_minmax, dim3(p.blocks), dim3(PRS_THREADS), 0, s, p);
     hipLaunchKernelGGL(k_present_view, dim3(p.blocks), dim3(PRS_THREADS), 0, s, p);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : gft_fail("gft_present_view: %s", hipGetErrorString(err));
+    return gft_launched("gft_present_view");
 }
 
 extern "C" int gft_present_ranges(void* hip_stream, int64_t pixels, const float* gt_tof, int64_t stride, void* partials, float* ranges)
@@ -377,14 +372,12 @@ extern "C" int gft_present_ranges(void* hip_stream, int64_t pixels, const float*
     hipStream_t s = (hipStream_t)hip_stream;
     hipLaunchKernelGGL(k_present_ranges_part, dim3(blocks), dim3(PRS_THREADS), 0, s, pixels, gt_tof, stride, static_cast<float*>(partials));
     hipLaunchKernelGGL(k_present_ranges_finish, dim3(1), dim3(PRS_THREADS), 0, s, blocks, static_cast<const float*>(partials), ranges);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : gft_fail("gft_present_ranges: %s", hipGetErrorString(err));
+    return gft_launched("gft_present_ranges");
 }
 
 extern "C" int gft_present_ranges_reset(void* hip_stream, float* ranges)
 {
     if (!ranges) return gft_fail("gft_present_ranges_reset: ranges is NULL");
     hipLaunchKernelGGL(k_present_ranges_reset, dim3(1), dim3(64), 0, (hipStream_t)hip_stream, ranges);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : gft_fail("gft_present_ranges_reset: %s", hipGetErrorString(err));
+    return gft_launched("gft_present_ranges_reset");
 }

@@ -113,8 +113,7 @@ __global__ __launch_bounds__(QR_THREADS) void k_query_combine(CombineArgs a)
 int combine_launch(hipStream_t s, CombineArgs& a, const char* who)
 {
     hipLaunchKernelGGL(k_query_combine, dim3(qr_blocks(a.total)), dim3(QR_THREADS), 0, s, a);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : gft_fail("%s: %s", who, hipGetErrorString(err));
+    return gft_launched(who);
 }
 
 int combine_sizes(int64_t n, int32_t K, int32_t M, const char* who)
@@ -147,8 +146,7 @@ extern "C" int gft_query_inputs(void* hip_stream, int64_t P, const float* xyz, c
         for (int k = 0; k < K; k++) a.times[k] = times_host[k];
     a.scale = scale; a.K = K; a.x = x; a.t = t;
     hipLaunchKernelGGL(k_query_inputs, dim3(qr_blocks(a.items)), dim3(QR_THREADS), 0, (hipStream_t)hip_stream, a);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : gft_fail("gft_query_inputs: %s", hipGetErrorString(err));
+    return gft_launched("gft_query_inputs");
 }
 
 extern "C" int gft_query_combine(void* hip_stream, int64_t n, int32_t K, int32_t M, const float* d, const float* coeffs_dev,

@@ -1,11 +1,11 @@
 // k_reg.hip -- the per-Gaussian regularisers of the training loss, forward and backward (include/gftorf_reg.h;
 // train.py:237-240 motion, :266-267 depth distortion, :270-272 opacity entropy, :275-277 scale).  One grid-stride loop over
 // the concatenation of the four inputs -- the floats of d_xyz, the rows of opacity, the rows of scaling, the floats of the
-// distortion image -- in the shape of k_pix_fwd / k_pix_bwd (k_loss.hip): wave64 shuffles and 4 LDS slots reduce to one row
-// of partials per workgroup, k_reg_finish adds the rows in a fixed order in double.  No atomics, no memset, scalar loads and
-// stores only (callers pass views such as d_xyz[1:]: nothing is assumed of a pointer beyond its element's alignment; the
-// whole pass moves ~21 bytes per Gaussian and is bound by its launches, not by its loads).
+// distortion image --, summed in the two stages and the order of gft_reduce.h.  Scalar loads and stores only (callers pass
+// views such as d_xyz[1:]: nothing is assumed of a pointer beyond its element's alignment; the whole pass moves ~21 bytes per
+// Gaussian and is bound by its launches, not by its loads).
 #include "gft_internal.h"
+#include "gft_reduce.h"
 #include "gftorf_reg.h"
 
 namespace {
@@ -33,24 +33,13 @@ struct RegArgs {
     float* g_dd;
 };
 
-int64_t reg_blocks(int64_t total)
-{
-    const int64_t b = (total + REG_THREADS * REG_PER_THREAD - 1) / (REG_THREADS * REG_PER_THREAD);
-    return b < 1 ? 1 : (b > REG_MAX_BLOCKS ? REG_MAX_BLOCKS : b);
-}
-
-__device__ __forceinline__ float sign_of(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }
+int64_t reg_blocks(int64_t total) { return gft_grid_blocks(total, REG_THREADS, REG_PER_THREAD, REG_MAX_BLOCKS); }
 
 // torch's fp32 sigmoid expression, as k_assemble.hip's
 __device__ __forceinline__ float opacity_of(const RegArgs& p, int64_t r)
 {
     const float x = p.opacity[r];
     return p.opacity_is_raw ? 1.0f / (1.0f + expf(-x)) : x;
-}
-
-__device__ __forceinline__ bool visible_row(const RegArgs& p, int64_t r)
-{
-    return p.visible_is_radii ? static_cast<const int32_t*>(p.visible)[r] > 0 : static_cast<const uint8_t*>(p.visible)[r] != 0;
 }
 
 // the row's activated scales; with one column the value three times (gaussian_model.py:125 repeats it)
@@ -85,7 +74,7 @@ __global__ __launch_bounds__(REG_THREADS) void k_reg_fwd(RegArgs p)
             }
         } else if (i < eC) {
             const int64_t r = i - eB;
-            if (visible_row(p, r)) {
+            if (gft_visible_row(p.visible, p.visible_is_radii, r)) {
                 float v[3];
                 scales_of(p, r, v);
                 const float m = p.scaling_cols == 3 ? (v[0] + v[1] + v[2]) / 3.0f : v[0];
@@ -96,33 +85,13 @@ __global__ __launch_bounds__(REG_THREADS) void k_reg_fwd(RegArgs p)
             s[3] += p.dd[i - eC];
         }
     }
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int k = 0; k < 4; k++) s[k] += __shfl_xor(s[k], o);
-        n[0] += (uint32_t)__shfl_xor((int)n[0], o);
-        n[1] += (uint32_t)__shfl_xor((int)n[1], o);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 4; k++) sRed[k][threadIdx.x >> 6] = s[k];
-        sCnt[0][threadIdx.x >> 6] = n[0];
-        sCnt[1][threadIdx.x >> 6] = n[1];
-    }
+    gft_fold_store<REG_THREADS>(s, sRed);
+    gft_fold_store<REG_THREADS>(n, sCnt);
     __syncthreads();
     if (threadIdx.x < GFT_REG_PARTIAL_WORDS) {
-        uint32_t* row = p.partials + (size_t)blockIdx.x * GFT_REG_PARTIAL_WORDS;
         const int k = threadIdx.x;
-        if (k < 4) {
-            float t = sRed[k][0];
-            for (int w = 1; w < REG_THREADS / 64; w++) t += sRed[k][w];
-            row[k] = __float_as_uint(t);
-        } else if (k < 6) {
-            uint32_t t = 0;
-            for (int w = 0; w < REG_THREADS / 64; w++) t += sCnt[k - 4][w];
-            row[k] = t;
-        } else {
-            row[k] = 0u;
-        }
+        p.partials[(size_t)blockIdx.x * GFT_REG_PARTIAL_WORDS + k] =
+            k < 4 ? __float_as_uint(gft_waves_total<REG_THREADS>(sRed[k])) : (k < 6 ? gft_waves_total<REG_THREADS>(sCnt[k - 4]) : 0u);
     }
 }
 
@@ -145,16 +114,7 @@ __global__ __launch_bounds__(REG_THREADS) void k_reg_finish(RegArgs p)
     for (int k = 0; k < 4; k++) sSum[k][tid] = s[k];
     sCnt[0][tid] = n[0];
     sCnt[1][tid] = n[1];
-    __syncthreads();
-    for (int h = REG_THREADS / 2; h > 0; h >>= 1) {
-        if (tid < h) {
-#pragma unroll
-            for (int k = 0; k < 4; k++) sSum[k][tid] += sSum[k][tid + h];
-            sCnt[0][tid] += sCnt[0][tid + h];
-            sCnt[1][tid] += sCnt[1][tid + h];
-        }
-        __syncthreads();
-    }
+    gft_tree_sum<REG_THREADS>(sSum, sCnt);
     if (tid != 0) return;
     const unsigned long long n_dyn = sCnt[0][0], n_vis = sCnt[1][0];
     const double recip[4] = {p.nA > 0 ? 1.0 / (double)p.nA : 0.0, 1.0 / (double)(n_dyn > 0 ? n_dyn : 1ull),
@@ -205,7 +165,7 @@ __global__ __launch_bounds__(REG_THREADS) void k_reg_bwd(RegArgs p)
         } else if (i < eC) {
             const int64_t r = i - eB;
             double gs[3] = {0.0, 0.0, 0.0};
-            if (visible_row(p, r)) {
+            if (gft_visible_row(p.visible, p.visible_is_radii, r)) {
                 double v[3];
                 if (p.scaling_cols == 3) {
                     v[0] = (double)p.scaling[3 * r]; v[1] = (double)p.scaling[3 * r + 1]; v[2] = (double)p.scaling[3 * r + 2];
@@ -289,8 +249,7 @@ extern "C" int gft_reg_forward(void* hip_stream, int64_t n_dxyz, int64_t P, int6
     hipStream_t s = (hipStream_t)hip_stream;
     hipLaunchKernelGGL(k_reg_fwd, dim3(p.blocks), dim3(REG_THREADS), 0, s, p);
     hipLaunchKernelGGL(k_reg_finish, dim3(1), dim3(REG_THREADS), 0, s, p);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : gft_fail("gft_reg_forward: %s", hipGetErrorString(err));
+    return gft_launched("gft_reg_forward");
 }
 
 extern "C" int gft_reg_backward(void* hip_stream, int64_t n_dxyz, int64_t P, int64_t pixels, const float* d_xyz,
@@ -317,6 +276,5 @@ extern "C" int gft_reg_backward(void* hip_stream, int64_t n_dxyz, int64_t P, int
     const int64_t total = p.nA + p.nB + p.nC + p.nD;
     if (total == 0) return 0;
     hipLaunchKernelGGL(k_reg_bwd, dim3((unsigned)reg_blocks(total)), dim3(REG_THREADS), 0, (hipStream_t)hip_stream, p);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : gft_fail("gft_reg_backward: %s", hipGetErrorString(err));
+    return gft_launched("gft_reg_backward");
 }

@@ -1,11 +1,11 @@
 // k_tof.hip -- the ToF depth of scene/torf_utils.py:59-64 and the scalars of the training log (include/gftorf_tof.h;
 // train.py:188-200, 402-433).  k_tof_depth: one pixel per thread, grid-stride.  k_tof_log_sums: one grid-stride loop over
-// the concatenation of the pixels and the Gaussians' amplitude coefficients in the shape of k_reg_fwd (k_reg.hip): per-lane
-// fp32 sums, wave64 shuffles and 4 LDS slots to one row of partials per workgroup; k_tof_log_finish adds the rows in a fixed
-// order in double, writes the log's row (into a ring when there is a cursor) and advances the cursor.  No atomics, no memset,
-// scalar loads only (a pixel's nine loads are each coalesced across the wave; the pass moves 36 bytes per pixel, and per
-// Gaussian one float amp_stride floats from the last one's plus its visibility).
+// the concatenation of the pixels and the Gaussians' amplitude coefficients, summed in the two stages and the order of
+// gft_reduce.h; k_tof_log_finish writes the log's row (into a ring when there is a cursor) and advances the cursor.  Scalar
+// loads only (a pixel's nine loads are each coalesced across the wave; the pass moves 36 bytes per pixel, and per Gaussian
+// one float amp_stride floats from the last one's plus its visibility).
 #include "gft_internal.h"
+#include "gft_reduce.h"
 #include "gft_tof_depth.h"
 #include "gftorf_tof.h"
 
@@ -41,19 +41,14 @@ struct TofArgs {
     uint32_t* cursor;                           // or NULL
 };
 
-int64_t tof_blocks(int64_t total)
-{
-    const int64_t b = (total + TOF_THREADS - 1) / TOF_THREADS;
-    return b < 1 ? 1 : (b > TOF_MAX_BLOCKS ? TOF_MAX_BLOCKS : b);
-}
+int64_t tof_blocks(int64_t total) { return gft_grid_blocks(total, TOF_THREADS, 1, TOF_MAX_BLOCKS); }
 
 __global__ __launch_bounds__(TOF_THREADS) void k_tof_depth(int64_t pixels, const float* __restrict__ tof, int64_t plane_stride,
                                                            const float* __restrict__ depth_range_dev, float depth_range,
                                                            const float* __restrict__ phase_offset_dev, float phase_offset,
                                                            float* __restrict__ out)
 {
-    const float dr = depth_range_dev ? *depth_range_dev : depth_range;
-    const float off = phase_offset_dev ? *phase_offset_dev : phase_offset;
+    const float dr = gft_dev_or(depth_range_dev, depth_range), off = gft_dev_or(phase_offset_dev, phase_offset);
     for (int64_t i = (int64_t)blockIdx.x * TOF_THREADS + threadIdx.x; i < pixels; i += (int64_t)gridDim.x * TOF_THREADS)
         out[i] = depth_from_tof(tof[i], tof[plane_stride + i], dr, off);
 }
@@ -66,8 +61,7 @@ __global__ __launch_bounds__(TOF_THREADS) void k_tof_log_sums(TofArgs p)
 #pragma unroll
     for (int k = 0; k < TOF_SUMS; k++) s[k] = 0.f;
     uint32_t n = 0u;
-    const float dr = p.depth_range_dev ? *p.depth_range_dev : p.depth_range;
-    const float off = p.phase_offset_dev ? *p.phase_offset_dev : p.phase_offset;
+    const float dr = gft_dev_or(p.depth_range_dev, p.depth_range), off = gft_dev_or(p.phase_offset_dev, p.phase_offset);
     const int64_t total = p.pixels + p.P;
     for (int64_t i = (int64_t)blockIdx.x * TOF_THREADS + threadIdx.x; i < total; i += (int64_t)gridDim.x * TOF_THREADS) {
         if (i < p.pixels) {
@@ -91,39 +85,19 @@ __global__ __launch_bounds__(TOF_THREADS) void k_tof_log_sums(TofArgs p)
             const int64_t r = i - p.pixels;
             const float v = p.amp[r * p.amp_stride] * TOF_SH_C0 + 0.5f;          // sh_utils.py SH2PA
             s[GFT_TOF_LOG_GS_SP] += v;
-            if (p.visible) {
-                const bool vis = p.visible_is_radii ? static_cast<const int32_t*>(p.visible)[r] > 0
-                                                    : static_cast<const uint8_t*>(p.visible)[r] != 0;
-                if (vis) {
-                    s[GFT_TOF_LOG_GS_SP_VISIBLE] += v;
-                    n++;
-                }
+            if (p.visible && gft_visible_row(p.visible, p.visible_is_radii, r)) {
+                s[GFT_TOF_LOG_GS_SP_VISIBLE] += v;
+                n++;
             }
         }
     }
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int k = 0; k < TOF_SUMS; k++) s[k] += __shfl_xor(s[k], o);
-        n += (uint32_t)__shfl_xor((int)n, o);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < TOF_SUMS; k++) sRed[k][threadIdx.x >> 6] = s[k];
-        sCnt[threadIdx.x >> 6] = n;
-    }
+    gft_fold_store<TOF_THREADS>(s, sRed);
+    gft_fold_store<TOF_THREADS>(n, sCnt);
     __syncthreads();
     if (threadIdx.x < GFT_TOF_PARTIAL_WORDS) {
-        uint32_t* row = p.partials + (size_t)blockIdx.x * GFT_TOF_PARTIAL_WORDS;
         const int k = threadIdx.x;
-        if (k < TOF_SUMS) {
-            float t = sRed[k][0];
-            for (int w = 1; w < TOF_THREADS / 64; w++) t += sRed[k][w];
-            row[k] = __float_as_uint(t);
-        } else {
-            uint32_t t = 0;
-            for (int w = 0; w < TOF_THREADS / 64; w++) t += sCnt[w];
-            row[k] = t;
-        }
+        p.partials[(size_t)blockIdx.x * GFT_TOF_PARTIAL_WORDS + k] =
+            k < TOF_SUMS ? __float_as_uint(gft_waves_total<TOF_THREADS>(sRed[k])) : gft_waves_total<TOF_THREADS>(sCnt);
     }
 }
 
@@ -131,7 +105,7 @@ __global__ __launch_bounds__(TOF_THREADS) void k_tof_log_sums(TofArgs p)
 __global__ __launch_bounds__(TOF_THREADS) void k_tof_log_finish(TofArgs p)
 {
     __shared__ double sSum[TOF_SUMS][TOF_THREADS];
-    __shared__ unsigned long long sCnt[TOF_THREADS];
+    __shared__ unsigned long long sCnt[1][TOF_THREADS];
     const int tid = threadIdx.x;
     double s[TOF_SUMS];
 #pragma unroll
@@ -145,18 +119,10 @@ __global__ __launch_bounds__(TOF_THREADS) void k_tof_log_finish(TofArgs p)
     }
 #pragma unroll
     for (int k = 0; k < TOF_SUMS; k++) sSum[k][tid] = s[k];
-    sCnt[tid] = n;
-    __syncthreads();
-    for (int h = TOF_THREADS / 2; h > 0; h >>= 1) {
-        if (tid < h) {
-#pragma unroll
-            for (int k = 0; k < TOF_SUMS; k++) sSum[k][tid] += sSum[k][tid + h];
-            sCnt[tid] += sCnt[tid + h];
-        }
-        __syncthreads();
-    }
+    sCnt[0][tid] = n;
+    gft_tree_sum<TOF_THREADS>(sSum, sCnt);
     if (tid != 0) return;
-    const unsigned long long n_vis = sCnt[0];
+    const unsigned long long n_vis = sCnt[0][0];
     const uint32_t seq = p.cursor ? *p.cursor : 0u;
     uint32_t* out = p.rows + (size_t)(seq % p.slots) * GFT_TOF_LOG_WORDS;
     const double per_pixel = 1.0 / (double)p.pixels;
@@ -185,8 +151,7 @@ extern "C" int gft_tof_depth(void* hip_stream, int64_t pixels, const float* tof,
     if (plane_stride < 0 || plane_stride > (1ll << 40)) return gft_fail("gft_tof_depth: bad plane_stride=%lld", (long long)plane_stride);
     hipLaunchKernelGGL(k_tof_depth, dim3((unsigned)tof_blocks(pixels)), dim3(TOF_THREADS), 0, (hipStream_t)hip_stream, pixels, tof,
                        plane_stride, depth_range_dev, depth_range, phase_offset_dev, phase_offset, out);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : gft_fail("gft_tof_depth: %s", hipGetErrorString(err));
+    return gft_launched("gft_tof_depth");
 }
 
 extern "C" int64_t gft_tof_log_blocks(int64_t pixels, int64_t P)
@@ -234,6 +199,5 @@ extern "C" int gft_tof_log_row(void* hip_stream, int64_t pixels, int64_t P, cons
     hipStream_t s = (hipStream_t)hip_stream;
     hipLaunchKernelGGL(k_tof_log_sums, dim3(p.blocks), dim3(TOF_THREADS), 0, s, p);
     hipLaunchKernelGGL(k_tof_log_finish, dim3(1), dim3(TOF_THREADS), 0, s, p);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : gft_fail("gft_tof_log_row: %s", hipGetErrorString(err));
+    return gft_launched("gft_tof_log_row");
 }

@@ -21,7 +21,8 @@ import math
 
 import torch
 
-from . import _lib
+from . import _args, _lib
+from ._args import ptr as _ptr
 
 
 def _check(items):
@@ -36,18 +37,8 @@ def _check(items):
         if t.requires_grad and not grad_ok:
             raise NotImplementedError("gftorf_amd.flow: gradients flow to the 3-D flows only; %s requires grad (detach it, "
                                       "as train.py detaches the depth)" % name)
-    device = items[0][0].device
-    for t, name, _, _ in items:
-        if t.device.type != "cuda":
-            raise RuntimeError("gftorf_amd.flow: %s is on %s; the flow kernels run on a HIP device only, there is no CPU path"
-                               % (name, t.device))
-        if t.device != device:
-            raise RuntimeError("gftorf_amd.flow: %s is on %s, %s on %s" % (name, t.device, items[0][1], device))
+    _args.devices("gftorf_amd.flow", "flow", items)
     return [t if t.dtype == torch.float32 and t.is_contiguous() else t.float().contiguous() for t, _, _, _ in items]
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def _hw(t):

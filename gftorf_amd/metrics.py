@@ -20,61 +20,19 @@ under ``torch.no_grad()``).  There is no CPU path.
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
+from ._args import ptr as _ptr
 
+_TAG = "gftorf_amd.metrics"
 VALUES = _lib.METRICS_VALUES                     # the eight names, in the order of a row and of the report's sums
 MAX_PLANES = _lib.METRICS_MAX_PLANES
 
 
-def _tensor(t, name):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError("gftorf_amd.metrics: %s must be a tensor, got %s" % (name, type(t).__name__))
-    if t.dtype != torch.float32:
-        raise TypeError("gftorf_amd.metrics: %s must be torch.float32, got %s" % (name, t.dtype))
-    return t.detach()
-
-
-def _devices(named):
-    """Shapes and dtypes are checked first, then the devices: every tensor on the first one's HIP device."""
-    dev = named[0][0].device
-    for t, name in named:
-        if t.device.type != "cuda":
-            raise RuntimeError("gftorf_amd.metrics: %s is on %s; the metric kernels run on a HIP device only, there is no CPU path"
-                               % (name, t.device))
-        if t.device != dev:
-            raise RuntimeError("gftorf_amd.metrics: %s is on %s, %s on %s" % (name, t.device, named[0][1], dev))
-    return dev
-
-
 def _planes(t, name, shape=None, most=MAX_PLANES, least=1):
-    """A [C, H, W] image (`least` <= C <= `most`; `shape` = the (C, H, W) it must have, when its partner is known) as
-    (tensor, plane stride): taken in place when every plane is contiguous -- ``phasor[:n]``, one plane of the 7-plane
-    tensor --, else copied."""
-    t = _tensor(t, name)
-    if shape is not None and tuple(t.shape) != tuple(shape):
+    """``_args.planes``; `shape` = the (C, H, W) the image must have, when its partner is known"""
+    if shape is not None and tuple(_args.tensor(_TAG, t, name).shape) != tuple(shape):
         raise RuntimeError("gftorf_amd.metrics: %s must be %s, got %s" % (name, list(shape), list(t.shape)))
-    if t.dim() != 3 or not least <= t.shape[0] <= most or t.shape[1] < 1 or t.shape[2] < 1:
-        raise RuntimeError("gftorf_amd.metrics: %s must be [%s, H, W], got %s"
-                           % (name, "%d..%d" % (least, most) if most < 1 << 30 else ">=%d" % least, list(t.shape)))
-    H, W = int(t.shape[1]), int(t.shape[2])
-    if not ((W == 1 or t.stride(2) == 1) and (H == 1 or t.stride(1) == W) and (t.shape[0] == 1 or t.stride(0) >= 0)):
-        t = t.contiguous()
-    return t, (int(t.stride(0)) if t.shape[0] > 1 else 0)
-
-
-def _scalar(v, name, named):
-    """(tensor or None, float): a one-element float32 device tensor is passed by address, a number by value"""
-    if isinstance(v, torch.Tensor):
-        v = _tensor(v, name)
-        if v.numel() != 1:
-            raise RuntimeError("gftorf_amd.metrics: %s must be a number or a one-element tensor, got %s" % (name, list(v.shape)))
-        named.append((v, name))
-        return v, 0.0
-    return None, float(v)
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
+    return _args.planes(_TAG, t, name, least, most)
 
 
 def _pair(a, b, name, gt_name, most):
@@ -132,11 +90,11 @@ def _launch(row, accum, partials, image=None, gt_image=None, tof=None, gt_tof=No
         ph, ph_stride = _planes(phasor, "phasor", most=1 << 30, least=2)
         group_b(ph, "phasor")
         named.append((ph, "phasor"))
-        dr_t, dr = _scalar(depth_range, "depth_range", named)
-        po_t, po = _scalar(phase_offset, "phase_offset", named)
+        dr_t, dr = _args.scalar(_TAG, depth_range, "depth_range", named)
+        po_t, po = _args.scalar(_TAG, phase_offset, "phase_offset", named)
     if not named:
         raise ValueError("gftorf_amd.metrics: nothing to compare: give image, tof, depth or phasor with their ground truth")
-    dev = _devices(named)
+    dev = _args.devices(_TAG, "metric", named)
     n_a = int(colour[0][0].shape[0]) if colour else 0
     n_b = int(chans[0][0].shape[0]) if chans else 0
     pixels_a = int(colour[0][0].shape[1] * colour[0][0].shape[2]) if colour else 0
@@ -164,7 +122,7 @@ def _first_device(*tensors):
 
 def _planewise(img1, img2, word):
     """mse / psnr of every channel: [C, ...] flattened per channel as the reference's ``.view(img1.shape[0], -1)``"""
-    a, b = _tensor(img1, "img1"), _tensor(img2, "img2")
+    a, b = _args.tensor(_TAG, img1, "img1"), _args.tensor(_TAG, img2, "img2")
     if a.dim() < 1 or a.shape != b.shape:
         raise RuntimeError("gftorf_amd.metrics: img1 and img2 must have one shape [C, ...], got %s and %s" % (list(a.shape), list(b.shape)))
     C = int(a.shape[0])
@@ -221,11 +179,7 @@ class EvalReport:
 
     def __init__(self, device=None):
         lib = _lib.load()
-        device = torch.device("cuda" if device is None else device)
-        if device.type != "cuda":
-            raise RuntimeError("gftorf_amd.metrics: an EvalReport lives on a HIP device, got %s; there is no CPU path" % device)
-        # (an indexed device: "cuda" alone does not compare equal to the cuda:0 of the tensors added)
-        self.device = torch.device("cuda", torch.cuda.current_device() if device.index is None else device.index)
+        self.device = _args.indexed_device(_TAG, "an EvalReport", device)
         # eight doubles, then the view count and the present word (GFT_METRICS_ACC_*): 9 doubles' worth, 8-byte aligned
         self._sums = torch.empty((_lib.METRICS_ACC_WORDS // 2,), device=self.device, dtype=torch.float64)
         # the scratch of the largest launch there is, once: a graph captured by an earlier add_view keeps its address

@@ -22,8 +22,10 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
+from ._args import ptr as _ptr
 
+_TAG = "gftorf_amd.present"
 IMAGES = tuple(name for name, _, _, _ in _lib.PRESENT_IMAGES)       # the keys, in the order the images lie in a sheet
 _EVERY = (_lib.PRESENT_HAS_COLOR | _lib.PRESENT_HAS_PHASOR | _lib.PRESENT_HAS_QUAD | _lib.PRESENT_HAS_DEPTH | _lib.PRESENT_HAS_ACC |
           _lib.PRESENT_HAS_DD)
@@ -56,55 +58,14 @@ def sheet_layout(H, W, groups):
     return total, {name: int(offsets[k]) for k, name in enumerate(IMAGES) if offsets[k] >= 0}
 
 
-def _tensor(t, name):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError("gftorf_amd.present: %s must be a tensor, got %s" % (name, type(t).__name__))
-    if t.dtype != torch.float32:
-        raise TypeError("gftorf_amd.present: %s must be torch.float32, got %s" % (name, t.dtype))
-    return t.detach()
-
-
-def _devices(named):
-    """Shapes and dtypes are checked first, then the devices: every tensor on the first one's HIP device."""
-    dev = named[0][0].device
-    for t, name in named:
-        if t.device.type != "cuda":
-            raise RuntimeError("gftorf_amd.present: %s is on %s; the display kernels run on a HIP device only, there is no CPU path"
-                               % (name, t.device))
-        if t.device != dev:
-            raise RuntimeError("gftorf_amd.present: %s is on %s, %s on %s" % (name, t.device, named[0][1], dev))
-    return dev
-
-
 def _planes(t, name, least, most, size=None):
-    """A [C, H, W] image (`least` <= C <= `most`) as (tensor, plane stride): taken in place when every plane is contiguous
-    -- ``phasor[:3]`` of the 7-plane tensor --, else copied.  `size` = ((H, W), the name of the input that set it)."""
-    t = _tensor(t, name)
-    if t.dim() != 3 or not least <= t.shape[0] <= most or t.shape[1] < 1 or t.shape[2] < 1:
-        want = "%d" % least if least == most else ("%d..%d" % (least, most) if most < 1 << 30 else ">=%d" % least)
-        raise RuntimeError("gftorf_amd.present: %s must be [%s, H, W], got %s" % (name, want, list(t.shape)))
+    """``_args.planes`` (an exact plane count is worded as such); `size` = ((H, W), the name of the input that set it)"""
+    t, stride = _args.planes(_TAG, t, name, least, most, want="%d" % least if least == most else None)
     H, W = int(t.shape[1]), int(t.shape[2])
     if size is not None and (H, W) != size[0]:
         raise RuntimeError("gftorf_amd.present: %s is %d x %d, %s %d x %d: the inputs of one call have one size"
                            % ((name, H, W, size[1]) + size[0]))
-    if not ((W == 1 or t.stride(2) == 1) and (H == 1 or t.stride(1) == W) and (t.shape[0] == 1 or t.stride(0) >= 0)):
-        t = t.contiguous()
-    return t, (int(t.stride(0)) if t.shape[0] > 1 else 0)
-
-
-def _scalar(v, name, named):
-    """(tensor or None, float): a one-element float32 device tensor is passed by address, a number by value"""
-    if isinstance(v, torch.Tensor):
-        v = _tensor(v, name)
-        if v.numel() != 1:
-            raise RuntimeError("gftorf_amd.present: %s must be a number or a one-element tensor, got %s" % (name, list(v.shape)))
-        named.append((v, name))
-        return v, 0.0
-    return None, float(v)
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
+    return t, stride
 
 
 def _views(sheet, offsets, H, W):
@@ -176,7 +137,7 @@ def view_images(image=None, phasor=None, depth=None, acc=None, dd=None, *, range
         if depth_range is None:
             raise ValueError("gftorf_amd.present: the ToF depth of phasor needs depth_range")
         if isinstance(ranges, torch.Tensor):
-            rg_t = _tensor(ranges, "ranges")
+            rg_t = _args.tensor(_TAG, ranges, "ranges")
             if tuple(rg_t.shape) != (6,) or not rg_t.is_contiguous():
                 raise RuntimeError("gftorf_amd.present: ranges must be six numbers or a contiguous tensor [6], got %s" % list(rg_t.shape))
             named.append((rg_t, "ranges"))
@@ -185,14 +146,14 @@ def view_images(image=None, phasor=None, depth=None, acc=None, dd=None, *, range
             if len(vals) != 6:
                 raise RuntimeError("gftorf_amd.present: ranges must be six numbers or a contiguous tensor [6], got %d numbers" % len(vals))
             rg_host = (C.c_float * 6)(*vals)
-        dr_t, dr = _scalar(depth_range, "depth_range", named)
-        po_t, po = _scalar(phase_offset, "phase_offset", named)
+        dr_t, dr = _args.scalar(_TAG, depth_range, "depth_range", named)
+        po_t, po = _args.scalar(_TAG, phase_offset, "phase_offset", named)
     znear = zfar = 0.0
     if ph is not None or d is not None:
         if zplanes is None:
             raise ValueError("gftorf_amd.present: the colour map of a depth needs zplanes = (znear, zfar)")
         znear, zfar = (float(z) for z in zplanes)
-    dev = _devices(named)
+    dev = _args.devices(_TAG, "display", named)
     (H, W) = size[0]
     groups = ((_lib.PRESENT_HAS_COLOR if im is not None else 0) | (_lib.PRESENT_HAS_PHASOR if ph is not None else 0) |
               (_lib.PRESENT_HAS_QUAD if planes == 7 and quad is not False else 0) | (_lib.PRESENT_HAS_DEPTH if d is not None else 0) |
@@ -234,10 +195,7 @@ class PhasorRanges:
 
     def __init__(self, device=None):
         lib = _lib.load()
-        device = torch.device("cuda" if device is None else device)
-        if device.type != "cuda":
-            raise RuntimeError("gftorf_amd.present: PhasorRanges lives on a HIP device, got %s; there is no CPU path" % device)
-        self.device = torch.device("cuda", torch.cuda.current_device() if device.index is None else device.index)
+        self.device = _args.indexed_device(_TAG, "PhasorRanges", device)
         self.tensor = torch.empty((_lib.PRESENT_RANGE_WORDS,), device=self.device, dtype=torch.float32)
         # the scratch of the largest launch there is, once: a graph captured by an earlier add keeps its address
         self._partials = torch.empty((int(lib.gft_present_blocks(1 << 40)), _lib.PRESENT_RANGE_WORDS), device=self.device,
@@ -252,7 +210,7 @@ class PhasorRanges:
     def add(self, gt_tof):
         """Fold one ground-truth ToF image [>= 3, H, W] (planes 0..2 are read, in place) into the ranges: two launches"""
         t, stride = _planes(gt_tof, "gt_tof", 3, 1 << 30)
-        if _devices([(t, "gt_tof")]) != self.device:
+        if _args.devices(_TAG, "display", [(t, "gt_tof")]) != self.device:
             raise RuntimeError("gftorf_amd.present: gt_tof is on %s, the ranges on %s" % (t.device, self.device))
         with _lib.on_device(self.device):
             _lib.check(_lib.load().gft_present_ranges(_lib.raw_stream(self.device), int(t.shape[1] * t.shape[2]), t.data_ptr(), stride,

@@ -18,7 +18,8 @@ import collections
 
 import torch
 
-from . import _lib
+from . import _args, _lib
+from ._args import ptr_nonempty as _ptr
 
 TERMS = ("motion", "opacity_entropy", "scale", "depth_distortion")          # the order of the means and of `weights`
 
@@ -74,17 +75,7 @@ def _check(d_xyz, opacity, motion_mask, scaling, visible, dd, weights):
         if t.dtype != dtype and not (isinstance(dtype, tuple) and t.dtype in dtype):
             names = " or ".join(str(d) for d in (dtype if isinstance(dtype, tuple) else (dtype,)))
             raise TypeError("gftorf_amd.reg: %s must be %s, got %s" % (name, names, t.dtype))
-    device = named[0][0].device
-    for t, name, _ in named:
-        if t.device.type != "cuda":
-            raise RuntimeError("gftorf_amd.reg: %s is on %s; the regulariser kernels run on a HIP device only, there is no CPU path"
-                               % (name, t.device))
-        if t.device != device:
-            raise RuntimeError("gftorf_amd.reg: %s is on %s, %s on %s" % (name, t.device, named[0][1], device))
-
-
-def _ptr(t):
-    return None if t is None or t.numel() == 0 else t.data_ptr()
+    _args.devices("gftorf_amd.reg", "regulariser", named)
 
 
 class _Regularizers(torch.autograd.Function):

@@ -24,42 +24,23 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
+from ._args import ptr_nonempty as _ptr
 
+_TAG = "gftorf_amd.tof"
 FLOATS = _lib.TOF_LOG_FLOATS                     # names of the float words of a row, in order
 MAX_EXTRAS = _lib.TOF_LOG_MAX_EXTRAS
 
 
 def _tensor(t, name, dtypes=(torch.float32,)):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError("gftorf_amd.tof: %s must be a tensor, got %s" % (name, type(t).__name__))
-    if t.dtype not in dtypes:
-        raise TypeError("gftorf_amd.tof: %s must be %s, got %s" % (name, " or ".join(str(d) for d in dtypes), t.dtype))
-    return t.detach()
-
-
-def _devices(named):
-    """Shapes and dtypes are checked first, then the devices: every tensor on the first one's HIP device."""
-    dev = named[0][0].device
-    for t, name in named:
-        if t.device.type != "cuda":
-            raise RuntimeError("gftorf_amd.tof: %s is on %s; the ToF kernels run on a HIP device only, there is no CPU path"
-                               % (name, t.device))
-        if t.device != dev:
-            raise RuntimeError("gftorf_amd.tof: %s is on %s, %s on %s" % (name, t.device, named[0][1], dev))
-    return dev
+    return _args.tensor(_TAG, t, name, dtypes)
 
 
 def _planes(t, name, n):
-    """A [C >= n, H, W] image as (tensor, plane stride, H, W): taken in place when every plane is contiguous, else its
-    first n planes copied."""
-    t = _tensor(t, name)
-    if t.dim() != 3 or t.shape[0] < n or t.shape[1] < 1 or t.shape[2] < 1:
-        raise RuntimeError("gftorf_amd.tof: %s must be [>=%d, H, W], got %s" % (name, n, list(t.shape)))
-    H, W = int(t.shape[1]), int(t.shape[2])
-    if not ((W == 1 or t.stride(2) == 1) and (H == 1 or t.stride(1) == W) and t.stride(0) >= 0):
-        t = t[:n].contiguous()
-    return t, int(t.stride(0)), H, W
+    """A [C >= n, H, W] image (n >= 2) as (tensor, plane stride, H, W): taken in place when every plane is contiguous, else
+    its first n planes copied."""
+    t, stride = _args.planes(_TAG, t, name, least=n, keep=n)
+    return t, stride, int(t.shape[1]), int(t.shape[2])
 
 
 def _image(t, name, H, W):
@@ -67,17 +48,6 @@ def _image(t, name, H, W):
     if tuple(t.shape) != (1, H, W):
         raise RuntimeError("gftorf_amd.tof: %s must be [1, %d, %d], got %s" % (name, H, W, list(t.shape)))
     return t.contiguous()
-
-
-def _scalar(v, name, named):
-    """(device pointer or None, float): a one-element float32 device tensor is passed by address, a number by value"""
-    if isinstance(v, torch.Tensor):
-        v = _tensor(v, name)
-        if v.numel() != 1:
-            raise RuntimeError("gftorf_amd.tof: %s must be a number or a one-element tensor, got %s" % (name, list(v.shape)))
-        named.append((v, name))
-        return v, 0.0
-    return None, float(v)
 
 
 def depth_from_tof(tof, depth_range, phase_offset=0.0):
@@ -90,18 +60,14 @@ def depth_from_tof(tof, depth_range, phase_offset=0.0):
     backward: the result is detached."""
     t, stride, H, W = _planes(tof, "tof", 2)
     named = [(t, "tof")]
-    dr_t, dr = _scalar(depth_range, "depth_range", named)
-    po_t, po = _scalar(phase_offset, "phase_offset", named)
-    dev = _devices(named)
+    dr_t, dr = _args.scalar(_TAG, depth_range, "depth_range", named)
+    po_t, po = _args.scalar(_TAG, phase_offset, "phase_offset", named)
+    dev = _args.devices(_TAG, "ToF", named)
     out = torch.empty((H, W), device=dev, dtype=torch.float32)
     with _lib.on_device(dev):
         _lib.check(_lib.load().gft_tof_depth(_lib.raw_stream(dev), H * W, t.data_ptr(), stride, _ptr(dr_t), dr, _ptr(po_t), po,
                                              out.data_ptr()))
     return out
-
-
-def _ptr(t):
-    return None if t is None or t.numel() == 0 else t.data_ptr()
 
 
 def _launch(rows, slots, cursor, partials, phasor, depth, gt_phasor, depth_range, phase_offset=0.0, tof_multiplier=1.0,
@@ -159,9 +125,9 @@ def _launch(rows, slots, cursor, partials, phasor, depth, gt_phasor, depth_range
             raise RuntimeError("gftorf_amd.tof: extras[%d] must be 0-dim or one-element, got %s" % (k, list(e.shape)))
         ex.append(e)
         named.append((e, "extras[%d]" % k))
-    dr_t, dr = _scalar(depth_range, "depth_range", named)
-    po_t, po = _scalar(phase_offset, "phase_offset", named)
-    dev = _devices(named)
+    dr_t, dr = _args.scalar(_TAG, depth_range, "depth_range", named)
+    po_t, po = _args.scalar(_TAG, phase_offset, "phase_offset", named)
+    dev = _args.devices(_TAG, "ToF", named)
     if _ptr(amp) is None:
         P = 0
     blocks = int(lib.gft_tof_log_blocks(H * W, P))
@@ -229,11 +195,7 @@ class TrainLog:
             raise ValueError("gftorf_amd.tof: slots must be in 1 .. 2^31 - 1, got %r" % (slots,))
         lib = _lib.load()
         self.slots = int(slots)
-        device = torch.device("cuda" if device is None else device)
-        if device.type != "cuda":
-            raise RuntimeError("gftorf_amd.tof: a TrainLog lives on a HIP device, got %s; there is no CPU path" % device)
-        # (an indexed device: "cuda" alone does not compare equal to the cuda:0 of the tensors recorded)
-        self.device = torch.device("cuda", torch.cuda.current_device() if device.index is None else device.index)
+        self.device = _args.indexed_device(_TAG, "a TrainLog", device)
         self.rows = torch.zeros((self.slots, _lib.TOF_LOG_WORDS), device=self.device, dtype=torch.float32)
         self.cursor = torch.zeros((1,), device=self.device, dtype=torch.int32)
         # the scratch of the largest launch there is, once: a graph captured by an earlier record keeps its address
