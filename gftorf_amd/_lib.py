@@ -181,7 +181,7 @@ METRICS_ACC_SUMS, METRICS_ACC_VIEWS, METRICS_ACC_PRESENT, METRICS_ACC_WORDS = 0,
 METRICS_HAS_COLOUR, METRICS_HAS_TOF, METRICS_HAS_DEPTH, METRICS_HAS_TOF_DEPTH = 1, 2, 4, 8
 # include/gftorf_present.h (a rendered view's display images; no struct, so the ABI version is unchanged)
 PRESENT_EXPORTS = ["gft_present_blocks", "gft_present_sheet_bytes", "gft_present_magma", "gft_present_view", "gft_present_ranges",
-                   "gft_present_ranges_reset"]
+                   "gft_present_ranges_reset", "gft_present_seismic", "gft_present_quad"]
 # GFT_PRESENT_*: the images of a sheet in the order they lie in it: (name, bytes per pixel, numpy dtype, shape of an H x W view)
 PRESENT_IMAGES = (("color", 3, "uint8", lambda H, W: (H, W, 3)), ("real", 3, "uint8", lambda H, W: (H, W, 3)),
                   ("imag", 3, "uint8", lambda H, W: (H, W, 3)), ("amp", 1, "uint8", lambda H, W: (H, W)),
@@ -191,6 +191,10 @@ PRESENT_IMAGES = (("color", 3, "uint8", lambda H, W: (H, W, 3)), ("real", 3, "ui
                   ("depth_norm_f", 4, "float32", lambda H, W: (H, W)))
 PRESENT_HAS_COLOR, PRESENT_HAS_PHASOR, PRESENT_HAS_QUAD, PRESENT_HAS_DEPTH, PRESENT_HAS_ACC, PRESENT_HAS_DD = 1, 2, 4, 8, 16, 32
 PRESENT_ALIGN, PRESENT_PARTIAL_WORDS, PRESENT_RANGE_WORDS, PRESENT_MAGMA_ROWS = 16, 2, 6, 257      # GFT_PRESENT_*
+PRESENT_SEISMIC_ROWS = 257                                                                         # GFT_PRESENT_SEISMIC_ROWS
+# include/gftorf_tracks.h (the F-ToRF motion tracks; no struct, so the ABI version is unchanged)
+TRACKS_EXPORTS = ["gft_tracks_integrate", "gft_tracks_table_bytes", "gft_tracks_table"]
+TRACKS_PARTS = ("index", "xy", "motion", "step_ok")             # GFT_TRACKS_*: the parts of a table in the order they lie in it
 
 
 def load():
@@ -371,6 +375,21 @@ def load():
     lib.gft_present_ranges.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.gft_present_ranges_reset.restype = C.c_int
     lib.gft_present_ranges_reset.argtypes = [C.c_void_p, C.c_void_p]
+    lib.gft_present_seismic.restype = C.POINTER(C.c_uint8)
+    lib.gft_present_seismic.argtypes = []
+    # stream, H, W, phasor, stride, permutation, has_gt, tonemap, out
+    lib.gft_present_quad.restype = C.c_int
+    lib.gft_present_quad.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.c_int32, C.c_int32,
+                                     C.c_void_p]
+    # stream, P, n, T, U, initial_pos, flow, flow_index, K, world_view, mask, rank, H, W, xy, pos_last, motion, mean_z, step_ok
+    lib.gft_tracks_integrate.restype = C.c_int
+    lib.gft_tracks_integrate.argtypes = ([C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 7 +
+                                         [C.c_int32, C.c_int32] + [C.c_void_p] * 5)
+    lib.gft_tracks_table_bytes.restype = C.c_int64
+    lib.gft_tracks_table_bytes.argtypes = [C.c_int32, C.c_int64, C.POINTER(C.c_int64)]
+    # stream, P, T, S, mask, rank, xy, step_ok, motion, table
+    lib.gft_tracks_table.restype = C.c_int
+    lib.gft_tracks_table.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64] + [C.c_void_p] * 6
     lib.gft_densify_stats.restype = C.c_int
     lib.gft_densify_stats.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8
     lib.gft_rows_rank_scratch_bytes.restype = C.c_size_t

@@ -5,6 +5,8 @@
 // images are stored per lane; the 3-byte HWC pixels and the 1-byte planes are staged in LDS at the destination's offset
 // within a dword and leave as whole dwords, with byte stores only for a run's ragged head and tail.
 // k_present_ranges_part / _finish: the (lo, hi) of the ground truth's real, imag and amp images, folded into six floats.
+// k_present_quad: tof_to_image (scene/torf_utils.py:43-50) of the four quad planes, staged and stored as k_present_view's
+// 3-byte pixels are.
 // No atomics, no memset, scalar loads (each coalesced across the wave).
 //
 // The arithmetic is numpy's float32 sequence operation for operation: nothing here may contract into a multiply-add, and
@@ -13,6 +15,7 @@
 #include "gft_reduce.h"
 #include "gft_tof_depth.h"
 #include "gft_present_magma.h"
+#include "gft_present_seismic.h"
 #include "gftorf_present.h"
 
 #pragma clang fp contract(off)
@@ -29,6 +32,9 @@ static_assert(PRS_MAX_BLOCKS % PRS_THREADS == 0, "the finish reads PRS_MAX_BLOCK
 
 const uint32_t h_magma[GFT_MAGMA_ROWS] = {GFT_MAGMA_TABLE};
 __device__ const uint32_t d_magma[GFT_MAGMA_ROWS] = {GFT_MAGMA_TABLE};
+static_assert(GFT_SEISMIC_ROWS == GFT_PRESENT_SEISMIC_ROWS, "header");
+const uint32_t h_seismic[GFT_SEISMIC_ROWS] = {GFT_SEISMIC_TABLE};
+__device__ const uint32_t d_seismic[GFT_SEISMIC_ROWS] = {GFT_SEISMIC_TABLE};
 
 struct PresentArgs {
     int64_t pixels;
@@ -282,6 +288,62 @@ __global__ void k_present_ranges_reset(float* ranges)
     if (threadIdx.x < GFT_PRESENT_RANGE_WORDS) ranges[threadIdx.x] = (threadIdx.x & 1) ? -INFINITY : INFINITY;
 }
 
+// tof_to_image of one value as an RGBx word: np.clip(x, -0.5, 0.5) keeps a NaN; Normalize(-0.5, 0.5) of a float32 is
+// (c - -0.5) / 1 in float32; matplotlib's index of that is trunc(n * 256) with 256 (n == 1) taken as 255, a NaN the bad colour
+__device__ __forceinline__ uint32_t seismic(const uint32_t* table, float x)
+{
+    const float c = x < -0.5f ? -0.5f : (x > 0.5f ? 0.5f : x);
+    const float n = c + 0.5f;
+    int row;
+    if (n != n) row = 256;
+    else {
+        const float s = n * 256.f;
+        row = s >= 256.f ? 255 : (int)s;
+    }
+    return table[row];
+}
+
+struct QuadArgs {
+    int64_t pixels;
+    const float* phasor;            // 7 planes `stride` apart
+    int64_t stride;
+    int plane[4];                   // 3 + permutation[k]
+    int has_gt, tonemap;
+    uint8_t* out;                   // [4][pixels][3]
+};
+
+__global__ __launch_bounds__(PRS_THREADS) void k_present_quad(QuadArgs p)
+{
+    __shared__ uint32_t sSeismic[GFT_SEISMIC_ROWS];
+    __shared__ uint32_t sRun3[4][PRS_RUN3];
+    const int tid = threadIdx.x;
+    for (int k = tid; k < GFT_SEISMIC_ROWS; k += PRS_THREADS) sSeismic[k] = d_seismic[k];
+    __syncthreads();
+    const int64_t runs = (p.pixels + PRS_THREADS - 1) / PRS_THREADS;
+    for (int64_t run = blockIdx.x; run < runs; run += gridDim.x) {
+        const int64_t i0 = run * PRS_THREADS, i = i0 + tid;
+        const int64_t left = p.pixels - i0;
+        const int n = left < PRS_THREADS ? (int)left : PRS_THREADS;
+        if (tid < n) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                // render_ftorf_viz_traj.py:238-243: minus 0.5 with a ground truth, then the tonemap x / (1 + x)
+                float v = p.phasor[p.plane[k] * p.stride + i];
+                if (p.has_gt) v = v - 0.5f;
+                if (p.tonemap) v = v / (1.f + v);
+                const uint32_t w = seismic(sSeismic, v);
+                uint8_t* s = reinterpret_cast<uint8_t*>(sRun3[k]) + ((uintptr_t)(p.out + 3 * (k * p.pixels + i0)) & 3u) + 3 * tid;
+                s[0] = (uint8_t)w;
+                s[1] = (uint8_t)(w >> 8);
+                s[2] = (uint8_t)(w >> 16);
+            }
+        }
+        __syncthreads();
+        for (int k = 0; k < 4; k++) put_run(p.out + 3 * (k * p.pixels + i0), 3 * n, sRun3[k]);
+        __syncthreads();
+    }
+}
+
 // offsets of the images the groups produce, -1 for the others; the sheet's bytes, or 0 for groups that make no sense
 int64_t prs_layout(int64_t pixels, int groups, int64_t* offsets)
 {
@@ -380,4 +442,30 @@ extern "C" int gft_present_ranges_reset(void* hip_stream, float* ranges)
     if (!ranges) return gft_fail("gft_present_ranges_reset: ranges is NULL");
     hipLaunchKernelGGL(k_present_ranges_reset, dim3(1), dim3(64), 0, (hipStream_t)hip_stream, ranges);
     return gft_launched("gft_present_ranges_reset");
+}
+
+extern "C" const uint8_t* gft_present_seismic(void)
+{
+    return reinterpret_cast<const uint8_t*>(h_seismic);
+}
+
+extern "C" int gft_present_quad(void* hip_stream, int32_t H, int32_t W, const float* phasor, int64_t phasor_stride,
+                                const int32_t* permutation, int32_t has_gt, int32_t tonemap, void* out)
+{
+    if (H < 1 || W < 1 || (int64_t)H * W > (1ll << 40)) return gft_fail("gft_present_quad: bad size H=%d W=%d", H, W);
+    if (!phasor || !permutation || !out) return gft_fail("gft_present_quad: NULL argument");
+    if (bad_stride(phasor_stride)) return gft_fail("gft_present_quad: bad plane stride");
+    QuadArgs p = {};
+    p.pixels = (int64_t)H * W;
+    p.phasor = phasor;
+    p.stride = phasor_stride;
+    for (int k = 0; k < 4; k++) {
+        if (permutation[k] < 0 || permutation[k] > 3) return gft_fail("gft_present_quad: permutation[%d]=%d is not in 0..3", k, permutation[k]);
+        p.plane[k] = 3 + permutation[k];
+    }
+    p.has_gt = has_gt != 0;
+    p.tonemap = tonemap != 0;
+    p.out = static_cast<uint8_t*>(out);
+    hipLaunchKernelGGL(k_present_quad, dim3((unsigned)prs_blocks(p.pixels)), dim3(PRS_THREADS), 0, (hipStream_t)hip_stream, p);
+    return gft_launched("gft_present_quad");
 }

@@ -12,6 +12,8 @@ blocking ``.cpu()`` calls, about 130 bytes per pixel -- and forms the images it 
 ``ViewSheets``  pinned staging: ``submit`` enqueues ``view_images`` and the sheet's asynchronous copy, ``ready`` hands out the
     finished views as numpy arrays, so the host encodes view i while view i + 1 renders.
 ``zplanes(depth_range)``  the colour map's planes of ``render.py:54``.
+``quad_images(phasor, ...)``  the four quad images of the track program (``render_ftorf_viz_traj.py:237-244``): ``tof_to_image``,
+    matplotlib's ``seismic`` map, in one launch.
 
 The uint8 images equal the reference's bit for bit wherever its float32 statements are IEEE operations; the one exception is
 ``arctan2`` in ``depth_tof``, whose last bits may differ (see tests/test_present.py).  Nothing here has a gradient and there is
@@ -42,6 +44,13 @@ def magma_table():
     """``to8b(cm.magma(.))`` as the kernel holds it: uint8 [257, 4], rows 0..255 the map's entries, row 256 a NaN's colour"""
     ptr = _lib.load().gft_present_magma()
     return np.ctypeslib.as_array(ptr, shape=(_lib.PRESENT_MAGMA_ROWS, 4)).copy()
+
+
+def seismic_table():
+    """``(255 * seismic(.)).astype(uint8)`` as the kernel holds it: uint8 [257, 4], rows 0..255 the entries of matplotlib's
+    ``seismic`` map, row 256 a NaN's colour; ``tof_to_image`` shows the first three bytes of a row"""
+    ptr = _lib.load().gft_present_seismic()
+    return np.ctypeslib.as_array(ptr, shape=(_lib.PRESENT_SEISMIC_ROWS, 4)).copy()
 
 
 def blocks(pixels):
@@ -179,6 +188,37 @@ def view_images(image=None, phasor=None, depth=None, acc=None, dd=None, *, range
                                         _ptr(dist), _ptr(rg_t), rg_host, _ptr(dr_t), dr, _ptr(po_t), po, znear, zfar,
                                         float(tof_multiplier), _ptr(partials) if dist is not None else None, out.data_ptr()))
     return _views(out, offsets, H, W)
+
+
+def quad_images(phasor, permutation=(0, 1, 2, 3), has_gt=False, tonemap=False, out=None):
+    """The four quad images of a view, ``render_ftorf_viz_traj.py:237-244``, as one uint8 device tensor [4, H, W, 3] written
+    by one launch: image i is ``tof_to_image`` (``scene/torf_utils.py:43-50``: clip to [-0.5, 0.5], ``Normalize(-0.5, 0.5)``,
+    matplotlib's ``seismic`` map, ``(255 * rgb).astype(uint8)``) of plane ``3 + permutation[i]`` of ``phasor`` [7, H, W]
+    (float32 on a HIP device, planes read in place through their stride), after ``- 0.5`` when ``has_gt`` and ``x / (1 + x)``
+    when ``tonemap`` (``args.quad_scale > 1``).  ``permutation``: the scene's ``tof_inverse_permutation``, four host integers
+    in 0..3.  ``out``: a contiguous uint8 device tensor [4, H, W, 3] to write into; else a new one.  The bytes are the
+    reference's; nothing is read on the host, so the call can be captured in a graph."""
+    ph, stride = _planes(phasor, "phasor", 7, 7)
+    try:
+        perm = [int(k) for k in (permutation.tolist() if hasattr(permutation, "tolist") else permutation)]
+    except (TypeError, ValueError):
+        raise TypeError("gftorf_amd.present: permutation must be four integers, got %r" % (permutation,)) from None
+    if len(perm) != 4 or any(not 0 <= k <= 3 for k in perm):
+        raise ValueError("gftorf_amd.present: permutation must be four integers in 0..3, got %s" % perm)
+    H, W = int(ph.shape[1]), int(ph.shape[2])
+    named = [(ph, "phasor")]
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (4, H, W, 3) or not out.is_contiguous():
+            raise TypeError("gftorf_amd.present: out must be a contiguous torch.uint8 tensor [4, %d, %d, 3]" % (H, W))
+        named.append((out, "out"))
+    dev = _args.devices(_TAG, "display", named)
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty((4, H, W, 3), device=dev, dtype=torch.uint8)
+    with _lib.on_device(dev):
+        _lib.check(lib.gft_present_quad(_lib.raw_stream(dev), H, W, ph.data_ptr(), stride, (C.c_int32 * 4)(*perm), int(bool(has_gt)),
+                                        int(bool(tonemap)), out.data_ptr()))
+    return out
 
 
 class PhasorRanges:

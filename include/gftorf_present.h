@@ -12,6 +12,7 @@
  *   gft_present_ranges        folds one ground-truth ToF image into the six (lo, hi) of save_input's np.min / np.max over the
  *                             whole sequence (render.py:46-47, 61): a partials launch and a one-workgroup finish
  *   gft_present_ranges_reset  sets the six values to (+inf, -inf) pairs with a kernel
+ *   gft_present_quad          the four quad images of render_ftorf_viz_traj.py:237-244 (tof_to_image, the seismic map): one launch
  *
  * Every statement is numpy's float32 sequence, operation for operation (no contraction, correctly rounded division), so
  * the bytes are the reference's; only arctan2 is not an IEEE operation.  With to8b(x) = trunc(255 * clip(x, 0, 1)), a NaN
@@ -67,6 +68,7 @@ extern "C" {
 #define GFT_PRESENT_PARTIAL_WORDS 2 /* floats of one row of gft_present_view's partials: min, max of dd */
 #define GFT_PRESENT_RANGE_WORDS 6   /* lo, hi of real; of imag; of amp */
 #define GFT_PRESENT_MAGMA_ROWS 257  /* 256 entries, then the NaN row */
+#define GFT_PRESENT_SEISMIC_ROWS 257 /* 256 entries, then the NaN row */
 
 /* Workgroups of a launch = rows of partials for an image of `pixels`; 0 when pixels < 1. */
 int64_t gft_present_blocks(int64_t pixels);
@@ -102,6 +104,18 @@ int gft_present_ranges(void* hip_stream, int64_t pixels, const float* gt_tof, in
 
 /* ranges (DEVICE, 6 floats) = (+inf, -inf) three times, by a kernel (no memset node) */
 int gft_present_ranges_reset(void* hip_stream, float* ranges);
+
+/* The 257 x 4 bytes of trunc(255 * seismic(.)): rows 0..255 matplotlib's `seismic` entries, row 256 the NaN colour (HOST,
+ * static); the fourth byte of a row is not shown. */
+const uint8_t* gft_present_seismic(void);
+
+/* tof_to_image (scene/torf_utils.py:43-50) of the four quad planes, render_ftorf_viz_traj.py:237-244, in one launch.  phasor: 7
+ * planes phasor_stride apart; permutation (HOST, 4 entries in 0..3, read before the call returns): image i shows plane 3 +
+ * permutation[i].  v = plane value, minus 0.5f when has_gt, then v / (1 + v) when tonemap; c = clip(v, -0.5, 0.5), a NaN
+ * stays; n = c + 0.5f; the pixel is the first three bytes of row min(trunc(n * 256), 255) of gft_present_seismic(), of row
+ * 256 for a NaN -- matplotlib's index of the float32 Normalize(-0.5, 0.5).  out: uint8 [4, H, W, 3], every byte written. */
+int gft_present_quad(void* hip_stream, int32_t H, int32_t W, const float* phasor, int64_t phasor_stride,
+                     const int32_t* permutation, int32_t has_gt, int32_t tonemap, void* out);
 
 #ifdef __cplusplus
 }
