@@ -149,6 +149,7 @@ EXPORTS = [
     "gft_grad_norm_scratch_bytes", "gft_grad_norm", "gft_grad_scale",
     "gft_densify_stats", "gft_rows_rank_scratch_bytes", "gft_rows_rank", "gft_rows_rank_dev", "gft_rows_gather", "gft_rows_any_nonzero",
     "gft_densify_plan_scratch_bytes", "gft_densify_classify", "gft_densify_layout", "gft_rows_remap",
+    "gft_split_children",
 ]
 # include/gftorf_flow.h (the scene-flow term; no struct, so the ABI version is unchanged)
 FLOW_EXPORTS = ["gft_flow_loss_blocks", "gft_flow_loss_forward", "gft_flow_loss_backward", "gft_flow_points", "gft_flow_project",
@@ -418,6 +419,9 @@ def load():
     # stream, n_out, map, src, src_rows, extra, dst, row_bytes
     lib.gft_rows_remap.restype = C.c_int
     lib.gft_rows_remap.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]
+    # stream, P, S, N, split_rows, xyz, rotation, scaling, z, new_xyz
+    lib.gft_split_children.restype = C.c_int
+    lib.gft_split_children.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32] + [C.c_void_p] * 6
     lib.gft_knn_scratch_bytes.restype = C.c_size_t
     lib.gft_knn_scratch_bytes.argtypes = [C.c_int32]
     lib.gft_knn_mean_dist2.restype = C.c_int

@@ -1,8 +1,9 @@
 // k_densify.hip -- per-Gaussian bookkeeping around the rasterizer (include/gftorf_densify.h): the
 // statistics update of every iteration, the order-preserving row compaction of `t[mask]`, and the plan and the
-// row mover of a whole densify_and_prune event.
+// row mover of a whole densify_and_prune event, and the children of its split rows (k_split_children).
 // HBM-bound byte work: coalesced reads, one pass.
 #include "gft_internal.h"
+#include "gft_reduce.h"
 #include "gftorf_densify.h"
 
 namespace {
@@ -538,4 +539,61 @@ extern "C" int gft_rows_remap(void* hip_stream, int64_t n_out, const int32_t* ma
                             (const uint32_t*)extra, (uint32_t*)dst);
     GFT_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+// ---- the children of the split rows (scene/gaussian_model.py:577-581, utils/general_utils.py:91-112) -----------------------
+// One thread per split row j: its quaternion, activated scaling and position are read once from the model's own tensors, R
+// is built once, and the position of child k * S + j is written for k < N -- consecutive lanes write consecutive rows.  The
+// arithmetic is stated in include/gftorf_densify.h: every operation rounded on its own as eager torch rounds it, the rotation
+// of the sample as one explicit chain of fused multiply-adds.
+namespace {
+
+constexpr int SC_MAX_BLOCKS = 1 << 16;
+
+__global__ __launch_bounds__(DN_BLOCK) void k_split_children(int64_t P, int64_t S, int N, const int32_t* __restrict__ split_rows,
+                                                             const float* __restrict__ xyz, const float4* __restrict__ rotation,
+                                                             const float* __restrict__ scaling, const float* __restrict__ z,
+                                                             float* __restrict__ new_xyz)
+{
+#pragma clang fp contract(off)
+    for (int64_t j = (int64_t)blockIdx.x * DN_BLOCK + threadIdx.x; j < S; j += (int64_t)gridDim.x * DN_BLOCK) {
+        const int64_t row = split_rows[j];
+        const bool ok = row >= 0 && row < P;                   // (a row outside the model is read nowhere: its children are NaN)
+        const float nan = __int_as_float(0x7fc00000);
+        const float4 r = ok ? rotation[row] : make_float4(nan, nan, nan, nan);
+        const float px = ok ? xyz[3 * row] : nan, py = ok ? xyz[3 * row + 1] : nan, pz = ok ? xyz[3 * row + 2] : nan;
+        const float sx = ok ? scaling[3 * row] : nan, sy = ok ? scaling[3 * row + 1] : nan, sz = ok ? scaling[3 * row + 2] : nan;
+        // build_rotation: q = r / |r|, (w, x, y, z) = q
+        const float norm = sqrtf(r.x * r.x + r.y * r.y + r.z * r.z + r.w * r.w);
+        const float qw = r.x / norm, qx = r.y / norm, qy = r.z / norm, qz = r.w / norm;
+        const float R00 = 1.0f - 2.0f * (qy * qy + qz * qz), R01 = 2.0f * (qx * qy - qw * qz), R02 = 2.0f * (qx * qz + qw * qy);
+        const float R10 = 2.0f * (qx * qy + qw * qz), R11 = 1.0f - 2.0f * (qx * qx + qz * qz), R12 = 2.0f * (qy * qz - qw * qx);
+        const float R20 = 2.0f * (qx * qz - qw * qy), R21 = 2.0f * (qy * qz + qw * qx), R22 = 1.0f - 2.0f * (qx * qx + qy * qy);
+        for (int k = 0; k < N; k++) {
+            const int64_t c = (int64_t)k * S + j;
+            // torch.normal(mean = 0, std): normal_(0, 1) * std + mean
+            const float s0 = z[3 * c] * sx + 0.0f, s1 = z[3 * c + 1] * sy + 0.0f, s2 = z[3 * c + 2] * sz + 0.0f;
+            new_xyz[3 * c] = fmaf(R02, s2, fmaf(R01, s1, R00 * s0)) + px;
+            new_xyz[3 * c + 1] = fmaf(R12, s2, fmaf(R11, s1, R10 * s0)) + py;
+            new_xyz[3 * c + 2] = fmaf(R22, s2, fmaf(R21, s1, R20 * s0)) + pz;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int gft_split_children(void* hip_stream, int64_t P, int64_t S, int32_t N, const int32_t* split_rows, const float* xyz,
+                                  const float* rotation, const float* scaling, const float* z, float* new_xyz)
+{
+    if (P < 0 || S < 0 || N < 1 || S > P) return gft_fail("gft_split_children: bad row counts (P %lld, S %lld, N %d)", (long long)P, (long long)S, (int)N);
+    if ((int64_t)N * S > 0x7fffffffll) return gft_fail("gft_split_children: more than 2^31 - 1 children");
+    if (S == 0) return 0;
+    if (!split_rows || !xyz || !rotation || !scaling || !z || !new_xyz) return gft_fail("gft_split_children: NULL argument");
+    if ((uintptr_t)rotation & 15) return gft_fail("gft_split_children: rotation must be 16-byte aligned");
+    if (((uintptr_t)xyz | (uintptr_t)scaling | (uintptr_t)z | (uintptr_t)new_xyz | (uintptr_t)split_rows) & 3)
+        return gft_fail("gft_split_children: pointers must be 4-byte aligned");
+    const dim3 grid((unsigned)gft_grid_blocks(S, DN_BLOCK, 1, SC_MAX_BLOCKS));
+    hipLaunchKernelGGL(k_split_children, grid, dim3(DN_BLOCK), 0, (hipStream_t)hip_stream, P, S, (int)N, split_rows, xyz,
+                       (const float4*)rotation, scaling, z, new_xyz);
+    return gft_launched("gft_split_children");
 }

@@ -19,6 +19,9 @@ gather or scatter, which at 1 M Gaussians costs more per iteration than the rast
 * :func:`densify_and_prune_fused` -- the whole ``densify_and_prune`` event as one plan and one pass over every tensor (two
   host reads instead of four, every parameter and moment read once and written once), with the same result as the composite;
   its :class:`DensifyResult` carries the new motion mask, a ready ``DeformQuery`` and any caller tensor across the event.
+* :func:`split_children` -- the positions of a split's children in one kernel (``gft_split_children``) instead of the
+  reference's ``build_rotation`` + ``torch.normal`` + ``torch.bmm`` statements: the opt-in ``children="kernel"`` route of
+  :func:`densify_and_prune_fused` and :func:`densify_and_split`, with a contract of its own for the children's ``xyz`` rows.
 
 Kernels: ``csrc/k_densify.hip`` behind ``include/gftorf_densify.h``; no CPU path.
 """
@@ -101,6 +104,13 @@ class RowSelection:
                                          self.mask.data_ptr() if self.P else None, self.rank.data_ptr() if self.P else None,
                                          scratch.data_ptr() if self.P else None, C.byref(n)))
         self.count = int(n.value)
+        self._rows = None
+
+    def rows(self):
+        """The kept rows in increasing order (int32 [count]): ``mask.nonzero()`` without its host read."""
+        if self._rows is None:
+            self._rows = self.take(torch.arange(self.P, device=self.dev, dtype=torch.int32))
+        return self._rows
 
     def take(self, t, out=None):
         """``t[mask]`` (into ``out[:count]`` when given)."""
@@ -250,9 +260,63 @@ def densify_and_clone(pc, grads, grad_threshold, scene_extent):
     densification_postfix(pc, {name: sel.take(getattr(pc, attr)) for name, attr in GROUP_ATTR.items()})
 
 
-def densify_and_split(pc, grads, grad_threshold, scene_extent, N=2):
+def _children_route(children, who):
+    if children not in ("torch", "kernel"):
+        raise ValueError("%s: children must be 'torch' or 'kernel', got %r" % (who, children))
+    return children == "kernel"
+
+
+def split_children(pc, split_rows, n_split, N=2):
+    """The children of the ``n_split`` rows ``split_rows`` (int32, increasing) of ``pc``: ``(new_xyz [N * n_split, 3],
+    new_scaling [N * n_split, 3 or 1], child_max_scaling [N * n_split])``, child ``k * n_split + j`` belonging to row
+    ``split_rows[j]`` as ``repeat(N, ...)`` lays them out.  The positions come from one kernel (``gft_split_children``): the
+    standard normals are one ``torch.randn((N * n_split, 3))``, which consumes torch's generator as ``densify_and_split``'s
+    ``torch.normal(mean=zeros, std=stds)`` does; rotation, activated scaling and position of the split rows are read from the
+    model's tensors, no gathered copies, no rotation matrices in memory, no ``bmm``.  The scalings are the reference's own
+    torch statements on one gather of the split rows (``log`` and ``exp`` stay torch's: their last bit is the build's).
+
+    The positions' contract is the kernel's own (``include/gftorf_densify.h``), not ``torch.bmm``'s bits: the rotation of the
+    same samples by the same R as an ascending chain of fused multiply-adds, within 16 eps (|s_0| + |s_1| + |s_2|) + 2 eps
+    |exact| of the exact value, as the reference's own route is."""
+    xyz = pc.get_xyz
+    _dev_check(xyz, "split_children")
+    lib = _lib.load()
+    dev = xyz.device
+    P, S, N = int(xyz.shape[0]), int(n_split), int(N)
+    if N < 1:
+        raise ValueError("split_children: N must be at least 1, got %d" % N)
+    if split_rows.dtype != torch.int32 or split_rows.device != dev or not split_rows.is_contiguous() or split_rows.numel() < S or S > P:
+        raise RuntimeError("split_children: split_rows must hold the %d split rows as contiguous int32 on %s" % (S, dev))
+    isotropic = getattr(pc, "isotropic", False)
+    with torch.no_grad():
+        scaling = pc.get_scaling
+        stds = scaling.expand(P, 3) if scaling.dim() == 2 and scaling.size(1) == 1 else scaling     # (a get_scaling of one column)
+        xyz_c, rot, stds = xyz.detach().contiguous(), pc._rotation.detach().contiguous(), stds.detach().contiguous()
+        for t, shape, name in ((xyz_c, (P, 3), "get_xyz"), (rot, (P, 4), "_rotation"), (stds, (P, 3), "get_scaling")):
+            if t.dtype != torch.float32 or tuple(t.shape) != shape or t.device != dev:
+                raise RuntimeError("split_children: %s must be float32 %s on %s, got %s %s on %s"
+                                   % (name, shape, dev, t.dtype, tuple(t.shape), t.device))
+        z = torch.randn((N * S, 3), device=dev)
+        new_xyz = torch.empty((N * S, 3), device=dev)
+        ptr = lambda t: t.data_ptr() if t.numel() else None
+        with _lib.on_device(dev):
+            _lib.check(lib.gft_split_children(_lib.raw_stream(dev), P, S, N, ptr(split_rows), ptr(xyz_c), ptr(rot), ptr(stds), ptr(z),
+                                              ptr(new_xyz)))
+        if isotropic:
+            sel = pc.scaling_activation(_remap(lib, dev, S, split_rows, pc._scaling))
+        else:
+            sel = _remap(lib, dev, S, split_rows, scaling)
+        new_scaling = pc.scaling_inverse_activation(sel.repeat(N, 1) / (0.8 * N))
+        child_max_scaling = pc.scaling_activation(new_scaling).max(dim=1).values.contiguous()
+    return new_xyz, new_scaling, child_max_scaling
+
+
+def densify_and_split(pc, grads, grad_threshold, scene_extent, N=2, children="torch"):
     """``GaussianModel.densify_and_split`` (gaussian_model.py:571-601): large Gaussians with a large gradient are
-    replaced by N smaller ones sampled inside them (torch.normal: torch's generator decides the samples)."""
+    replaced by N smaller ones sampled inside them (torch.normal: torch's generator decides the samples).
+    ``children="kernel"``: positions and scalings of the children from :func:`split_children` (same samples, its own
+    rounding of the rotation) instead of the reference's torch statements."""
+    kernel = _children_route(children, "densify_and_split")
     n_init = pc.get_xyz.shape[0]
     dev = pc.get_xyz.device
     padded = torch.zeros((n_init,), device=dev)
@@ -260,17 +324,21 @@ def densify_and_split(pc, grads, grad_threshold, scene_extent, N=2):
     mask = torch.where(padded >= grad_threshold, True, False)
     mask = torch.logical_and(mask, torch.max(pc.get_scaling, dim=1).values > pc.percent_dense * scene_extent)
     sel = RowSelection(mask)
-    scaling_sel = sel.take(pc.get_scaling)
-    stds = scaling_sel.repeat(N, 1)
-    means = torch.zeros((stds.size(0), 3), device=dev)
-    samples = torch.normal(mean=means, std=stds)
     rotation_sel = sel.take(pc._rotation)
-    rots = _rotation_matrices(rotation_sel).repeat(N, 1, 1)
-    new = {"xyz": torch.bmm(rots, samples.unsqueeze(-1)).squeeze(-1) + sel.take(pc.get_xyz).repeat(N, 1)}
-    if getattr(pc, "isotropic", False):
-        new["scaling"] = pc.scaling_inverse_activation(pc.scaling_activation(sel.take(pc._scaling)).repeat(N, 1) / (0.8 * N))
+    if kernel:
+        new_xyz, new_scaling, _ = split_children(pc, sel.rows(), sel.count, N)
+        new = {"xyz": new_xyz, "scaling": new_scaling}
     else:
-        new["scaling"] = pc.scaling_inverse_activation(scaling_sel.repeat(N, 1) / (0.8 * N))
+        scaling_sel = sel.take(pc.get_scaling)
+        stds = scaling_sel.repeat(N, 1)
+        means = torch.zeros((stds.size(0), 3), device=dev)
+        samples = torch.normal(mean=means, std=stds)
+        rots = _rotation_matrices(rotation_sel).repeat(N, 1, 1)
+        new = {"xyz": torch.bmm(rots, samples.unsqueeze(-1)).squeeze(-1) + sel.take(pc.get_xyz).repeat(N, 1)}
+        if getattr(pc, "isotropic", False):
+            new["scaling"] = pc.scaling_inverse_activation(pc.scaling_activation(sel.take(pc._scaling)).repeat(N, 1) / (0.8 * N))
+        else:
+            new["scaling"] = pc.scaling_inverse_activation(scaling_sel.repeat(N, 1) / (0.8 * N))
     new["rotation"] = rotation_sel.repeat(N, 1)
     for name in ("f_dc_color", "f_rest_color", "phase_f_dc", "phase_f_rest", "amp_f_dc", "amp_f_rest"):
         new[name] = sel.take(getattr(pc, GROUP_ATTR[name])).repeat(N, 1, 1)
@@ -364,12 +432,31 @@ class DensifyResult:
         return DeformQuery.from_rank(self.motion_mask, self._motion_rank, self._dynamic)
 
 
+def _children_torch(pc, lib, scaling, split_rows, n_split, N):
+    """``densify_and_split``'s own statements (gaussian_model.py:577-585) on the ``n_split`` rows ``split_rows``."""
+    dev = scaling.device
+    with torch.no_grad():
+        take = lambda t: _remap(lib, dev, n_split, split_rows, t)
+        scaling_sel = take(scaling)
+        stds = scaling_sel.repeat(N, 1)
+        means = torch.zeros((stds.size(0), 3), device=dev)
+        samples = torch.normal(mean=means, std=stds)
+        rots = _rotation_matrices(take(pc._rotation)).repeat(N, 1, 1)
+        new_xyz = torch.bmm(rots, samples.unsqueeze(-1)).squeeze(-1) + take(pc.get_xyz).repeat(N, 1)
+        if getattr(pc, "isotropic", False):
+            new_scaling = pc.scaling_inverse_activation(pc.scaling_activation(take(pc._scaling)).repeat(N, 1) / (0.8 * N))
+        else:
+            new_scaling = pc.scaling_inverse_activation(scaling_sel.repeat(N, 1) / (0.8 * N))
+        child_max_scaling = pc.scaling_activation(new_scaling).max(dim=1).values.contiguous()
+    return new_xyz, new_scaling, child_max_scaling
+
+
 def _f32_positive(x):
     """``x`` rounded to float32, as a kernel argument and torch's comparison with a float32 tensor take it, is > 0."""
     return C.c_float(float(x)).value > 0.0
 
 
-def densify_and_prune_fused(pc, max_grad, min_opacity, extent, max_screen_size=20, N=2):
+def densify_and_prune_fused(pc, max_grad, min_opacity, extent, max_screen_size=20, N=2, children="torch"):
     """``GaussianModel.densify_and_prune`` (gaussian_model.py:624-640) as one plan and one pass over every tensor: leaves
     ``pc`` and its optimizer exactly as :func:`densify_and_prune` does under the same torch generator state (every
     parameter, both moments of every group, ``step``, the order of ``param_groups``, the three statistics), and returns a
@@ -391,7 +478,16 @@ def densify_and_prune_fused(pc, max_grad, min_opacity, extent, max_screen_size=2
     * the statistics are three ``zeros(P')``.
 
     A clone is never split because its padded gradient is 0, which needs ``max_grad > 0`` (as float32): for ``max_grad <=
-    0`` the call goes through :func:`densify_and_prune` (``N`` must then be 2) and the result carries row counts only."""
+    0`` the call goes through :func:`densify_and_prune` (``N`` must then be 2) and the result carries row counts only.
+
+    ``children="kernel"`` (opt-in; the default ``"torch"`` is the route described above, bit for bit): the children's ``xyz``
+    comes from one launch of ``gft_split_children`` (:func:`split_children`) instead of two of the three gathers, the ~45
+    eager launches of the rotation matrices, ``torch.normal`` and the ``torch.bmm`` over N * S 3x3 matrices; the scaling
+    statements stay torch's.  Same generator consumption, same samples, same R, every tensor but the children's ``xyz`` rows
+    bit for bit what the default gives; those rows carry the kernel's own rounding of the three products (an ascending chain
+    of fused multiply-adds) where the default carries ``torch.bmm``'s, both within the same bound of the exact value.  The
+    composite route of ``max_grad <= 0`` ignores the keyword, as it ignores the plan."""
+    kernel = _children_route(children, "densify_and_prune_fused")
     xyz = pc.get_xyz
     _dev_check(xyz, "densify_and_prune_fused")
     lib = _lib.load()
@@ -431,20 +527,11 @@ def densify_and_prune_fused(pc, max_grad, min_opacity, extent, max_screen_size=2
                                             ptr(scratch), counts))
     n_clone, n_split = int(counts[0]), int(counts[1])
 
-    # the children's positions and scalings: densify_and_split's statements on the split rows
-    with torch.no_grad():
-        take = lambda t: _remap(lib, dev, n_split, split_rows, t)
-        scaling_sel = take(scaling)
-        stds = scaling_sel.repeat(N, 1)
-        means = torch.zeros((stds.size(0), 3), device=dev)
-        samples = torch.normal(mean=means, std=stds)
-        rots = _rotation_matrices(take(pc._rotation)).repeat(N, 1, 1)
-        new_xyz = torch.bmm(rots, samples.unsqueeze(-1)).squeeze(-1) + take(xyz).repeat(N, 1)
-        if getattr(pc, "isotropic", False):
-            new_scaling = pc.scaling_inverse_activation(pc.scaling_activation(take(pc._scaling)).repeat(N, 1) / (0.8 * N))
-        else:
-            new_scaling = pc.scaling_inverse_activation(scaling_sel.repeat(N, 1) / (0.8 * N))
-        child_max_scaling = pc.scaling_activation(new_scaling).max(dim=1).values.contiguous()
+    # the children's positions and scalings: one kernel, or densify_and_split's statements on the split rows
+    if kernel:
+        new_xyz, new_scaling, child_max_scaling = split_children(pc, split_rows, n_split, N)
+    else:
+        new_xyz, new_scaling, child_max_scaling = _children_torch(pc, lib, scaling, split_rows, n_split, N)
     extra = {"xyz": new_xyz, "scaling": new_scaling}
 
     # plan, second half: the final prune over the virtual rows and every survivor's place (host read 2: P' and n')

@@ -102,6 +102,32 @@ int gft_densify_layout(void* hip_stream, int64_t P, int64_t C, int64_t S, int32_
 int gft_rows_remap(void* hip_stream, int64_t n_out, const int32_t* map, const void* src, int64_t src_rows, const void* extra,
                    void* dst, int64_t row_bytes);
 
+/* The positions of the N * S children of the S split rows (scene/gaussian_model.py:577-581, build_rotation of
+ * utils/general_utils.py:91-112) in one launch: child k * S + j (the virtual rows' order above) of split row split_rows[j] gets
+ *   new_xyz [N * S, 3] = R(rotation[row]) . (z[child] * scaling[row]) + xyz[row]
+ * xyz [P,3], rotation [P,4] raw (r, x, y, z; 16-byte aligned: one load per row), scaling [P,3] ACTIVATED (get_scaling),
+ * z [N * S, 3] standard normals (torch.randn), read straight from the model's tensors: no gathered copies.  One thread per
+ * split row, vector stores, no atomics, no memset, no host read.  S = 0 returns 0 without a launch; N < 1, S > P,
+ * N * S > 2^31 - 1 and a NULL pointer with S > 0 are refused before anything touches a device.  A split row outside [0, P)
+ * is not read: its children are NaN.
+ * (The children's scaling, log(scaling / (0.8 N)), and its largest exp stay torch statements: this library's logf is the
+ * compiler's of the day, torch.log the one torch was built with, and the two need not agree in the last bit.)
+ *
+ * The arithmetic, every operation rounded to float32 on its own (no contraction) unless stated:
+ *   norm = sqrtf(r0 r0 + r1 r1 + r2 r2 + r3 r3) added left to right, q = r / norm (IEEE division), the nine entries of R as
+ *   build_rotation writes them (1 - 2 (y y + z z), 2 (x y - r z), ...): what eager torch computes on the device; a zero
+ *   quaternion gives NaN, as there.
+ *   s_c = z_c * scaling_c + 0.0f: torch.normal(mean = zeros, std) after its normal_(0, 1); the add turns -0 into +0.
+ *   new_xyz_i = fmaf(R_i2, s_2, fmaf(R_i1, s_1, R_i0 * s_0)) + xyz_i: an ascending chain of fused multiply-adds, then a
+ *   separately rounded add.  The reference forms these three products inside torch.bmm, whose order and fusing belong to
+ *   the BLAS solution picked for the batch count; this route states its own order.  Of the six chains and the three
+ *   pairings of rounded products the ascending chain met torch.bmm's bits most often where it was measured (every
+ *   element at batch counts 1 .. 900000 on an MI355X, profiles/bmm_order_probe.json); nothing relies on that.  Against
+ *   float64 from the same float32 inputs:
+ *   |new_xyz_i - exact| <= 16 eps (|s_0| + |s_1| + |s_2|) + 2 eps |exact|, eps = 2^-23. */
+int gft_split_children(void* hip_stream, int64_t P, int64_t S, int32_t N, const int32_t* split_rows, const float* xyz,
+                       const float* rotation, const float* scaling, const float* z, float* new_xyz);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,8 +9,15 @@ the median, the launches counted from the call sites of one call (every C entry 
 makes, and every ATen operator that computes something, counted by a dispatch mode) and torch.cuda.max_memory_allocated over
 one call (the model itself included).
 
-    timeout 600 python profiles/densify_fused_time.py --out profiles/densify_fused_time.json
-    python profiles/densify_fused_time.py --table profiles/densify_fused_time.json        # the table of DESIGN.md, no device
+A third route, ``fused_kernel_children``, is the fused call with ``children="kernel"`` (the split rows' children from one launch
+of gft_split_children instead of the reference's torch statements); its yardstick is the ``fused`` route of the same session:
+``kernel_median_below_torch_min`` says whether its median lies below that route's fastest run.  gft_split_children alone is
+timed by device events around the call on the model's own split rows (5 warm + 20 timed, preallocated outputs).
+profiles/densify_fused_time.json is the record of the two-route script and stays as it is; this one writes
+profiles/densify_children_time.json.
+
+    timeout 900 python profiles/densify_fused_time.py --out profiles/densify_children_time.json
+    python profiles/densify_fused_time.py --table profiles/densify_children_time.json     # the tables of DESIGN.md, no device
 """
 import argparse
 import json
@@ -28,7 +35,8 @@ from torch.utils._python_dispatch import TorchDispatchMode  # noqa: E402
 MAX_GRAD, MIN_OPACITY, EXTENT, MAX_SCREEN_SIZE = 0.0002, 0.005, 2.0, 20
 WARM, TIMED = 5, 20
 # launches behind one call of a C entry point (csrc/k_densify.hip)
-ENTRY_LAUNCHES = {"gft_rows_rank": 3, "gft_rows_gather": 1, "gft_densify_classify": 3, "gft_densify_layout": 3, "gft_rows_remap": 1}
+ENTRY_LAUNCHES = {"gft_rows_rank": 3, "gft_rows_gather": 1, "gft_densify_classify": 3, "gft_densify_layout": 3, "gft_rows_remap": 1,
+                  "gft_split_children": 1}
 # ATen operators that launch nothing: views, allocations, metadata
 NO_LAUNCH = ("view", "reshape", "squeeze", "unsqueeze", "detach", "alias", "empty", "as_strided", "slice", "select", "expand",
              "_unsafe_view", "t.", "transpose", "permute", "is_", "size", "stride", "numel", "_local_scalar_dense", "lift_fresh",
@@ -83,7 +91,9 @@ def measure(P, dev):
     from oracle import densify_ref
     base = densify_ref.EagerGaussians(P, dev, seed=5)
     routes = {"composite": lambda m: densify.densify_and_prune(m, MAX_GRAD, MIN_OPACITY, EXTENT, MAX_SCREEN_SIZE),
-              "fused": lambda m: densify.densify_and_prune_fused(m, MAX_GRAD, MIN_OPACITY, EXTENT, MAX_SCREEN_SIZE)}
+              "fused": lambda m: densify.densify_and_prune_fused(m, MAX_GRAD, MIN_OPACITY, EXTENT, MAX_SCREEN_SIZE),
+              "fused_kernel_children": lambda m: densify.densify_and_prune_fused(m, MAX_GRAD, MIN_OPACITY, EXTENT, MAX_SCREEN_SIZE,
+                                                                                 children="kernel")}
     times = {name: [] for name in routes}
     rows_after = {}
     for run in range(WARM + TIMED):
@@ -101,7 +111,7 @@ def measure(P, dev):
             rows_after[name] = int(m._xyz.shape[0])
             del m
     out = {"P": P, "rows_after": rows_after["fused"]}
-    assert rows_after["fused"] == rows_after["composite"]
+    assert rows_after["fused"] == rows_after["composite"] == rows_after["fused_kernel_children"]
     for name, route in routes.items():
         m = base.twin()
         torch.cuda.synchronize()
@@ -122,7 +132,39 @@ def measure(P, dev):
         out[name] = dict(median_ms=round(statistics.median(times[name]), 3), min_ms=round(min(times[name]), 3),
                          max_ms=round(max(times[name]), 3), runs=len(times[name]), peak_bytes=peak, model_bytes=before, **counts)
     out["fused_over_composite"] = round(out["fused"]["median_ms"] / out["composite"]["median_ms"], 3)
+    out["kernel_children_over_fused"] = round(out["fused_kernel_children"]["median_ms"] / out["fused"]["median_ms"], 3)
+    out["kernel_median_below_torch_min"] = out["fused_kernel_children"]["median_ms"] < out["fused"]["min_ms"]
+    out["split_children_alone"] = kernel_alone(base, dev)
     return out
+
+
+def kernel_alone(base, dev, N=2):
+    """gft_split_children on the model's own split rows, device events around the call."""
+    from gftorf_amd import _lib
+    lib = _lib.load()
+    grads = base.xyz_gradient_accum / base.denom
+    grads[grads.isnan()] = 0.0
+    scaling = base.get_scaling.detach().contiguous()
+    mask = (grads.reshape(-1) >= MAX_GRAD) & (scaling.max(dim=1).values > base.percent_dense * EXTENT)
+    rows = mask.nonzero().reshape(-1).to(torch.int32).contiguous()
+    P, S = int(mask.numel()), int(rows.numel())
+    z = torch.randn((N * S, 3), device=dev)
+    new_xyz = torch.empty((N * S, 3), device=dev)
+    xyz, rot = base._xyz.detach().contiguous(), base._rotation.detach().contiguous()
+    times = []
+    for run in range(WARM + TIMED):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        _lib.check(lib.gft_split_children(_lib.raw_stream(dev), P, S, N, rows.data_ptr(), xyz.data_ptr(), rot.data_ptr(),
+                                          scaling.data_ptr(), z.data_ptr(), new_xyz.data_ptr()))
+        b.record()
+        torch.cuda.synchronize()
+        if run >= WARM:
+            times.append(a.elapsed_time(b) * 1e3)
+    moved = S * (4 + 12 + 16 + 12) + N * S * (12 + 12)
+    med = statistics.median(times)
+    return dict(S=S, N=N, median_us=round(med, 1), min_us=round(min(times), 1), max_us=round(max(times), 1), bytes=moved,
+                gb_per_s=round(moved / med / 1e3, 1))
 
 
 def table(results):
@@ -133,12 +175,20 @@ def table(results):
     for r in results["sizes"]:
         lines.append("| %d -> %d | %s | %s | %.2f |" % (r["P"], r["rows_after"], cell(r["composite"]), cell(r["fused"]),
                                                         r["fused_over_composite"]))
+    if all("fused_kernel_children" in r for r in results["sizes"]):
+        lines += ["", "| P | fused, children=\"torch\": median (min) | children=\"kernel\": median, launches, peak | kernel / torch | "
+                      "gft_split_children alone |", "|---|---|---|---|---|"]
+        for r in results["sizes"]:
+            k = r["split_children_alone"]
+            lines.append("| %d -> %d | %.2f ms (%.2f) | %s | %.2f | S = %d: %.1f us, %.0f MB, %.0f GB/s |"
+                         % (r["P"], r["rows_after"], r["fused"]["median_ms"], r["fused"]["min_ms"], cell(r["fused_kernel_children"]),
+                            r["kernel_children_over_fused"], k["S"], k["median_us"], k["bytes"] / 1e6, k["gb_per_s"]))
     return "\n".join(lines)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "densify_fused_time.json"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "densify_children_time.json"))
     ap.add_argument("--sizes", type=int, nargs="+", default=[100_000, 1_000_000])
     ap.add_argument("--table", help="print DESIGN.md's table from a result file and exit")
     args = ap.parse_args()
