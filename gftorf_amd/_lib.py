@@ -196,6 +196,9 @@ PRESENT_SEISMIC_ROWS = 257                                                      
 # include/gftorf_tracks.h (the F-ToRF motion tracks; no struct, so the ABI version is unchanged)
 TRACKS_EXPORTS = ["gft_tracks_integrate", "gft_tracks_table_bytes", "gft_tracks_table"]
 TRACKS_PARTS = ("index", "xy", "motion", "step_ok")             # GFT_TRACKS_*: the parts of a table in the order they lie in it
+# include/gftorf_ply.h (the rows of the model's PLY files; no struct, so the ABI version is unchanged)
+PLY_EXPORTS = ["gft_ply_pack", "gft_ply_unpack"]
+PLY_ROWS, PLY_MAX_SOURCES, PLY_MAX_COLUMNS = 64, 16, 240        # GFT_PLY_ROWS, GFT_PLY_MAX_SOURCES, GFT_PLY_MAX_COLUMNS
 
 
 def load():
@@ -391,6 +394,13 @@ def load():
     # stream, P, T, S, mask, rank, xy, step_ok, motion, table
     lib.gft_tracks_table.restype = C.c_int
     lib.gft_tracks_table.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64] + [C.c_void_p] * 6
+    _ints = C.POINTER(C.c_int32)
+    # stream, P, count, sources, widths, channels, K_full, K_sibr, out_full, out_sibr
+    lib.gft_ply_pack.restype = C.c_int
+    lib.gft_ply_pack.argtypes = [C.c_void_p, C.c_int64, C.c_int32, _ptrs, _ints, _ints, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    # stream, rows, row0, K_file, chunk, count, dests, widths, table
+    lib.gft_ply_unpack.restype = C.c_int
+    lib.gft_ply_unpack.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, _ptrs, _ints, _ints]
     lib.gft_densify_stats.restype = C.c_int
     lib.gft_densify_stats.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8
     lib.gft_rows_rank_scratch_bytes.restype = C.c_size_t
