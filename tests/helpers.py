@@ -304,3 +304,272 @@ def oracle_rasterizer(oracle, scene, **over):
     def render(frame_id, means3D, means2D, opacities, shs, shs_p, scales, rotations):
         return _OracleRasterize.apply(oracle, kw, means3D, means2D, opacities, shs, shs_p, scales, rotations)
     return render
+
+
+# ---------------------------------------------------------------------------
+# The paths of dL/dmeans3D (tests/test_grad_paths.py, tests/test_gpu_grad_paths.py): a Gaussian's position is used eight
+# times (torch_ref.PATHS), and its gradient is the sum of one term per use.  A whole-tensor max-norm sees the largest
+# term only (the projected mean: 0.99 of |dL/dmeans3D|_inf in small_scene()); here every term is a yardstick of its own.
+PATH_CASES = {      # upstream case -> {plane: its channels that are non-zero}; every other upstream value is an exact zero
+    "color": dict(color=slice(0, 3)),
+    "phasor01": dict(phasor=slice(0, 2)),
+    "phasor2": dict(phasor=slice(2, 3)),
+    "phasor3to6": dict(phasor=slice(3, 7)),
+    "depth": dict(depth=slice(0, 1)),
+    "acc": dict(acc=slice(0, 1)),
+    "depth_distortion": dict(depth_distortion=slice(0, 1)),
+    "all": {k: slice(None) for k in GRAD_KEYS},
+    "phasor": dict(phasor=slice(0, 7)),          # (the whole plane: for the shares of DESIGN.md section 11b, not a GPU case)
+}
+_PHASOR_PATHS = ("mean2D", "cov_t", "dir_phasor", "dist_phase", "dist_factor")
+CASE_PATHS = {      # the paths that exist for a case (every other part of dL/dmeans3D is an exact zero)
+    "color": ("mean2D", "cov_t", "dir_color"),
+    "phasor01": _PHASOR_PATHS,
+    "phasor2": ("mean2D", "cov_t", "dir_phasor", "dist_factor"),      # amplitude / dist^2: no phase
+    "phasor3to6": _PHASOR_PATHS,
+    "phasor": _PHASOR_PATHS,
+    "depth": ("mean2D", "cov_t", "dist_depth"),
+    "acc": ("mean2D", "cov_t"),
+    "depth_distortion": ("mean2D", "cov_t", "dist_ndc"),
+    "all": ("mean2D", "cov_t", "dir_color", "dir_phasor", "dist_phase", "dist_factor", "dist_depth", "dist_ndc"),
+}
+GPU_PATH_CASES = ("color", "phasor01", "phasor2", "phasor3to6", "depth", "acc", "depth_distortion", "all")
+PHASOR_CASES = ("phasor01", "phasor2", "phasor3to6")
+
+
+def case_paths(case, scene, inputs=None):
+    """CASE_PATHS under the scene's argument pattern: precomputed colours have no view direction; precomputed phasors have
+    neither a view direction nor, in the reference's backward, any phasor chain (torch_ref's docstring)."""
+    g = dict(scene["gaussians"], **(inputs or {}))
+    drop = set()
+    if g.get("shs") is None:
+        drop.add("dir_color")
+    if g.get("shs_p") is None:
+        drop |= {"dir_phasor", "dist_phase", "dist_factor"}
+    return tuple(p for p in CASE_PATHS[case] if p not in drop)
+
+
+def case_upstream(scene, case):
+    """scene["grads"] with everything outside the case's channels set to zero."""
+    up = {k: np.zeros_like(v) for k, v in scene["grads"].items()}
+    for k, sl in PATH_CASES[case].items():
+        up[k][sl] = scene["grads"][k][sl]
+    return up
+
+
+def path_scene(D=3, vdp=True):
+    """A scene in which every path of dL/dmeans3D is large: 120 Gaussians, 48 x 32, near the wide camera (z 0.5 .. 1.5:
+    directions and distances change fast), large splats, and higher SH degrees of size 0.5 (colour) and 0.3 (phasor)
+    instead of synth's 0.1 and 0.05.  All 120 Gaussians are blended; 60 of them have a clamped colour channel, 23 a
+    clamped amplitude.  Shares of |dL/dmeans3D|_inf per path when only the named upstream plane is non-zero (float64,
+    tests/test_grad_paths.py asserts that each is at least 0.05):
+        color              mean2D 0.94, cov_t 0.63, dir_color 0.57
+        phasor             mean2D 0.50, cov_t 0.24, dir_phasor 0.52, dist_phase 0.36, dist_factor 0.87
+        depth              mean2D 0.88, cov_t 0.20, dist_depth 0.38
+        acc                mean2D 0.95, cov_t 0.19
+        depth_distortion   mean2D 0.35, cov_t 0.30, dist_ndc 0.56
+        all five together  mean2D 0.93, cov_t 0.33, dir_color 0.41, dir_phasor 0.41, dist_phase 0.29, dist_factor 0.68,
+                           dist_depth 0.094, dist_ndc 0.030
+    Seed 7: with seed 5 (shares as low as 0.089) one pair of the walk has |alpha - 1/255| = 2.0e-7, inside the 1e-4 / 255
+    that test_grad_paths.py asks for; here the closest pair is 1.2e-6 away, |power| >= 3.5e-5, |test_T - 1e-4| >= 8.4e-4,
+    and no SH sum is within 4.9e-4 of its clamp.
+    D, vdp: the SH degree in use (of 16 coefficients) and use_view_dependent_phase."""
+    sc = small_scene(P=120, W=48, H=32, D=D, scale_lo=0.05, scale_hi=0.3, z_lo=0.5, z_hi=1.5, camera="wide", seed=7)
+    rng = np.random.default_rng(1)
+    g = sc["gaussians"]
+    g["shs"][:, 1:, :] = rng.normal(0, 0.5, g["shs"][:, 1:, :].shape).astype(np.float32)
+    g["shs_p"][:, 1:, :] = rng.normal(0, 0.3, g["shs_p"][:, 1:, :].shape).astype(np.float32)
+    sc["use_view_dependent_phase"] = vdp
+    return sc
+
+
+def isolated_scene(seed=20):
+    """12 Gaussians on a 4 x 3 grid of a 48 x 32 image (identity pose, the centred camera) whose 3 sigma extents do not
+    overlap: every pixel blends one Gaussian at most, so a row of a gradient tensor is one Gaussian's own sum.  Opacities
+    0.02 .. 0.9, screen-space sigmas 0.45 .. 1.45 pixels and depths 0.6 .. 4 make the rows' sizes span decades (asserted in
+    tests/test_grad_paths.py), which a whole-tensor norm never looks at."""
+    W, H, nx, ny = 48, 32, 4, 3
+    P = nx * ny
+    sc = small_scene(P=P, W=W, H=H, w2c=None, seed=seed)
+    cam = sc["cam"]
+    rng = np.random.default_rng(seed + 500)
+    focal = W / (2.0 * cam["tanfovx"])
+    order = rng.permutation(P)
+    cx = ((order % nx) + 0.5) * (W / nx) - 0.5 + rng.uniform(-0.4, 0.4, P)
+    cy = ((order // nx) + 0.5) * (H / ny) - 0.5 + rng.uniform(-0.4, 0.4, P)
+    z = np.exp(np.linspace(np.log(0.5), np.log(5.5), P))
+    sigma_px = np.linspace(1.45, 0.35, P)                     # 3 sqrt(1.45^2 + 0.3) = 4.7 < 16/3 - 0.4, half a cell less the jitter
+    g = sc["gaussians"]
+    g["means3D"] = np.stack([(cx - (W - 1) / 2.0) / focal * z, (cy - (H - 1) / 2.0) / focal * z, z], 1).astype(np.float32)
+    g["scales"] = ((sigma_px * z / focal)[:, None] * rng.uniform(0.5, 1.0, (P, 3))).astype(np.float32)
+    g["opacities"] = np.exp(np.linspace(np.log(0.9), np.log(0.02), P))[:, None].astype(np.float32)
+    return sc
+
+
+_GRAD_NAMES = dict(means3D="dL_dmeans3D", means2D="dL_dmeans2D", opacities="dL_dopacity", scales="dL_dscales",
+                   rotations="dL_drotations", shs="dL_dsh", shs_p="dL_dsh_p", colors_precomp="dL_dcolors",
+                   cov3D_precomp="dL_dcov3D", phase_offset="dL_dphase_offset", dc_offset="dL_ddc_offset")
+
+
+def oracle_grads(b, scene, inputs=None):
+    """The oracle's backward under the names and shapes of run_gpu's gradients."""
+    g = dict(scene["gaussians"], **(inputs or {}))
+    out = {}
+    for k, n in _GRAD_NAMES.items():
+        if k in ("means2D", "phase_offset", "dc_offset"):      # no input array of that name
+            out[k] = b[n]
+        elif g.get(k) is not None:
+            out[k] = b[n].reshape(g[k].shape)
+    return out
+
+
+def path_variant(name):
+    """The scenes of the path tests: (scene, inputs, upstream cases)."""
+    if name == "base":
+        return path_scene(), None, GPU_PATH_CASES
+    if name in ("D1", "D2"):                       # degrees 1 and 2 of 16 coefficients: the higher columns are exact zeros
+        return path_scene(D=int(name[1])), None, ("color",) + PHASOR_CASES
+    if name == "no_vdp":                           # use_view_dependent_phase off: the SH phase is not used, the amplitude is
+        return path_scene(vdp=False), None, PHASOR_CASES
+    rng = np.random.default_rng(9)
+    if name == "phasors_precomp":
+        pp = np.stack([rng.uniform(-0.5, 0.5, 120), rng.uniform(0.05, 0.5, 120)], 1).astype(np.float32)
+        return path_scene(), dict(shs_p=None, phasors_precomp=pp), PHASOR_CASES
+    if name == "colors_precomp":
+        return path_scene(), dict(shs=None, colors_precomp=rng.random((120, 3)).astype(np.float32)), ("color",)
+    raise KeyError(name)
+
+
+PATH_VARIANTS = ("base", "D1", "D2", "no_vdp", "phasors_precomp", "colors_precomp")
+_F64_CACHE = {}
+
+
+def path_reference(name, oracle, cases=None, margins=None):
+    """path_variant(name) with the oracle's forward and the float64 gradients of its cases: (scene, inputs, f, ref)."""
+    scene, inputs, own = path_variant(name) if name != "isolated" else (isolated_scene(), None, ("all",))
+    if name == "base" and cases is None:
+        cases = GPU_PATH_CASES + ("phasor",)      # (the whole phasor plane too: its shares are asserted on the CPU)
+    f, _ = run_oracle(oracle, scene, backward=False, inputs=inputs)
+    return scene, inputs, f, float64_case_grads(name, scene, f, cases or own, inputs=inputs, margins=margins)
+
+
+def oracle_case_grads(oracle, scene, f, case, inputs=None):
+    up = case_upstream(scene, case)
+    return oracle_grads(oracle.backward(f, up["color"], up["phasor"], up["depth"], up["acc"], up["depth_distortion"]), scene, inputs)
+
+
+def gpu_case_grads(scene, dev, case, inputs=None, **over):
+    return run_gpu(dict(scene, grads=case_upstream(scene, case)), dev, inputs=inputs, optimize_offsets=True, **over)[1]
+
+
+def float64_case_grads(key, scene, f, cases, inputs=None, margins=None):
+    """The float64 gradients (tests/torch_ref.py, autograd) of `scene` for each upstream case of `cases` (names of
+    PATH_CASES), blending the lists of the oracle's forward `f`.  Returns {case: grads}: grads[input] for every input that
+    has a gradient, "means2D" [P, 2], "phase_offset" / "dc_offset" (the scalars) with "phase_offset_abs" / "dc_offset_abs"
+    (the sums of the absolute per-Gaussian terms: the offsets are given to torch_ref per Gaussian), and "parts":
+    {path: that path's term of dL/dmeans3D}, each equal to the full gradient minus the one with that use detached
+    (settings["detach"]) but taken from the same backward: dL/d(use), carried on to means3D.
+    key: results are computed once per key and shared; nobody writes to them.  margins: torch_ref's settings["margins"]."""
+    import torch_ref
+    key = (key, tuple(cases))
+    if key in _F64_CACHE and margins is None:
+        return _F64_CACHE[key]
+    dt = torch.float64
+    g = dict(scene["gaussians"], **(inputs or {}))
+    P = g["means3D"].shape[0]
+    params = {k: torch.tensor(v, dtype=dt, requires_grad=True) for k, v in g.items() if v is not None}
+    for k in ("shs", "shs_p", "colors_precomp", "phasors_precomp", "cov3D_precomp", "scales", "rotations"):
+        params.setdefault(k, None)
+    params["phase_offset"] = torch.full((P,), scene["phase_offset"], dtype=dt, requires_grad=True)
+    params["dc_offset"] = torch.full((P,), scene["dc_offset"], dtype=dt, requires_grad=True)
+    out = torch_ref.render(params, f, oracle_kwargs(scene, split_uses=True, margins=margins))
+    names = [k for k, v in params.items() if v is not None]
+    uses = [(n, t) for n in torch_ref.PATHS for t in out["uses"].get(n, []) if t.requires_grad]
+    res = {}
+    for case in cases:
+        up = case_upstream(scene, case)
+        loss = sum((out[k] * torch.tensor(up[k], dtype=dt)).sum() for k in GRAD_KEYS)
+        got = torch.autograd.grad(loss, [params[k] for k in names] + [out["ndc"]] + [t for _, t in uses],
+                                  retain_graph=True, allow_unused=True)
+        z = lambda gr, like: torch.zeros_like(like) if gr is None else gr
+        r = {k: z(gr, params[k]).numpy() for k, gr in zip(names, got)}
+        r["means2D"] = z(got[len(names)], out["ndc"]).numpy()
+        for k in ("phase_offset", "dc_offset"):
+            r[k + "_abs"] = float(np.abs(r[k]).sum())
+            r[k] = np.array([r[k].sum()])
+        parts = {n: np.zeros((P, 3)) for n in torch_ref.PATHS}
+        for (n, t), gr in zip(uses, got[len(names) + 1:]):
+            if gr is not None:
+                parts[n] = parts[n] + torch.autograd.grad(t, params["means3D"], grad_outputs=gr, retain_graph=True)[0].numpy()
+        r["parts"] = parts
+        res[case] = r
+    _F64_CACHE[key] = res
+    return res
+
+
+def check_path_case(tag, case, ref, got, paths, rtol, f=None, D=3, rows=False):
+    """The measure of tests/test_gpu_grad_paths.py.  ref: float64_case_grads(...)[case]; got: gradients under run_gpu's names
+    (a device's, or oracle_grads'); paths: the paths that exist (case_paths); f: the oracle's forward (the clamp bits).
+      means3D    |got - ref|_inf <= rtol * min over `paths` of |that path's part|_inf
+      shs, shs_p, colors_precomp per (coefficient, channel) column: <= rtol * the column's max over rows; columns whose reference is zero
+                 everywhere (inactive degrees, a plane without that input) are exact zeros
+      clamp bits where clamped[row, c]: dL/dshs[row, :, c] == 0; where clamped_p[row]: dL/dshs_p[row, :, 1] == 0; exactly
+      scales, rotations, opacities, means2D, cov3D_precomp: <= rtol * the tensor's max-norm; means2D[:, 2] == 0
+      phase_offset, dc_offset (where `got` has them): <= rtol * the sum of the absolute per-Gaussian terms; exact zeros
+                 where every term is zero
+    rows=True (isolated_scene): instead, every row of every tensor against rtol * its own max.
+    Returns (ratios, failures): {quantity: worst error / its yardstick} (to be compared with rtol) and a list of messages."""
+    ratios, bad = {}, []
+
+    def ratio(name, err, scale):
+        if scale == 0.0:
+            if err != 0.0:
+                bad.append("%s %s %s: %.3g where the reference is an exact zero" % (tag, case, name, err))
+            return
+        ratios[name] = max(ratios.get(name, 0.0), err / scale)
+        if not err <= rtol * scale:
+            bad.append("%s %s %s: error %.3g = %.3g of its yardstick %.3g (bound %.3g)" % (tag, case, name, err, err / scale, scale, rtol))
+
+    def f64(a):
+        a = np.asarray(a, np.float64)
+        assert np.isfinite(a).all(), "%s %s: non-finite gradient" % (tag, case)
+        return a
+
+    m2 = f64(got["means2D"])
+    if not (m2[:, 2] == 0).all():
+        bad.append("%s %s means2D[:, 2] is not zero" % (tag, case))
+    tensors = dict(means3D=(ref["means3D"], f64(got["means3D"])), means2D=(ref["means2D"], m2[:, :2]))
+    for k in ("opacities", "scales", "rotations", "shs", "shs_p", "colors_precomp", "cov3D_precomp"):
+        if ref.get(k) is not None and got.get(k) is not None:
+            tensors[k] = (ref[k], f64(got[k]).reshape(ref[k].shape))
+    if rows:
+        for k, (r, g_) in tensors.items():
+            r2, g2 = r.reshape(r.shape[0], -1), g_.reshape(r.shape[0], -1)
+            for i in range(r2.shape[0]):
+                ratio(k + " rows", float(np.abs(g2[i] - r2[i]).max()), float(np.abs(r2[i]).max()))
+        return ratios, bad
+    for k, (r, g_) in tensors.items():
+        err = np.abs(g_ - r)
+        if k == "means3D":
+            ratio("means3D / smallest path", float(err.max()), min(float(np.abs(ref["parts"][p]).max()) for p in paths))
+            ratios["means3D / max-norm"] = float(err.max()) / float(np.abs(r).max())
+        elif k in ("shs", "shs_p", "colors_precomp"):
+            r3, e3 = r.reshape(r.shape[0], -1, r.shape[-1]), err.reshape(r.shape[0], -1, r.shape[-1])
+            for j in range(r3.shape[1]):
+                for c in range(r3.shape[2]):
+                    if j >= (D + 1) ** 2 and (np.abs(r3[:, j, c]).max() != 0.0):
+                        bad.append("%s %s: the reference has a gradient at an inactive coefficient" % (tag, case))
+                    ratio("%s columns" % k, float(e3[:, j, c].max()), float(np.abs(r3[:, j, c]).max()))
+        else:
+            ratio(k, float(err.max()), float(np.abs(r).max()))
+    if f is not None and "shs" in tensors:
+        cl = f.geom["clamped"].astype(bool)
+        if tensors["shs"][1].transpose(0, 2, 1)[cl].any():
+            bad.append("%s %s: dL/dshs is not zero at a clamped colour channel" % (tag, case))
+    if f is not None and "shs_p" in tensors:
+        if tensors["shs_p"][1][f.geom["clamped_p"].astype(bool), :, 1].any():
+            bad.append("%s %s: dL/dshs_p's amplitude column is not zero at a clamped amplitude" % (tag, case))
+    for k in ("phase_offset", "dc_offset"):
+        if got.get(k) is not None:
+            ratio(k, float(np.abs(f64(got[k]).reshape(-1)[0] - ref[k][0])), ref[k + "_abs"])
+    return ratios, bad

@@ -415,6 +415,11 @@ def test_phasors_precomp(oracle, gpu):
     f, b = Hh.run_oracle(oracle, scene, inputs=inputs)
     out, grads, _ = Hh.run_gpu(scene, gpu, inputs=inputs)
     check_outputs(f, out)
+    # the inputs that have a gradient (the reference has no backward for phasors_precomp: rasterize_points.cu returns none)
+    s2 = dict(scene)
+    s2["gaussians"] = dict(scene["gaussians"], **inputs)
+    check_grads(b, grads, s2)
+    assert grads.get("phasors_precomp") is None or not grads["phasors_precomp"].any()
 
 
 @pytest.mark.parametrize("vdp", [False, True])

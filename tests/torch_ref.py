@@ -13,6 +13,9 @@ Deliberate gradient conventions of the reference that autograd must mimic:
     clamped value is dropped (backward.cu:293-297,383-385).
   * phase DC removal "- C0*sh_p[0].x" (forward.cu:115) is not differentiated
     (backward.cu:168-169).
+  * with phasors_precomp the backward has no phasor chain at all: it stands inside "if (shs_p != nullptr)"
+    (backward.cu:527-587), so the distance in the phase and in 1/dist^2 and the DC offset get no gradient there (the
+    precomputed phasors themselves get none either: rasterize_points.cu returns no dL_dphasors).
 Discrete decisions (culling, radii, tile lists, skips, termination) are taken
 from the oracle's forward so both sides blend the same lists.
 """
@@ -87,12 +90,41 @@ def _depth_distortion_tile(ids, pix_x, pix_y, con_x, con_y, con_z, opac, d_ndc, 
     return DD
 
 
+# The uses of a Gaussian's position, by name (settings["detach"]): dL/dmeans3D is the sum of one term per use.
+PATHS = ("mean2D", "cov_t", "dir_color", "dir_phasor", "dist_phase", "dist_factor", "dist_depth", "dist_ndc")
+
+
 def render(params, fwd, settings, dd_only=False):
     """params: dict of float64 leaf tensors (means3D, opacities, shs|colors_precomp,
     shs_p|phasors_precomp, scales+rotations|cov3D_precomp, phase_offset, dc_offset).
     fwd: oracle ForwardResult (lists / masks).  settings: dict of scalars + matrices.
     Returns dict of output images (float64) + 'ndc' (retain_grad leaf-like).
-    dd_only (forward only, call under torch.no_grad()): only the depth_distortion plane, by _depth_distortion_tile."""
+    dd_only (forward only, call under torch.no_grad()): only the depth_distortion plane, by _depth_distortion_tile.
+    settings["detach"] (optional, a set of names from PATHS; default empty = nothing changes): each name cuts exactly one use of
+    means3D out of the graph, the forward values staying what they are -- mean2D: pix_x, pix_y; cov_t: the p_view that enters
+    J and its clamp; dir_color / dir_phasor: the view direction into the colour / phasor SH; dist_phase, dist_factor,
+    dist_depth, dist_ndc: the distance into the phase, into 1/dist^2, into the depth output, into d_ndc.  By the chain rule
+    dL/dmeans3D minus the one computed with a name detached is that path's term.
+    settings["split_uses"] (optional, default off = nothing changes): the tensor at each of these cuts becomes a node of its
+    own (a view, no arithmetic: the outputs stay bit-identical, the gradients' sums may be taken in another order) and is
+    returned in 'uses' (name -> list), so that dL/d(use) can be asked for and taken on to means3D, which gives every path's
+    term from one backward.
+    settings["margins"] (optional, a dict that is filled in): how far the walk's discrete decisions stand from their edges,
+    over every (pixel, list entry) pair the walk looks at -- "alpha": min |alpha - 1/255| where power <= 0; "power": min
+    |power| (the skip is power > 0); "test_T": min |test_T - 1e-4| over the pairs that are not skipped."""
+    cut = frozenset(settings.get("detach", ()))
+    assert cut <= set(PATHS), cut
+    if params.get("phasors_precomp") is not None:
+        cut = cut | {"dist_phase", "dist_factor"}      # the reference's convention (module docstring)
+    split, uses = bool(settings.get("split_uses", False)), {}
+
+    def dz(t, name):
+        if name in cut:
+            t = t.detach()
+        elif split:
+            t = t.view_as(t)
+        uses.setdefault(name, []).append(t)
+        return t
     dt = torch.float64
     W, H = settings["image_width"], settings["image_height"]
     V = torch.tensor(np.asarray(settings["viewmatrix"]).reshape(4, 4), dtype=dt)  # transposed storage
@@ -116,8 +148,8 @@ def render(params, fwd, settings, dd_only=False):
     ndc = p_hom[:, :2] * p_w
     if ndc.requires_grad:          # (a forward-only call under torch.no_grad() has no graph)
         ndc.retain_grad()
-    pix_x = ((ndc[:, 0] + 1.0) * W - 1.0) * 0.5
-    pix_y = ((ndc[:, 1] + 1.0) * H - 1.0) * 0.5
+    pix_x = dz(((ndc[:, 0] + 1.0) * W - 1.0) * 0.5, "mean2D")
+    pix_y = dz(((ndc[:, 1] + 1.0) * H - 1.0) * 0.5, "mean2D")
 
     # cov3D
     if params.get("cov3D_precomp") is not None:
@@ -136,7 +168,8 @@ def render(params, fwd, settings, dd_only=False):
         Sigma = Rm @ torch.diag_embed(s * s) @ Rm.transpose(1, 2)
 
     # cov2D (EWA)
-    tx, ty, tz = p_view[:, 0], p_view[:, 1], p_view[:, 2]
+    pv_cov = dz(p_view, "cov_t")
+    tx, ty, tz = pv_cov[:, 0], pv_cov[:, 1], pv_cov[:, 2]
     limx, limy = 1.3 * tanfovx, 1.3 * tanfovy
     txtz, tytz = tx / tz, ty / tz
     gx_mul = ((txtz >= -limx) & (txtz <= limx)).to(dt)
@@ -161,26 +194,30 @@ def render(params, fwd, settings, dd_only=False):
     dir_orig = p - campos
     dirs = dir_orig / dir_orig.norm(dim=1, keepdim=True)
     if params.get("shs") is not None:
-        rgb = torch.clamp(sh_poly(D, params["shs"], dirs) + 0.5, min=0.0)
+        rgb = torch.clamp(sh_poly(D, params["shs"], dz(dirs, "dir_color")) + 0.5, min=0.0)
     else:
         rgb = params["colors_precomp"]
 
     dist = p_view.norm(dim=1)
-    d_ndc = far_n / (far_n - near_n) * (1 - near_n / dist)
-    factor = 1.0 / (dist * dist)
+    d_ndc = far_n / (far_n - near_n) * (1 - near_n / dz(dist, "dist_ndc"))
+    dist_f = dz(dist, "dist_factor")
+    factor = 1.0 / (dist_f * dist_f)
+    dist_ph = dz(dist, "dist_phase")
+    dist_out = dz(dist, "dist_depth")
     phase_offset, dc_offset = params["phase_offset"], params["dc_offset"]
     if params.get("phasors_precomp") is not None:
         pp = params["phasors_precomp"]
-        phase = dist * dist2phase
+        dc_offset = dc_offset.detach()
+        phase = dist_ph * dist2phase
         if vdp:
             phase = phase + pp[:, 0]
         amp = pp[:, 1]
     elif params.get("shs_p") is not None:
         sp = params["shs_p"]
-        pa = sh_poly(D, sp, dirs) + 0.5
+        pa = sh_poly(D, sp, dz(dirs, "dir_phasor")) + 0.5
         phase_sh = pa[:, 0] - 0.5 - (C0 * sp[:, 0, 0]).detach()
         amp = torch.clamp(pa[:, 1], min=0.0)
-        phase = dist * dist2phase + phase_offset
+        phase = dist_ph * dist2phase + phase_offset
         if vdp:
             phase = phase + phase_sh
     else:
@@ -236,6 +273,12 @@ def render(params, fwd, settings, dd_only=False):
             alpha = a_raw + (torch.clamp(a_raw, max=0.99) - a_raw).detach()
             skip = (power > 0) | (alpha < 1.0 / 255.0)
             test_T = T * (1 - alpha)
+            if settings.get("margins") is not None:
+                mg, live = settings["margins"], ~done
+                for name, val, where in (("alpha", alpha - 1.0 / 255.0, live & (power <= 0)), ("power", power, live),
+                                         ("test_T", test_T - 1e-4, live & ~skip)):
+                    if bool(where.any()):
+                        mg[name] = min(mg.get(name, math.inf), float(val.detach().abs()[where].min()))
             newly_done = (~skip) & (~done) & (test_T < 1e-4)
             done = done | newly_done
             act = (~skip) & (~done)
@@ -244,7 +287,7 @@ def render(params, fwd, settings, dd_only=False):
             w_p = alpha * T * T * am
             Cc = Cc + w[:, None] * rgb[j][None, :]
             Pp = Pp + w_p[:, None] * ph7[j][None, :]
-            Dd = Dd + w * dist[j]
+            Dd = Dd + w * dist_out[j]
             zz = d_ndc[j]
             DD = DD + w * (zz * zz * Aa - 2 * zz * DD_D + DD_D2)
             DD_D = DD_D + w * zz
@@ -266,4 +309,4 @@ def render(params, fwd, settings, dd_only=False):
     if dd_only:
         return dict(depth_distortion=out_dd)
     return dict(color=out_color, phasor=out_phasor, depth=out_depth, acc=out_acc,
-                depth_distortion=out_dd, ndc=ndc)
+                depth_distortion=out_dd, ndc=ndc, uses=uses)
