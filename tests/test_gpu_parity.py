@@ -377,6 +377,41 @@ def test_sh_degrees(D, M, oracle, gpu):
         assert not grads["shs_p"][:, (D + 1) ** 2:, :].any()
 
 
+@pytest.mark.parametrize("D,M", [(0, 16), (1, 16), (2, 16), (3, 16), (0, 9), (1, 9), (2, 9), (0, 4)])
+def test_sh_degrees_without_direction_records(D, M, oracle, gpu):
+    """The backward that is told not to use the forward's direction-gradient records (api.native_backward with
+    want_bw_records=False, gft_config.want_backward = 0): it reads the SH coefficients again and forms dL/dsh in
+    k_preprocess.hip's sh_backward -- with M = 16 in place on the staged row that held the coefficients, otherwise straight
+    into the tensor -- whose tail loop writes the zeros of the inactive coefficients.  Every other backward of the suite has
+    the records and goes through sh_backward_basis.  The forward is the one the pybind-level route makes (records written,
+    no accumulator); the gradients are the oracle's at that degree and the inactive columns exact zeros."""
+    from gftorf_amd import api
+    scene = Hh.small_scene(D=D, sh_coeffs=M, P=250)
+    f, b = Hh.run_oracle(oracle, scene)
+    g = scene["gaussians"]
+    t = lambda a: torch.tensor(np.asarray(a), dtype=torch.float32, device=gpu)
+    s = Hh.gpu_settings(scene, gpu)
+    r = api.native_forward(s, t(g["means3D"]), t(g["shs"]), t(g["shs_p"]), None, None, t(g["opacities"]), t(g["scales"]),
+                           t(g["rotations"]), None, scene["phase_offset"], scene["dc_offset"], True, False)
+    means3D_c, _, sh_c, sh_p_c, scales_c, rot_c, cov_c, _, _ = r["inputs"]
+    up = tuple(t(scene["grads"][k]) for k in Hh.GRAD_KEYS)
+    got = api.native_backward(s, means3D_c, None, sh_c, sh_p_c, scales_c, rot_c, cov_c, r["outputs"][10], r["geom"], r["binning"],
+                              r["img"], r["bg"], r["consts"], scene["phase_offset"], scene["dc_offset"], up, None, False, False,
+                              want_bw_records=False)
+    torch.cuda.synchronize()
+    assert api.last_call_stats["grads_reused"] is False
+    grads = dict(means3D=got["means3D"], means2D=got["means2D"], opacities=got["opacities"].reshape(g["opacities"].shape),
+                 shs=got["sh"], shs_p=got["sh_p"], scales=got["scales"], rotations=got["rotations"])
+    grads = {k: v.cpu().numpy() for k, v in grads.items()}
+    check_grads(b, grads, scene)
+    n = (D + 1) ** 2
+    blended = (np.asarray(f.radii) > 0) & (np.asarray(f.pixels).reshape(-1) > 0)
+    assert grads["shs"].shape == (250, M, 3) and grads["shs_p"].shape == (250, M, 2) and blended.sum() > 100
+    for k in ("shs", "shs_p"):
+        assert not grads[k][:, n:].any(), (k, float(np.abs(grads[k][:, n:]).max()))
+        assert grads[k][blended][:, n - 1].any(), k
+
+
 def test_colors_precomp_and_no_tof(oracle, gpu):
     """render_flow pattern (gaussian_renderer/__init__.py:194-202): precomputed colours,
     no shs_p / phasors -> phasor planes are background only."""
@@ -1451,6 +1486,81 @@ def test_kept_gradient_tensors_switch_between_rows_and_full_writes(oracle, gpu):
     assert all(m[0] for m in modes[1:])                                # one buffer went round
     assert any(m[0] and not m[1] for m in modes[:7])                   # the dense frame came to be written in full ...
     assert any(m[1] for m in modes[7:14])                              # ... and the sparse one by rows again
+
+
+KEPT_DEGREE_CASES = {
+    # scene, the degrees of the calls in order, how the kept set is written, GFT_BWD_DETERMINISTIC's flag
+    # 4500 Gaussians: three workgroups of the rows kernel at its 2048-Gaussian chunk; 15 % of them blended: rows only throughout
+    "sparse_rows": (dict(P=4500, W=96, H=64, spread=3.0), (3, 1, 3, 0, 2), "rows", False),
+    "dense_full": (dict(P=3000, seed=51, opacity=0.03), (3, 1, 3, 0, 2), "full", False),
+    # M != 16: the SH rows of a full write do not go through the LDS staging
+    "dense_nine_coefficients": (dict(P=3000, seed=51, opacity=0.03, sh_coeffs=9, D=2), (2, 0, 1), "full", False),
+    "dense_deterministic": (dict(P=3000, seed=51, opacity=0.03), (3, 1, 3, 0, 2), "full", True),
+}
+KEPT_DEGREE_SHIFTS = (0.0, 0.5, -0.4, 0.25, -0.8)      # world x of every Gaussian at each call: the blended set changes
+
+
+@pytest.mark.parametrize("name", list(KEPT_DEGREE_CASES))
+def test_kept_gradient_tensors_across_sh_degrees(name, oracle, gpu):
+    """The SH degree is not part of the key of a kept set of gradient tensors (api.state.grad_pool: device, P, layout): one set
+    is written at degree 3, then 1, 3, 0, 2 -- rising as in training (oneupSHdegree), and falling as when a viewer or an
+    evaluation renders under grad at another degree, the order in which a row written with 48 columns has to be cleaned.
+    One set of leaves; between the calls every Gaussian moves, so that each call meets rows the last one wrote and it does
+    not (zero_gradient_rows), rows both write (sh_backward's tail loop over the inactive coefficients) and rows only it
+    writes.  Every call: the gradients are the oracle's at that degree, and the columns of the inactive coefficients are
+    exact zeros over ALL rows.  GFT_GRADS_REUSE_CHECK's test of the unmarked rows is on."""
+    from gftorf_amd import api, GaussianRasterizer
+    if not api._GRADS_REUSE:
+        pytest.skip("gradient-tensor reuse is off")
+    kw, degrees, write, deterministic = KEPT_DEGREE_CASES[name]
+    base = Hh.small_scene(**kw)
+    P, M = base["cfg"]["P"], base["cfg"]["sh_coeffs"]
+    keep = (api._GRADS_CHECK, api._DETERMINISTIC)
+    api._grad_pool.clear()
+    api._GRADS_CHECK, api._DETERMINISTIC = True, deterministic
+    try:
+        leaf = {k: torch.tensor(v, dtype=torch.float32, device=gpu, requires_grad=True) for k, v in base["gaussians"].items() if v is not None}
+        m2 = torch.zeros((P, 3), device=gpu, requires_grad=True)
+        x0 = leaf["means3D"].detach()[:, 0].clone()
+        up = {k: torch.tensor(base["grads"][k], device=gpu) for k in Hh.GRAD_KEYS}
+        modes, last = [], None
+        for D, dx in zip(degrees, KEPT_DEGREE_SHIFTS):
+            with torch.no_grad():
+                leaf["means3D"][:, 0] = x0 + dx
+            g = dict(base["gaussians"], means3D=leaf["means3D"].detach().cpu().numpy())
+            scene = dict(base, gaussians=g, cfg=dict(base["cfg"], D=D))
+            f, b = Hh.run_oracle(oracle, scene)
+            blended = (np.asarray(f.radii) > 0) & (np.asarray(f.pixels).reshape(-1) > 0)
+            if last is not None:           # the three kinds of row
+                assert (last & ~blended).sum() >= 10 and (last & blended).sum() >= 10 and (~last & blended).sum() >= 10, (name, D)
+            last = blended
+            o = GaussianRasterizer(raster_settings=Hh.gpu_settings(scene, gpu))(
+                means3D=leaf["means3D"], means2D=m2, opacities=leaf["opacities"], shs=leaf["shs"], shs_p=leaf["shs_p"],
+                scales=leaf["scales"], rotations=leaf["rotations"], phase_offset=scene["phase_offset"], dc_offset=scene["dc_offset"])
+            modes.append((D, api.last_call_stats["grads_reused"], api.last_call_stats["grads_rows_only"], float(blended.mean())))
+            sum((dict(zip(Hh.OUT_NAMES, o))[k] * up[k]).sum() for k in Hh.GRAD_KEYS).backward()
+            torch.cuda.synchronize()
+            grads = {k: v.grad.cpu().numpy() for k, v in leaf.items()}
+            grads["means2D"] = m2.grad.cpu().numpy()
+            for v in list(leaf.values()) + [m2]:
+                v.grad = None
+            del o
+            check_grads(b, grads, scene)
+            n = (D + 1) ** 2
+            assert grads["shs"].shape == (P, M, 3) and grads["shs_p"].shape == (P, M, 2)
+            for k in ("shs", "shs_p"):
+                assert not grads[k][:, n:].any(), (name, D, k, float(np.abs(grads[k][:, n:]).max()), int(np.abs(grads[k][:, n:]).reshape(P, -1).any(1).sum()))
+                assert n >= M or grads[k][blended][:, :n].any(), (name, D, k)
+    finally:
+        api._GRADS_CHECK, api._DETERMINISTIC = keep
+        api._grad_pool.clear()
+    print(name, "(degree, reused, rows only, blended share):", modes)
+    assert not modes[0][1] and all(m[1] for m in modes[1:]), modes               # one set went through every degree
+    if write == "rows":
+        assert all(m[2] for m in modes[1:]) and all(m[3] < api._DENSE_SHARE for m in modes), modes
+    else:
+        # the second call writes its rows and reports their number, the calls behind it write everything
+        assert modes[1][2] and not any(m[2] for m in modes[2:]) and all(m[3] > api._DENSE_SHARE for m in modes), modes
 
 
 def test_accumulator_is_kept_and_left_zero(oracle, gpu):

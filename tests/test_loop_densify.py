@@ -13,8 +13,8 @@ evaluated on the product's own state just before that step (Adam turns rounding 
 turns it into another P: two free-running trajectories cannot be compared tightly enough to see a stale buffer).
 
 Every Gaussian is static here; the deformation network and a motion mask that densification keeps in step are carried through
-the same kind of loop by tests/test_loop_dynamic.py.  Not covered: the SH degree schedule, and the length of a real run (38
-iterations, not 7 000).
+the same kind of loop by tests/test_loop_dynamic.py; the SH degree schedule (here the constant 3, _Loop's `degrees`) by
+tests/test_loop_sh_degree.py.  Not covered: the length of a real run (38 iterations, not 7 000).
 
 CPU tests: the restated reset_opacity / replace_tensor_to_optimizer against a per-row loop, the twin copy, the thresholds."""
 import numpy as np
@@ -126,17 +126,19 @@ def test_thresholds_select_rows_in_every_branch():
 
 # ---- GPU -------------------------------------------------------------------------------------------------------------------
 class _Loop:
-    """The loop of one mode: model, optimizer, target, the iteration (eager or captured per shape), the events, the checks."""
+    """The loop of one mode: model, optimizer, target, the iteration (eager or captured per shape and SH degree), the events,
+    the checks.  `degrees`: iteration -> active SH degree (oneupSHdegree's schedule, train.py); None: 3 throughout."""
 
-    def __init__(self, mode, dev, oracle, spread):
-        from gftorf_amd import FusedAdam, GaussianRasterizer
+    def __init__(self, mode, dev, oracle, spread, degrees=None):
+        from gftorf_amd import FusedAdam
         self.mode, self.dev, self.oracle, self.sparse = mode, dev, oracle, spread > 2.0
         self.scene = helpers.small_scene(P=1500, W=96, H=64, seed=33, spread=spread)
-        self.rast = GaussianRasterizer(raster_settings=helpers.gpu_settings(self.scene, dev))
-        self.frames = []                 # every rasterizer call: dict(P, captured, R = num_rendered, backward, reused, rows_only)
+        self.degrees = degrees if degrees is not None else (lambda it: self.scene["cfg"]["D"])
+        self.D, self.rasts = self.scene["cfg"]["D"], {}
+        self.frames = []                 # every rasterizer call: dict(P, D, captured, R = num_rendered, backward, reused, rows_only)
         g = self.scene["gaussians"]
         t32 = lambda a: torch.tensor(np.asarray(a, np.float32), device=dev)
-        with torch.no_grad():            # the target: a render of the unperturbed scene
+        with torch.no_grad():            # the target: a render of the unperturbed scene (at the full degree)
             out = self.render(t32(g["means3D"]), torch.zeros((1500, 3), device=dev), t32(g["opacities"]).reshape(1500, 1),
                               t32(g["shs"]), t32(g["shs_p"]), t32(g["scales"]), t32(g["rotations"]))
             self.target = dict(color=out[0].clone(), phasor=out[1].clone())
@@ -145,21 +147,33 @@ class _Loop:
         self.it = 0
         self.new_shape()
 
+    def rasterizer(self, D):
+        """One GaussianRasterizer per degree, its settings carrying that degree (and its own tensors: kept for the run)."""
+        from gftorf_amd import GaussianRasterizer
+        if D not in self.rasts:
+            self.rasts[D] = GaussianRasterizer(raster_settings=helpers.gpu_settings(self.scene, self.dev, sh_degree=D))
+        return self.rasts[D]
+
+    def scene_at(self, D):
+        """The scene as the composed reference takes it at degree `D` (cfg["D"] is what helpers.run_oracle hands the oracle)."""
+        return dict(self.scene, cfg=dict(self.scene["cfg"], D=D))
+
     def render(self, m3, m2, op, shs, shp, sc, ro):
         from gftorf_amd import api
-        out = self.rast(means3D=m3, means2D=m2, opacities=op, shs=shs, shs_p=shp, scales=sc, rotations=ro,
-                        phase_offset=self.scene["phase_offset"], dc_offset=self.scene["dc_offset"])
-        self.frames.append(dict(P=m3.shape[0], captured=torch.cuda.is_current_stream_capturing(), R=api.last_call_stats["num_rendered"],
+        out = self.rasterizer(self.D)(means3D=m3, means2D=m2, opacities=op, shs=shs, shs_p=shp, scales=sc, rotations=ro,
+                                      phase_offset=self.scene["phase_offset"], dc_offset=self.scene["dc_offset"])
+        self.frames.append(dict(P=m3.shape[0], D=self.D, captured=torch.cuda.is_current_stream_capturing(), R=api.last_call_stats["num_rendered"],
                                 backward=torch.is_grad_enabled(), reused=api.last_call_stats.get("grads_reused"),
                                 rows_only=api.last_call_stats.get("grads_rows_only")))
         return out
 
     def new_shape(self):
-        """After an event: nothing of the old shape is kept -- the graph, its static tensors, the screen-space leaf."""
+        """After an event: nothing of the old shape is kept -- the graphs (one per degree), their static tensors, the
+        screen-space leaf.  `in_shape` counts the iterations of the shape at the degree in use."""
         self.P = self.pc._xyz.shape[0]
         self.ssp = torch.zeros((self.P, 3), device=self.dev, requires_grad=True)
         self.mask = torch.zeros((self.P,), dtype=torch.bool, device=self.dev)        # no motion mask: every Gaussian is static
-        self.in_shape, self.graph, self.static = 0, None, None
+        self.in_shape, self.graphs = 0, {}
 
     def body(self):
         """The device work of one iteration (train.py:164-231, 441-449, 468-474); what the checks read is copied before the
@@ -187,6 +201,7 @@ class _Loop:
 
     def iteration(self, checked):
         pc = self.pc
+        self.next_degree()
         self.it += 1
         for grp in pc.optimizer.param_groups:                                  # gaussian_model.py:294-310
             if grp["name"] == "xyz":
@@ -198,33 +213,49 @@ class _Loop:
         if not replay:
             kept = self.body()
         else:
-            if self.graph is None:
+            if self.D not in self.graphs:
                 # torch's recipe for a whole-iteration capture: eager iterations first, no gradient tensor alive
                 torch.cuda.synchronize()
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph):
-                    self.static = self.body()
-                self.graph = graph            # (the capture ran nothing: this iteration is the first replay)
+                    static = self.body()
+                self.graphs[self.D] = (graph, static)      # (the capture ran nothing: this iteration is the first replay)
             pc.optimizer.refresh_lr()
-            self.graph.replay()
-            kept = self.static
+            graph, kept = self.graphs[self.D]
+            graph.replay()
         self.in_shape += 1
         torch.cuda.synchronize()
-        what = "iteration %d (P = %d, %s%s)" % (self.it, self.P, self.mode, ", replay" if replay else "")
+        what = "iteration %d (P = %d, D = %d, %s%s)" % (self.it, self.P, self.D, self.mode, ", replay" if replay else "")
         after = L.optimizer_state(pc)
         L.assert_adam_step(before, kept["grads"], lrs, after, what)             # every iteration
         assert set(kept["grads"]) == set(L.NAMES) - {"f_seg_color"}, what
         assert np.isfinite(float(kept["loss"])), what
+        self.every_iteration(before, kept, after, what)
         if checked:
             self.check_render(before, kept, what)
             self.check_stats(stats, kept, what)
         return replay
 
+    def next_degree(self):
+        """The degree of the next iteration (oneupSHdegree): a degree step begins a new phase of the shape -- `in_shape` starts
+        again; the shape stays, and so do the graphs of its earlier degrees.  Returns the degree."""
+        D = self.degrees(self.it + 1)
+        if D != self.D:
+            self.D, self.in_shape = D, 0
+        return D
+
+    def every_iteration(self, before, kept, after, what):
+        """Further checks of every iteration (tests/test_loop_sh_degree.py)."""
+
+    def checked_step(self, before, kept, f, ref, what):
+        """Further checks of a checked step (from the state `before`) against the composed reference's forward `f` and
+        gradients `ref`."""
+
     def check_render(self, before, kept, what):
         color, phasor = kept["color"].cpu().numpy(), kept["phasor"].cpu().numpy()
         up_c = L.l1_upstream(color, self.target_np["color"], 1.0)
         up_p = L.l1_upstream(phasor, self.target_np["phasor"], 0.5)
-        f, ref = L.composed_reference(self.oracle, self.scene, {n: before[n]["param"] for n in L.NAMES}, up_c, up_p)
+        f, ref = L.composed_reference(self.oracle, self.scene_at(self.D), {n: before[n]["param"] for n in L.NAMES}, up_c, up_p)
         mae_c = float(np.abs(color - f["color"]).mean())
         # (the phasor planes are amplitudes, not bounded by one: the colour's bound in units of the largest reference value)
         mae_p = float(np.abs(phasor - f["phasor"]).mean()) / max(1.0, float(np.abs(f["phasor"]).max()))
@@ -236,6 +267,7 @@ class _Loop:
         for k, v in rels.items():
             assert v < 1e-3, (what, k, v)
         assert int((kept["radii"] > 0).sum()) > 100 and np.abs(ref["xyz"]).max() > 0, what
+        self.checked_step(before, kept, f, ref, what)
 
     def check_stats(self, stats, kept, what):
         acc, den, mr = stats
@@ -253,14 +285,15 @@ class _Loop:
         tw = pc.twin()
         L.assert_same_snapshot(pc, tw, "twin before " + kind)
         P0, seed, what = self.P, 1000 + self.it, "%s after iteration %d" % (kind, self.it)
-        if kind in ("densify", "densify_screen"):
+        if kind in ("densify", "densify_screen", "densify_fused"):
             th = L.thresholds(pc)
             clone, split, _ = L.selections(pc, th)
             size = 20 if kind == "densify_screen" else None
             torch.manual_seed(seed)
             tw.densify_and_prune(th["max_grad"], th["min_opacity"], th["extent"], size)
             torch.manual_seed(seed)
-            densify.densify_and_prune(pc, th["max_grad"], th["min_opacity"], th["extent"], size)
+            product = densify.densify_and_prune_fused if kind == "densify_fused" else densify.densify_and_prune
+            product(pc, th["max_grad"], th["min_opacity"], th["extent"], size)
             P1 = pc._xyz.shape[0]
             pruned = P0 + int(clone.sum()) + int(split.sum()) - P1
             assert int(clone.sum()) >= 1 and int(split.sum()) >= 1 and pruned >= 1 and P1 != P0, (what, int(clone.sum()), int(split.sum()), pruned, P1)

@@ -26,6 +26,8 @@ counts its rows on the device and a captured one runs over the rows that count; 
 `apply_mask=get_motion_mask` renders the dynamic region alone, as train.py:446-447 does -- the reference's masked branch
 (gaussian_model.py:652-654) is only defined when every visible Gaussian is inside the mask.
 
+The SH degree is the constant 3 here (_Loop's `degrees`); tests/test_loop_sh_degree.py runs the "torf" loop while it rises.
+
 With no dynamic row the query does not run the network: its parameters get no gradient and its optimizer takes no step
 (gftorf_amd/query.py).
 
@@ -231,14 +233,16 @@ def network_reference(params, X, T, g_dxyz, g_dsh, got, eps=RELU_EDGE):
 
 
 class _Loop:
-    """The loop of one mode and schedule: model, network, optimizers, target, the iteration (eager or captured per shape),
-    the events, the checks."""
+    """The loop of one mode and schedule: model, network, optimizers, target, the iteration (eager or captured per shape and
+    SH degree), the events, the checks.  `degrees`: iteration -> active SH degree (oneupSHdegree's schedule, train.py); None:
+    3 throughout."""
 
-    def __init__(self, mode, schedule, dev, oracle):
-        from gftorf_amd import DeformQuery, FusedAdam, GaussianRasterizer, reference_network
+    def __init__(self, mode, schedule, dev, oracle, degrees=None):
+        from gftorf_amd import DeformQuery, FusedAdam, reference_network
         self.mode, self.schedule, self.dev, self.oracle = mode, schedule, dev, oracle
         self.scene = helpers.small_scene(P=1500, W=96, H=64, seed=33)
-        self.rast = GaussianRasterizer(raster_settings=helpers.gpu_settings(self.scene, dev))
+        self.degrees = degrees if degrees is not None else (lambda it: self.scene["cfg"]["D"])
+        self.D, self.rasts = self.scene["cfg"]["D"], {}
         g = self.scene["gaussians"]
         t32 = lambda a: torch.tensor(np.asarray(a, np.float32), device=dev)
         with torch.no_grad():            # the target: a render of the unperturbed, undeformed scene
@@ -259,18 +263,25 @@ class _Loop:
         self.maxima = {}
         self.new_shape(DeformQuery(pc.get_motion_mask.contiguous()))
 
+    def rasterizer(self, D):
+        """One GaussianRasterizer per degree, its settings carrying that degree."""
+        from gftorf_amd import GaussianRasterizer
+        if D not in self.rasts:
+            self.rasts[D] = GaussianRasterizer(raster_settings=helpers.gpu_settings(self.scene, self.dev, sh_degree=D))
+        return self.rasts[D]
+
     def render(self, m3, m2, op, shs, shp, sc, ro):
-        return self.rast(means3D=m3, means2D=m2, opacities=op, shs=shs, shs_p=shp, scales=sc, rotations=ro,
-                         phase_offset=self.scene["phase_offset"], dc_offset=self.scene["dc_offset"])
+        return self.rasterizer(self.D)(means3D=m3, means2D=m2, opacities=op, shs=shs, shs_p=shp, scales=sc, rotations=ro,
+                                       phase_offset=self.scene["phase_offset"], dc_offset=self.scene["dc_offset"])
 
     def new_shape(self, q):
-        """After an event: the query of the new mask; nothing else of the old shape is kept -- the graph, its static tensors,
-        the screen-space leaf."""
+        """After an event: the query of the new mask; nothing else of the old shape is kept -- the graphs (one per degree),
+        their static tensors, the screen-space leaf.  `in_shape` counts the iterations of the shape at the degree in use."""
         self.q, self.mask = q, q.motion_mask
         self.P, self.n = self.pc._xyz.shape[0], q.n
         assert q.P == self.P
         self.ssp = torch.zeros((self.P, 3), device=self.dev, requires_grad=True)
-        self.in_shape, self.graph, self.static = 0, None, None
+        self.in_shape, self.graphs = 0, {}
         K = 2 if self.schedule == "ftorf" else 1
         self.times_dev = torch.zeros((K,), device=self.dev)
         self.combine_dev = torch.zeros((1, K), device=self.dev)
@@ -319,6 +330,7 @@ class _Loop:
 
     def iteration(self, checked):
         pc = self.pc
+        self.next_degree()
         self.it += 1
         for grp in pc.optimizer.param_groups:                                  # gaussian_model.py:294-310
             if grp["name"] == "xyz":
@@ -333,34 +345,52 @@ class _Loop:
         if not replay:
             kept = self.body(times if self.schedule == "ftorf" else times[0], combine)
         else:
-            if self.graph is None:
+            if self.D not in self.graphs:
                 # torch's recipe for a whole-iteration capture: eager iterations first, no gradient tensor alive
                 torch.cuda.synchronize()
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph):
-                    self.static = self.body(self.times_dev, self.combine_dev if combine is not None else None)
-                self.graph = graph            # (the capture ran nothing: this iteration is the first replay)
+                    static = self.body(self.times_dev, self.combine_dev if combine is not None else None)
+                self.graphs[self.D] = (graph, static)      # (the capture ran nothing: this iteration is the first replay)
             self.times_dev.copy_(t_dev)
             if combine is not None:
                 self.combine_dev.copy_(torch.tensor(combine, dtype=torch.float32, device=self.dev))
             pc.optimizer.refresh_lr()
-            self.graph.replay()
-            kept = self.static
+            graph, kept = self.graphs[self.D]
+            graph.replay()
         self.in_shape += 1
         torch.cuda.synchronize()
-        what = "iteration %d (P = %d, n = %d, K = %d, %s %s%s)" % (self.it, self.P, self.n, len(times), self.schedule, self.mode,
-                                                                  ", replay" if replay else "")
-        L.assert_adam_step(before, kept["grads"], lrs, L.optimizer_state(pc), what)
+        what = "iteration %d (P = %d, n = %d, K = %d, D = %d, %s %s%s)" % (self.it, self.P, self.n, len(times), self.D, self.schedule,
+                                                                          self.mode, ", replay" if replay else "")
+        after = L.optimizer_state(pc)
+        L.assert_adam_step(before, kept["grads"], lrs, after, what)
         assert set(kept["grads"]) == set(L.NAMES) - {"f_seg_color"}, what
         assert np.isfinite(float(kept["loss"])), what
         # the network: exactly the expected parameters have a gradient, and its Adam step is the CPU twin's
         net_grads = {k: v.cpu() for k, v in kept["net_grads"].items()}
         assert set(net_grads) == self.expected_net_grads(), (what, sorted(set(net_grads) ^ self.expected_net_grads()))
-        L.assert_adam_step(net_before, net_grads, {k: NET_LR for k in net_before}, network_state(self.net, self.opt_net), what + " network")
+        net_after = network_state(self.net, self.opt_net)
+        L.assert_adam_step(net_before, net_grads, {k: NET_LR for k in net_before}, net_after, what + " network")
         self.net_steps += self.n > 0
+        self.every_iteration(before, kept, after, net_grads, net_after, what)
         if checked:
             self.check(before, net_before, stats, probe, kept, times, combine, what)
         return replay
+
+    def next_degree(self):
+        """The degree of the next iteration (oneupSHdegree): a degree step begins a new phase of the shape -- `in_shape` starts
+        again; the shape stays, and so do the graphs of its earlier degrees.  Returns the degree."""
+        D = self.degrees(self.it + 1)
+        if D != self.D:
+            self.D, self.in_shape = D, 0
+        return D
+
+    def every_iteration(self, before, kept, after, net_grads, net_after, what):
+        """Further checks of every iteration (tests/test_loop_sh_degree.py)."""
+
+    def checked_step(self, before, kept, f, ref, what):
+        """Further checks of a checked step (from the state `before`) against the composed reference's forward `f` and
+        gradients `ref`."""
 
     def probe(self, times, times_arg):
         """Before a checked step, on the weights the step will use: the query's inputs and the K d_xyz blocks themselves (the
@@ -409,7 +439,8 @@ class _Loop:
         color, phasor = kept["color"].cpu().numpy(), kept["phasor"].cpu().numpy()
         up_c = L.l1_upstream(color, self.target_np["color"], 1.0)
         up_p = L.l1_upstream(phasor, self.target_np["phasor"], 0.5)
-        f, ref = L.composed_reference_dynamic(self.oracle, self.scene, {k: before[k]["param"] for k in L.NAMES}, mask, o_comb, o_sh,
+        scene = dict(self.scene, cfg=dict(self.scene["cfg"], D=self.D))          # (cfg["D"]: what helpers.run_oracle hands the oracle)
+        f, ref = L.composed_reference_dynamic(self.oracle, scene, {k: before[k]["param"] for k in L.NAMES}, mask, o_comb, o_sh,
                                               up_c, up_p, regions)
         mae_c = float(np.abs(color - f["color"]).mean())
         mae_p = float(np.abs(phasor - f["phasor"]).mean()) / max(1.0, float(np.abs(f["phasor"]).max()))
@@ -422,6 +453,7 @@ class _Loop:
             assert v < 1e-3, (what, k, v)
         assert int(visible.sum()) > 100 and np.abs(ref["xyz"]).max() > 0, what
         assert n == 0 or int((visible & mask.numpy()).sum()) >= 30, what
+        self.checked_step(before, kept, f, ref, what)
         # ---- the network's gradients: the oracle's gradient on its offsets, through the coefficients and the written-out adjoint
         net_rels = {}
         if n:
