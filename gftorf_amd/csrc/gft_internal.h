@@ -293,7 +293,11 @@ __device__ __forceinline__ bool gft_splat_reaches_box(const float4& a0, const fl
     const float ca = a0.z, cb = a0.w, cc = a1.x, op = a1.y;
     const float det = ca * cc - cb * cb;
     const float tau = __logf(255.0f * op);
-    if (!(tau > 0.0f)) return false;            // opacity <= 1/255: can never pass the alpha test
+    // opacity < 1/255 (or NaN): can never pass the alpha test.  Decided on the opacity itself, as the blend decides on alpha:
+    // an opacity of exactly 1/255 has 255 o round to 1 and tau = 0 (and the logarithm of the next float above 1 need not come
+    // out positive), yet it is blended where power = 0 (a mean on a pixel centre); the margin below covers a tau that is
+    // short of zero by the logarithm's rounding.
+    if (!(op >= 1.0f / 255.0f)) return false;
     if (!(det > 0.0f && ca > 0.0f && cc > 0.0f)) return true;   // degenerate conic: let the pixel test decide
     const float ux0 = bx0 - a0.x, ux1 = ux0 + bw;
     const float uy0 = by0 - a0.y, uy1 = uy0 + bh;

@@ -573,3 +573,243 @@ def check_path_case(tag, case, ref, got, paths, rtol, f=None, D=3, rows=False):
         if got.get(k) is not None:
             ratio(k, float(np.abs(f64(got[k]).reshape(-1)[0] - ref[k][0])), ref[k + "_abs"])
     return ratios, bad
+
+
+# ---------------------------------------------------------------------------
+# Degenerate Gaussians (tests/test_hostile_rows.py, tests/test_gpu_hostile.py): rows that training produces and
+# synth.make_gaussians never does -- collapsed axes, unnormalised quaternions, raw opacities, clones, points behind the camera,
+# a Gaussian that covers the frame -- each under a name, so that a test can hold every one of them to its own yardstick.
+HOSTILE_W, HOSTILE_H, HOSTILE_P = 48, 32, 160
+HOSTILE_ROWS = (
+    "zero3", "zero1", "needle", "pancake", "giant",
+    "q_small", "q_large", "q_zero", "q_negw",
+    "op_zero", "op_one", "op_above_one", "op_negative", "thr_below", "thr_above", "thr_exact",
+    "behind", "at_camera", "pixel_centre", "tile_corner", "off_one_tile_in", "off_miss", "beyond_clamp",
+    "rect_lo_exact", "rect_hi_exact", "rect_hi_touch",
+    "clone_a0", "clone_a1", "clone_a2", "pair_front", "pair_opaque", "pair_back",
+)
+ALPHA_MIN = np.float32(1.0) / np.float32(255.0)      # the blend's `alpha < 1.0f / 255.0f`
+_HOSTILE = {}
+
+
+def _focal(scene):
+    return scene["cfg"]["W"] / (2.0 * scene["cam"]["tanfovx"])
+
+
+def _mean_at(scene, px, py, z):
+    """The camera-space (= world-space: identity pose) position that projects to pixel (px, py) at depth z, in float32."""
+    W, H, f = scene["cfg"]["W"], scene["cfg"]["H"], _focal(scene)
+    return np.array([(px - (W - 1) / 2.0) / f * z, (py - (H - 1) / 2.0) / f * z, z], np.float32)
+
+
+def exact_means(oracle, scene, targets, reach=64):
+    """For every (px, py, z) of `targets`, inside the frame: a float32 position whose projected mean in the ORACLE's arithmetic
+    is (px, py) bit for bit.  The floats within `reach` steps of the analytic x and y are all projected once.  (Not every
+    target can be hit: where ndc's ulp, times half the image size, is coarser than the pixel coordinate's, no float may
+    land on it -- at W = 48 every centre from 12 to 35 can; at H = 32 the ndc of a centre is dyadic and every one can.)"""
+    ks = np.arange(-reach, reach + 1)
+    rows = []
+    for px, py, z in targets:
+        m = _mean_at(scene, px, py, z)
+        c = np.repeat(m[None], ks.size, 0)
+        c[:, 0] = m[0] + ks * np.spacing(m[0])
+        c[:, 1] = m[1] + ks * np.spacing(m[1])
+        rows.append(c)
+    cand = np.concatenate(rows).astype(np.float32)
+    probe = small_scene(P=cand.shape[0], W=scene["cfg"]["W"], H=scene["cfg"]["H"], w2c=None, scale_lo=0.02, scale_hi=0.03)
+    probe["gaussians"]["means3D"] = cand
+    f, _ = run_oracle(oracle, dict(probe, cam=scene["cam"]), backward=False)
+    assert (f.radii > 0).all()
+    m2 = f.geom["means2D"].reshape(len(targets), ks.size, 2)
+    out = []
+    for t, (px, py, z) in enumerate(targets):
+        ix, iy = np.flatnonzero(m2[t, :, 0] == np.float32(px)), np.flatnonzero(m2[t, :, 1] == np.float32(py))
+        assert ix.size and iy.size, "no float projects to (%s, %s) at depth %s" % (px, py, z)
+        c = cand.reshape(len(targets), ks.size, 3)[t]
+        out.append(np.array([c[ix[ix.size // 2], 0], c[iy[iy.size // 2], 1], c[0, 2]], np.float32))
+    return out
+
+
+def ewa_radius(scene, i):
+    """float64 restatement of forward.cu's projected mean and 3 sigma radius of row i (scales and rotations; the oracle writes
+    neither for a Gaussian whose tile rectangle is empty).  Returns (px, py, radius)."""
+    cam, cfg, g = scene["cam"], scene["cfg"], scene["gaussians"]
+    V = cam["viewmatrix"].astype(np.float64).reshape(4, 4)
+    t = np.append(g["means3D"][i].astype(np.float64), 1.0) @ V
+    hom = np.append(g["means3D"][i].astype(np.float64), 1.0) @ cam["projmatrix"].astype(np.float64).reshape(4, 4)
+    ndc = hom[:2] / (hom[3] + 1e-7)
+    px, py = ((ndc[0] + 1) * cfg["W"] - 1) * 0.5, ((ndc[1] + 1) * cfg["H"] - 1) * 0.5
+    r, x, y, z = g["rotations"][i].astype(np.float64)
+    R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y)],
+                  [2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x)],
+                  [2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)]])
+    Sigma = R @ np.diag(g["scales"][i].astype(np.float64) ** 2) @ R.T
+    fx, fy = cfg["W"] / (2.0 * cam["tanfovx"]), cfg["H"] / (2.0 * cam["tanfovy"])
+    tx = np.clip(t[0] / t[2], -1.3 * cam["tanfovx"], 1.3 * cam["tanfovx"]) * t[2]
+    ty = np.clip(t[1] / t[2], -1.3 * cam["tanfovy"], 1.3 * cam["tanfovy"]) * t[2]
+    J = np.array([[fx / t[2], 0, -fx * tx / t[2] ** 2], [0, fy / t[2], -fy * ty / t[2] ** 2]])
+    A = J @ V[:3, :3].T
+    c = A @ Sigma @ A.T
+    a, b, d = c[0, 0] + 0.3, c[0, 1], c[1, 1] + 0.3
+    mid, det = 0.5 * (a + d), a * d - b * b
+    return px, py, float(np.ceil(3.0 * np.sqrt(mid + np.sqrt(max(0.1, mid * mid - det)))))
+
+
+def giant_row(scene, i, px, py):
+    """Row i becomes a Gaussian of scale 20 .. 30 at depth 5: a 3 sigma radius of hundreds of pixels (below 1e5: the
+    oracle's and the device's float -> int conversions agree), faint, behind most of the scene."""
+    g = scene["gaussians"]
+    c2w = np.linalg.inv(scene["cam"]["w2c"].astype(np.float64))
+    g["means3D"][i] = (np.append(_mean_at(scene, px, py, 5.0).astype(np.float64), 1.0) @ c2w.T)[:3].astype(np.float32)
+    g["scales"][i] = np.array([30.0, 20.0, 25.0], np.float32)
+    g["opacities"][i] = 0.05
+
+
+def hostile_scene(oracle):
+    """(scene, rows): 160 Gaussians on 48 x 32, identity pose, the centred camera, small_scene's upstream gradients, with the
+    rows of HOSTILE_ROWS overwritten; rows[name] is the row's index.  Every input is finite.  What each name claims is
+    asserted against the oracle in tests/test_hostile_rows.py::test_hostile_scene_conditions.  Computed once; nobody writes
+    to it."""
+    if "scene" in _HOSTILE:
+        return _HOSTILE["scene"]
+    sc = small_scene(P=HOSTILE_P, W=HOSTILE_W, H=HOSTILE_H, w2c=None, seed=11, scale_lo=0.01, scale_hi=0.12)
+    g = sc["gaussians"]
+    rows = {n: 2 + 5 * k for k, n in enumerate(HOSTILE_ROWS)}
+    f = _focal(sc)
+    iso = lambda sigma_px, z: np.full(3, sigma_px * z / f, np.float32)      # an isotropic scale of sigma_px pixels on the axis
+
+    def put(name, px, py, z, scales=None, opacity=None):
+        i = rows[name]
+        g["means3D"][i] = _mean_at(sc, px, py, z)
+        if scales is not None:
+            g["scales"][i] = np.asarray(scales, np.float32)
+        if opacity is not None:
+            g["opacities"][i] = opacity
+        return i
+
+    # scales
+    put("zero3", 8, 6, 2.0, (0, 0, 0), 0.7)
+    put("zero1", 20, 25, 2.5, (0.06, 0.0, 0.09), 0.6)
+    put("needle", 34, 8, 2.0, (0.3, 3e-5, 3e-5), 0.5)
+    put("pancake", 12, 20, 3.0, (0.15, 0.15, 5e-7), 0.5)
+    giant_row(sc, rows["giant"], 30, 20)
+    # rotations
+    put("q_small", 40, 25, 2.75, None, 0.5)
+    g["rotations"][rows["q_small"]] *= np.float32(0.1)
+    put("q_large", 6, 14, 3.5, (0.002, 0.003, 0.004), 0.5)
+    g["rotations"][rows["q_large"]] *= np.float32(10.0)
+    put("q_zero", 28, 4, 2.25, None, 0.5)
+    g["rotations"][rows["q_zero"]] = 0.0
+    i = put("q_negw", 18, 12, 3.75, None, 0.5)
+    if g["rotations"][i][0] > 0:
+        g["rotations"][i] = -g["rotations"][i]
+    # opacities: raw values, as a caller hands over who passes _opacity instead of the activated tensor
+    put("op_zero", 44, 12, 1.75, iso(2.0, 1.75), 0.0)
+    put("op_one", 3, 22, 4.0, iso(2.0, 4.0), 1.0)
+    put("op_above_one", 36, 28, 4.5, iso(2.5, 4.5), 1.5)
+    put("op_negative", 22, 3, 1.25, iso(2.0, 1.25), -0.2)
+    inf = np.float32(np.inf)
+    # means: the exact ones are filled in below
+    g["means3D"][rows["behind"]] = np.array([0.1, -0.2, -2.0], np.float32)
+    g["means3D"][rows["at_camera"]] = 0.0
+    put("off_one_tile_in", -10, 12, 2.0, iso(4.5, 2.0), 0.5)
+    put("off_miss", -8.5, 16, 2.0, iso(2.24, 2.0), 0.5)
+    put("beyond_clamp", 23.5 + 1.9 * 24, 16, 2.0, iso(9.0, 2.0), 0.5)
+    exact = dict(
+        # the only pixel that can blend them: sigma 0.17 px, alpha at a neighbouring centre 0.2 of the one at the mean; in
+        # front of everything else (z 0.5 against 1 and more)
+        thr_below=(14, 27, 0.5, iso(0.17, 0.5), np.nextafter(ALPHA_MIN, -inf)),
+        thr_above=(33, 3, 0.5, iso(0.17, 0.5), np.nextafter(ALPHA_MIN, inf)),
+        thr_exact=(24, 30, 0.5, iso(0.17, 0.5), ALPHA_MIN),       # alpha == 1/255 is blended: the test is `<`
+        pixel_centre=(30, 10, 1.5, iso(1.5, 1.5), 0.5),
+        tile_corner=(15.5, 15.5, 2.0, iso(1.5, 2.0), 0.5),
+        # radius 5 (3 sqrt(1.38^2 + 0.3 + sqrt(0.1)) = 4.8): (21 - 5) / 16 = 1, (12 + 5 + 15) / 16 = 2, and a rectangle that
+        # ends on pixel 16 in x and y, the first of the next tile: (11 + 5 + 15) / 16 = 1.94
+        rect_lo_exact=(21, 9, 2.0, iso(1.38, 2.0), 0.5),
+        rect_hi_exact=(12, 22, 2.0, iso(1.38, 2.0), 0.5),
+        rect_hi_touch=(12, 12, 2.0, iso(0.86, 2.0), 0.5),
+        # clones: bit-identical rows
+        clone_a0=(38, 22, 3.25, None, 0.4),
+        pair_front=(26, 14, 2.2, iso(1.2, 2.2), 0.5),
+    )
+    means = exact_means(oracle, sc, [v[:3] for v in exact.values()])
+    for (name, v), m in zip(exact.items(), means):
+        put(name, v[0], v[1], v[2], v[3], v[4])
+        g["means3D"][rows[name]] = m
+    for name in ("clone_a1", "clone_a2"):
+        for k in g:
+            g[k][rows[name]] = g[k][rows["clone_a0"]]
+    for k in g:
+        g[k][rows["pair_back"]] = g[k][rows["pair_front"]]
+    # ... and between the pair, by id, at the same depth: an opaque row.  Equal keys keep their id order, so the first of the
+    # pair is blended in front of it and the second behind it (T 0.01 .. 1 of what the first saw)
+    i = rows["pair_opaque"]
+    g["means3D"][i] = g["means3D"][rows["pair_front"]]
+    g["scales"][i] = iso(2.0, 2.2)
+    g["opacities"][i] = 1.0
+    assert all(np.isfinite(v).all() for v in g.values())
+    _HOSTILE["scene"] = (sc, rows)
+    return _HOSTILE["scene"]
+
+
+def hostile_inputs(oracle, variant):
+    """The argument patterns of the hostile scene: None (scales and rotations, SH colours), "cov3D_precomp" (the hostile
+    scales and rotations as 3-D covariances, in float32 by the oracle's own formula: the zero-scale row's is singular, a culled
+    row's all zeros) or "colors_precomp" (values below 0 and above 1)."""
+    if variant is None:
+        return None
+    sc, _ = hostile_scene(oracle)
+    if variant == "cov3D_precomp":
+        return dict(scales=None, rotations=None, cov3D_precomp=run_oracle(oracle, sc, backward=False)[0].geom["cov3D"].copy())
+    assert variant == "colors_precomp"
+    return dict(shs=None, colors_precomp=np.random.default_rng(5).uniform(-1.0, 2.0, (HOSTILE_P, 3)).astype(np.float32))
+
+
+def hostile_reference(oracle, variant=None):
+    """hostile_scene under hostile_inputs(variant), with the oracle's forward and the float64 gradients under every upstream
+    plane together: (scene, rows, f, ref, inputs).  Computed once per variant."""
+    sc, rows = hostile_scene(oracle)
+    inputs = hostile_inputs(oracle, variant)
+    if ("f", variant) not in _HOSTILE:
+        _HOSTILE[("f", variant)] = run_oracle(oracle, sc, backward=False, inputs=inputs)[0]
+    f = _HOSTILE[("f", variant)]
+    return sc, rows, f, float64_case_grads(("hostile", variant), sc, f, ("all",), inputs=inputs)["all"], inputs
+
+
+def frame_scene(W, H):
+    """The scene of the extreme frame shapes: 200 Gaussians under small_scene's tilted pose, row 0 replaced by the giant."""
+    sc = small_scene(P=200, W=W, H=H, scale_lo=0.02, scale_hi=0.2)
+    giant_row(sc, 0, (W - 1) / 2.0, (H - 1) / 2.0)
+    return sc
+
+
+ROW_TENSORS = ("means3D", "means2D", "opacities", "scales", "rotations", "shs", "shs_p")
+ROW_FLOOR = 1e-6
+
+
+def row_errors(ref, got, rows):
+    """The row-by-row measure of the hostile scene: {(name, tensor): (error, own, yardstick)} with, for every named row, its
+    max-norm error, its own max-norm in `ref`, and the yardstick max(own, ROW_FLOOR * the whole tensor's max-norm); under the
+    name "ordinary" all other rows as one block.  ref, got: gradients under run_gpu's names (means2D: its first two columns).
+    The floor: a row may have no gradient of its own in a tensor -- thr_above is blended by the one pixel it is centred on,
+    where dL/dmean2D, dL/dscales and dL/drotations are proportional to the offset from the pixel, an exact zero in fp32 and
+    the rounding of the projection (1e-7 px) in float64 -- and a ratio of two roundings says nothing; 1e-6 of the tensor's
+    size is ten fp32 roundings of it, far below anything that a whole-tensor bound of 3e-4 sees."""
+    out = {}
+    for k in ROW_TENSORS + ("colors_precomp", "cov3D_precomp"):
+        if ref.get(k) is None or got.get(k) is None:
+            continue
+        r = np.asarray(ref[k], np.float64)
+        r = r.reshape(r.shape[0], -1)
+        q = np.asarray(got[k], np.float64).reshape(r.shape[0], -1)
+        if k == "means2D":
+            r, q = r[:, :2], q[:, :2]
+        floor = ROW_FLOOR * float(np.abs(r).max())
+        named = np.zeros(r.shape[0], bool)
+        for name, i in rows.items():
+            named[i] = True
+            own = float(np.abs(r[i]).max())
+            out[(name, k)] = (float(np.abs(q[i] - r[i]).max()), own, max(own, floor) if own else 0.0)
+        own = float(np.abs(r[~named]).max())
+        out[("ordinary", k)] = (float(np.abs(q[~named] - r[~named]).max()), own, own)
+    return out

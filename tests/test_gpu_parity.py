@@ -180,7 +180,12 @@ def needs_float64_depth_distortion(scene):
 @pytest.mark.parametrize("mode", [1, 0], ids=["tile_pull", "whole_frame"])
 @pytest.mark.parametrize("name", list(SCENES))
 def test_preprocess_and_binning_bit_exact(name, mode, oracle, gpu):
-    scene = Hh.small_scene(**SCENES[name])
+    check_preprocess_and_binning_bit_exact(Hh.small_scene(**SCENES[name]), mode, oracle, gpu)
+
+
+def check_preprocess_and_binning_bit_exact(scene, mode, oracle, gpu):
+    """test_preprocess_and_binning_bit_exact's measure on any scene (tests/test_gpu_hostile.py runs it on degenerate Gaussians
+    and on extreme frame shapes)."""
     f, _ = Hh.run_oracle(oracle, scene, backward=False)
     st = raw_forward(scene, gpu, mode=mode)
     og = f.geom

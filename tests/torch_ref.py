@@ -140,6 +140,15 @@ def render(params, fwd, settings, dd_only=False):
 
     p = params["means3D"]
     P = p.shape[0]
+    culled = torch.tensor(np.asarray(fwd.radii).reshape(-1) <= 0)
+    if bool(culled.any()):
+        # A Gaussian the oracle culled stands in no list: it contributes nothing, and its gradients are exact zeros.  Its
+        # own position need not be one at which the formulas below are defined (the camera centre: a direction of length
+        # zero, t.x / t.z = 0 / 0, 1 / dist^2), and 0 * NaN in the backward is NaN: the formulas are evaluated at a point
+        # on the optical axis between the planes instead.  Every other row keeps its values and its graph.
+        mid = torch.tensor([0.0, 0.0, 0.5 * (near_n + far_n)], dtype=dt)
+        safe = torch.linalg.solve(V[:3, :3].T, mid - V[3, :3])
+        p = torch.where(culled[:, None], safe[None, :], p)
     ones = torch.ones(P, 1, dtype=dt)
     ph = torch.cat([p, ones], 1)
     p_view = (ph @ V)[:, :3]           # stored-transposed: row-vector times matrix
