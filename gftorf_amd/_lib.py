@@ -199,6 +199,12 @@ TRACKS_PARTS = ("index", "xy", "motion", "step_ok")             # GFT_TRACKS_*: 
 # include/gftorf_ply.h (the rows of the model's PLY files; no struct, so the ABI version is unchanged)
 PLY_EXPORTS = ["gft_ply_pack", "gft_ply_unpack"]
 PLY_ROWS, PLY_MAX_SOURCES, PLY_MAX_COLUMNS = 64, 16, 240        # GFT_PLY_ROWS, GFT_PLY_MAX_SOURCES, GFT_PLY_MAX_COLUMNS
+# include/gftorf_pcd.h (the input point cloud; no struct, so the ABI version is unchanged)
+PCD_EXPORTS = ["gft_pcd_unproject", "gft_pcd_row_bytes", "gft_pcd_pack", "gft_pcd_unpack", "gft_pcd_create"]
+PCD_ROWS, PCD_MAX_ROW_BYTES, PCD_STATUS_WORDS = 256, 128, 2     # GFT_PCD_ROWS, GFT_PCD_MAX_ROW_BYTES, GFT_PCD_STATUS_WORDS
+PCD_MODES = ("torf_init", "ftorf_init", "proxy")                # GFT_PCD_TORF_INIT, GFT_PCD_FTORF_INIT, GFT_PCD_PROXY
+# GFT_PCD_FIELDS: the entries of gft_pcd_unpack's offset table in order
+PCD_FIELDS = ("x", "y", "z", "nx", "ny", "nz", "red", "green", "blue", "phase", "amplitude", "seg_red", "seg_green", "seg_blue")
 
 
 def load():
@@ -401,6 +407,26 @@ def load():
     # stream, rows, row0, K_file, chunk, count, dests, widths, table
     lib.gft_ply_unpack.restype = C.c_int
     lib.gft_ply_unpack.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, _ptrs, _ints, _ints]
+    # stream, mode, H, W, stride, tof, rendered, rendered_f64, view, width_m, height_m, znear, depth_range_dev, depth_range,
+    # phase_offset_dev, phase_offset, xyz, dist, amp, sh_color, color, sh_amp, amplitude, status
+    lib.gft_pcd_unproject.restype = C.c_int
+    lib.gft_pcd_unproject.argtypes = ([C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                       C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_float, C.c_void_p,
+                                       C.c_float] + [C.c_void_p] * 8)
+    lib.gft_pcd_row_bytes.restype = C.c_int32
+    lib.gft_pcd_row_bytes.argtypes = [C.c_int32, C.c_int32]
+    # stream, P, xyz, colors, colors_f64, phases, amplitudes, seg, seg_f64, body, colors_back, seg_back, status
+    lib.gft_pcd_pack.restype = C.c_int
+    lib.gft_pcd_pack.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    # stream, rows, row0, row_bytes, chunk, offsets, xyz, normals, colors, phases, amplitudes, seg
+    lib.gft_pcd_unpack.restype = C.c_int
+    lib.gft_pcd_unpack.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, _ints] + [C.c_void_p] * 6
+    # stream, P, n, xyz, colors, colors_f64, phases, amplitudes, seg, seg_f64, log_scale, opacity, inv_c0, scaling_cols, then the
+    # twelve outputs
+    lib.gft_pcd_create.restype = C.c_int
+    lib.gft_pcd_create.argtypes = ([C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_int32] + [C.c_void_p] * 12)
     lib.gft_densify_stats.restype = C.c_int
     lib.gft_densify_stats.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8
     lib.gft_rows_rank_scratch_bytes.restype = C.c_size_t

@@ -14,6 +14,7 @@
 #include "gft_internal.h"
 #include "gft_reduce.h"
 #include "gft_tof_depth.h"
+#include "gft_byte_runs.h"
 #include "gft_present_magma.h"
 #include "gft_present_seismic.h"
 #include "gftorf_present.h"
@@ -125,24 +126,8 @@ __global__ __launch_bounds__(PRS_THREADS) void k_present_minmax(PresentArgs p)
     }
 }
 
-// A run of `nbytes` staged bytes to dst.  The bytes lie in `lds` from byte (dst & 3) on, so a dword of the destination is a
-// dword of the staging: whole dwords leave as such, the first and last dword of the run byte by byte where the run does
-// not cover them (a neighbouring run, or the next image's padding, owns the rest).
-__device__ __forceinline__ void put_run(uint8_t* dst, int nbytes, const uint32_t* lds)
-{
-    const int mis = (int)((uintptr_t)dst & 3u), total = mis + nbytes;
-    uint8_t* base = dst - mis;
-    const uint8_t* lb = reinterpret_cast<const uint8_t*>(lds);
-    for (int w = threadIdx.x; w * 4 < total; w += PRS_THREADS) {
-        const int first = w * 4;
-        if (first >= mis && first + 4 <= total) {
-            reinterpret_cast<uint32_t*>(base)[w] = lds[w];
-        } else {
-            for (int b = first; b < first + 4; b++)
-                if (b >= mis && b < total) base[b] = lb[b];
-        }
-    }
-}
+// gft_put_run (gft_byte_runs.h) by this file's workgroup
+__device__ __forceinline__ void put_run(uint8_t* dst, int nbytes, const uint32_t* lds) { gft_put_run<PRS_THREADS>(dst, nbytes, lds); }
 
 __global__ __launch_bounds__(PRS_THREADS) void k_present_view(PresentArgs p)
 {

@@ -11,7 +11,8 @@ nothing but the model's float32 values, one row per Gaussian in the column order
     ``Scene.save``.
 ``read_gaussians(path, device, max_sh_degree)``  the header parsed, the body streamed through pinned memory and scattered
     by one launch per chunk into the 11 tensors of ``load_ply``; ``load_ply(pc, path)`` adopts them.
-``columns(pc_or_shapes, full)``, ``header(names, P)``, ``parse_header(data)``  the file's text side, pure Python.
+``columns(pc_or_shapes, full)``, ``header(names, P)``, ``parse_header(data)``  the file's text side, pure Python (shared with
+    ``gftorf_amd.pcd``, whose input clouds also hold uchar columns).
 
 The values are moved bit for bit.  There is no CPU path; the reader handles the files this layout covers (binary little
 endian, float properties) and refuses the rest by name.
@@ -69,15 +70,21 @@ def columns(pc_or_shapes, full=False):
     return names
 
 
+PROPERTY_BYTES = {"float": 4, "uchar": 1}      # the property types the kernels move, as plyfile names them (f4, u1)
+
+
 def header(names, P):
-    """The PLY header of P vertices with the float properties ``names``, as bytes"""
-    lines = ["ply", "format binary_little_endian 1.0", "element vertex %d" % P] + ["property float %s" % n for n in names] + ["end_header"]
+    """The PLY header of P vertices with the properties ``names``, as bytes: a name alone is a float property, a
+    ``(name, "uchar")`` pair one of that type (``gftorf_amd.pcd``'s colour columns)"""
+    props = [("float", n) if isinstance(n, str) else (n[1], n[0]) for n in names]
+    lines = ["ply", "format binary_little_endian 1.0", "element vertex %d" % P] + ["property %s %s" % p for p in props] + ["end_header"]
     return ("\n".join(lines) + "\n").encode("ascii")
 
 
-def parse_header(data):
+def parse_header(data, uchar=False):
     """``(P, names, offset)`` of a file that begins with the bytes ``data``: the vertex count, the vertex element's property names
-    in file order and the offset of the body.  NotImplementedError for what the reader does not handle."""
+    in file order and the offset of the body.  NotImplementedError for what the reader does not handle.  With ``uchar`` the
+    vertex element may also hold uchar properties and the names come as ``(name, type)`` pairs (``gftorf_amd.pcd.fetch``)."""
     end = data.find(b"end_header\n")
     lines = data[:end].decode("ascii", "replace").split("\n") if end >= 0 else []
     if not lines or lines[0].strip() != "ply":
@@ -97,12 +104,13 @@ def parse_header(data):
                     raise NotImplementedError("%s: the file's first element is `%s`%s" % (_TAG, words[1], _REFUSAL))
                 P = int(words[2])
         elif words[0] == "property" and element == 1:
-            if words[1] not in ("float", "float32") or len(words) != 3:
+            kind = {"float32": "float", "uint8": "uchar"}.get(words[1], words[1])
+            if kind not in (("float", "uchar") if uchar else ("float",)) or len(words) != 3:
                 raise NotImplementedError("%s: the vertex element has the property `%s`%s" % (_TAG, " ".join(words[1:]), _REFUSAL))
-            names.append(words[2])
+            names.append((words[2], kind) if uchar else words[2])
     if P is None or P < 0:
         raise ValueError("%s: the header names no vertex element" % _TAG)
-    if len(set(names)) != len(names):
+    if len(set(n[0] if uchar else n for n in names)) != len(names):
         raise ValueError("%s: the vertex element names a property twice" % _TAG)
     return P, names, end + len(b"end_header\n")
 
