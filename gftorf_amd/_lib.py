@@ -193,6 +193,9 @@ PRESENT_IMAGES = (("color", 3, "uint8", lambda H, W: (H, W, 3)), ("real", 3, "ui
 PRESENT_HAS_COLOR, PRESENT_HAS_PHASOR, PRESENT_HAS_QUAD, PRESENT_HAS_DEPTH, PRESENT_HAS_ACC, PRESENT_HAS_DD = 1, 2, 4, 8, 16, 32
 PRESENT_ALIGN, PRESENT_PARTIAL_WORDS, PRESENT_RANGE_WORDS, PRESENT_MAGMA_ROWS = 16, 2, 6, 257      # GFT_PRESENT_*
 PRESENT_SEISMIC_ROWS = 257                                                                         # GFT_PRESENT_SEISMIC_ROWS
+# include/gftorf_flowviz.h (the optical-flow debug images; no struct, so the ABI version is unchanged)
+FLOWVIZ_EXPORTS = ["gft_flowviz_blocks", "gft_flowviz_wheel", "gft_flowviz_images"]
+FLOWVIZ_WHEEL_ROWS, FLOWVIZ_IMAGES, FLOWVIZ_RUN = 55, 3, 4      # GFT_FLOWVIZ_WHEEL_ROWS, GFT_FLOWVIZ_IMAGES, GFT_FLOWVIZ_RUN
 # include/gftorf_tracks.h (the F-ToRF motion tracks; no struct, so the ABI version is unchanged)
 TRACKS_EXPORTS = ["gft_tracks_integrate", "gft_tracks_table_bytes", "gft_tracks_table"]
 TRACKS_PARTS = ("index", "xy", "motion", "step_ok")             # GFT_TRACKS_*: the parts of a table in the order they lie in it
@@ -391,6 +394,13 @@ def load():
     lib.gft_present_quad.restype = C.c_int
     lib.gft_present_quad.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.c_int32, C.c_int32,
                                      C.c_void_p]
+    lib.gft_flowviz_blocks.restype = C.c_int64
+    lib.gft_flowviz_blocks.argtypes = [C.c_int64]
+    lib.gft_flowviz_wheel.restype = C.POINTER(C.c_uint8)
+    lib.gft_flowviz_wheel.argtypes = []
+    # stream, H, W, flow, stride, gt, stride, partials, out
+    lib.gft_flowviz_images.restype = C.c_int
+    lib.gft_flowviz_images.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     # stream, P, n, T, U, initial_pos, flow, flow_index, K, world_view, mask, rank, H, W, xy, pos_last, motion, mean_z, step_ok
     lib.gft_tracks_integrate.restype = C.c_int
     lib.gft_tracks_integrate.argtypes = ([C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 7 +

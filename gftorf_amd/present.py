@@ -14,10 +14,13 @@ blocking ``.cpu()`` calls, about 130 bytes per pixel -- and forms the images it 
 ``zplanes(depth_range)``  the colour map's planes of ``render.py:54``.
 ``quad_images(phasor, ...)``  the four quad images of the track program (``render_ftorf_viz_traj.py:237-244``): ``tof_to_image``,
     matplotlib's ``seismic`` map, in one launch.
+``flow_images(flow, gt_flow)``  the three optical-flow images of a direction in the ``pipe.debug`` block (``train.py:380-398``;
+    ``csrc/k_flowviz.hip``, ``include/gftorf_flowviz.h``): ``flow_to_image`` of (rendered, target), (target, target) and (target
+    - rendered, target) with the in-place edits the three calls share, in two launches; ``ViewSheets.submit_flow`` stages them.
 
-The uint8 images equal the reference's bit for bit wherever its float32 statements are IEEE operations; the one exception is
-``arctan2`` in ``depth_tof``, whose last bits may differ (see tests/test_present.py).  Nothing here has a gradient and there is
-no CPU path.
+The uint8 images equal the reference's bit for bit wherever its statements are IEEE operations; the one exception is
+``arctan2`` (in ``depth_tof`` and in the flow images' hue), whose last bits may differ (see tests/test_present.py and
+tests/test_present_flow.py).  Nothing here has a gradient and there is no CPU path.
 """
 import ctypes as C
 
@@ -221,6 +224,57 @@ def quad_images(phasor, permutation=(0, 1, 2, 3), has_gt=False, tonemap=False, o
     return out
 
 
+def flow_wheel():
+    """The Middlebury colour wheel of ``make_color_wheel`` (``scene/torf_utils.py:150-197``) as the kernel holds it: uint8
+    [55, 3]"""
+    ptr = _lib.load().gft_flowviz_wheel()
+    return np.ctypeslib.as_array(ptr, shape=(_lib.FLOWVIZ_WHEEL_ROWS, 3)).copy()
+
+
+def flow_blocks(pixels):
+    """workgroups of ``flow_images``' launches over an image of `pixels`; its partials hold one float more; 0 for no pixel"""
+    return int(_lib.load().gft_flowviz_blocks(int(pixels)))
+
+
+def flow_images(flow, gt_flow, out=None, _partials=None):
+    """The three optical-flow debug images of one direction, ``train.py:382-386``: ``flow_to_image`` (``scene/torf_utils.py:
+    242-305``) of (rendered, target), (target, target) and (target - rendered, target) as the reference's sequence of calls
+    leaves them -- ``flow_to_image`` zeroes the unknown (> 200) and NaN pixels of its arguments in place, so the later calls
+    see the earlier ones' edits -- in two launches.  Returns ``{"flow": ..., "gt": ..., "error": ...}``, uint8 [H, W, 3] views
+    into one device tensor [3, H, W, 3].
+
+    ``flow`` [>= 2, H, W]: the rendered 2-D flow, planes 0 and 1 read in place through their stride (``render_flow``'s 3-plane
+    output or a slice of it needs no copy).  ``gt_flow`` [2, H, W]: the target.  Both float32 on one HIP device; neither is
+    written.  ``out``: a contiguous uint8 device tensor [3, H, W, 3] to write into; else a new one.
+    The arithmetic is numpy >= 2's: the float32 ``maxrad * 1.1`` plus the float64 ``eps`` is a float64, and so is everything
+    behind the division by it (numpy 1.x stays in float32 and gives other bytes).  Only ``arctan2``'s last bits may differ
+    (tests/test_present_flow.py).  Nothing is read on the host; the call can be captured in a graph."""
+    fl, fl_stride = _args.planes(_TAG, flow, "flow", 2, 1 << 30, keep=2)
+    H, W = int(fl.shape[1]), int(fl.shape[2])
+    gt, gt_stride = _planes(gt_flow, "gt_flow", 2, 2, ((H, W), "flow"))
+    named = [(fl, "flow"), (gt, "gt_flow")]
+    if out is not None:
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (_lib.FLOWVIZ_IMAGES, H, W, 3)
+                or not out.is_contiguous()):
+            raise TypeError("gftorf_amd.present: out must be a contiguous torch.uint8 tensor [3, %d, %d, 3]" % (H, W))
+        named.append((out, "out"))
+    dev = _args.devices(_TAG, "display", named)
+    lib = _lib.load()
+    rows = flow_blocks(H * W) + 1
+    partials = _partials
+    if partials is None:
+        partials = torch.empty((rows,), device=dev, dtype=torch.float32)
+    elif (not isinstance(partials, torch.Tensor) or partials.dtype != torch.float32 or partials.device != dev or partials.numel() < rows
+          or not partials.is_contiguous()):
+        raise RuntimeError("gftorf_amd.present: the partials of a %d x %d flow are %d contiguous float32 on %s" % (H, W, rows, dev))
+    if out is None:
+        out = torch.empty((_lib.FLOWVIZ_IMAGES, H, W, 3), device=dev, dtype=torch.uint8)
+    with _lib.on_device(dev):
+        _lib.check(lib.gft_flowviz_images(_lib.raw_stream(dev), H, W, fl.data_ptr(), fl_stride, gt.data_ptr(), gt_stride,
+                                          partials.data_ptr(), out.data_ptr()))
+    return {"flow": out[0], "gt": out[1], "error": out[2]}
+
+
 class PhasorRanges:
     """The normalisation ranges of ``real``, ``imag`` and ``amp``: ``save_input``'s ``np.min`` / ``np.max`` over the whole
     ground-truth sequence (``render.py:46-47, 61``) as a float32 device tensor [6] = (lo, hi) three times::
@@ -319,6 +373,35 @@ class ViewSheets:
             raw = host[o:o + t.numel() * t.element_size()]
             arrays[name] = (raw.view(np.float32) if t.dtype == torch.float32 else raw).reshape(tuple(t.shape))
         slot.update(state="flight", tag=tag, arrays=arrays)
+        self._order.append(slot)
+
+    def submit_flow(self, tag, flow, gt_flow):
+        """``flow_images(flow, gt_flow)`` into a free slot, the three images' copy to pinned memory and an event, all on the
+        current stream; ``ready`` yields the tag with ``{"flow", "gt", "error"}`` as uint8 [H, W, 3] arrays"""
+        slot = next((s for s in self._slots if s["state"] == "free"), None)
+        if slot is None:
+            raise RuntimeError("gftorf_amd.present: all %d slots of this ViewSheets are in flight; take the finished views with ready()"
+                               % len(self._slots))
+        if not isinstance(flow, torch.Tensor) or flow.dim() != 3:
+            raise ValueError("gftorf_amd.present: nothing to show: give flow as a [C, H, W] tensor")
+        dev = _args.devices(_TAG, "display", [(flow, "flow")])
+        H, W = int(flow.shape[1]), int(flow.shape[2])
+        need = _lib.FLOWVIZ_IMAGES * H * W * 3
+        if slot["device"] is None or slot["device"].numel() < need or slot["device"].device != dev:
+            slot["device"] = torch.empty((need,), device=dev, dtype=torch.uint8)
+            slot["host"] = torch.empty((need,), dtype=torch.uint8, pin_memory=True)
+            # submit() takes a slot whose buffer is large enough with its partials: rows for as many pixels as there are bytes
+            slot["partials"] = torch.empty((max(1, blocks(need)), _lib.PRESENT_PARTIAL_WORDS), device=dev, dtype=torch.float32)
+            slot["event"] = torch.cuda.Event()
+        rows = flow_blocks(H * W) + 1
+        scratch = slot.get("flow_partials")
+        if scratch is None or scratch.numel() < rows or scratch.device != dev:
+            scratch = slot["flow_partials"] = torch.empty((rows,), device=dev, dtype=torch.float32)
+        flow_images(flow, gt_flow, out=slot["device"][:need].view(_lib.FLOWVIZ_IMAGES, H, W, 3), _partials=scratch)
+        slot["host"][:need].copy_(slot["device"][:need], non_blocking=True)
+        slot["event"].record()
+        host = slot["host"].numpy()[:need].reshape(_lib.FLOWVIZ_IMAGES, H, W, 3)
+        slot.update(state="flight", tag=tag, arrays={"flow": host[0], "gt": host[1], "error": host[2]})
         self._order.append(slot)
 
     def ready(self, wait=False):
