@@ -17,25 +17,34 @@ no torch GEMM in it.  Inputs are not differentiated: the reference passes detach
 (``scene/gaussian_model.py:172``).
 """
 import ctypes as C
+import math
+import os
 
 import torch
 from torch import nn
 
 from . import _lib
+from ._args import ptr
 
 _D, _W, _SH_DEGREE = 8, 256, 3
-_PAD = 192                       # DF_PAD: point counts are padded to multiples of 192 inside the saved / scratch buffers
 
-# The backward runs over the points whose upstream gradient row (d_xyz, d_sh) is non-zero only: in a training iteration
-# those are the Gaussians some pixel blended (6-14 % of the queried points on the metric scene); a row whose upstream
-# gradient is zero has dz = 0 in every layer and adds exactly nothing to any weight gradient.  The saved activations of
-# the rows that count are compacted (one rank computation, one blocking read of the count -- as the reference's
-# `t[mask]` has), then the same kernels run on the compact set: gradients equal the dense backward's up to summation
-# order.  Off: `gftorf_amd.deform.sparse_backward = False`.
+# Three switches decide which of six routes a call's backward takes; `_choose_route` holds the table.
+# `sparse_backward`: the backward runs over the rows whose upstream gradient (d_xyz, d_sh) is non-zero only -- in a training
+# iteration the Gaussians some pixel blended, 6-14 % of the queried points; a row without one has dz = 0 in every layer and
+# adds exactly nothing to any weight gradient: the dense backward's gradients up to summation order.  False: always dense.
 sparse_backward = True
 _SPARSE_MIN_POINTS = 8192        # below this the dense backward is launch-bound anyway
 _SPARSE_MAX_FRACTION = 0.6       # above this the compaction costs more than it saves
 last_backward_stats = {"points": 0, "points_processed": 0, "recomputed": False}
+last_backward_route = None       # the route the last backward ran ("dense" for a "compact" that met no upstream gradient)
+
+
+def _set_stats(route, points, processed, **rows_on_device):
+    """The one writer of ``last_backward_stats`` and ``last_backward_route``."""
+    global last_backward_route
+    last_backward_route = route
+    last_backward_stats.clear()
+    last_backward_stats.update(points=points, points_processed=processed, recomputed=route in ("recompute", "rows"), **rows_on_device)
 
 
 def backward_stats():
@@ -47,39 +56,57 @@ def backward_stats():
         st["points_processed"] = int(rows.item()) if rows is not None else 0
     return st
 
-# Activations on demand.  A saving forward writes 8.4 KB per point for the backward (2.5 GB at 300 k points, a sixth of the
-# forward's time -- and of its energy: that kernel runs at the board's power limit).  When the last backward used few of
-# the rows (the usual training iteration: only Gaussians that a pixel blended carry a gradient), the next forward keeps
-# NOTHING; its backward gathers the inputs of the rows that count, runs the saving forward on those rows alone (a point's
-# activations do not depend on the batch it is in: bit-identical) and goes on as before -- no 2.5 GB, no compaction of them.
-# (Bit-identical while the call stays inside the fp16 planes' range, which is every network the reference trains: the
-# library decides per CALL whether the fp16 walk's results stand or the fp32-range walk overwrites them (k_deform.hip,
-# range guard).  A forward that fell back because of a row WITHOUT a gradient is recomputed on the rows with one by the fp16
-# walk: the two walks agree to ~1e-7, a ReLU input within that of zero may change side.)
-# A backward that finds many rows with a gradient after all recomputes all of them (one extra forward, once) and the next
-# forward saves again.  `GFT_DEFORM_LAZY_SAVE=0` in the environment or `gftorf_amd.deform.lazy_save = False`: always save.
-import os as _os
-lazy_save = _os.environ.get("GFT_DEFORM_LAZY_SAVE", "1") != "0"
+# `lazy_save` (`GFT_DEFORM_LAZY_SAVE=0`: off, every forward saves): activations on demand.  A saving forward writes 8.4 KB
+# per point (2.5 GB at 300 k points, a sixth of its time); once backwards are known to use few rows the forward keeps nothing
+# and the backward runs the saving forward over the rows that count alone -- bit-identical, a point's activations do not
+# depend on its batch (inside the fp16 planes' range: k_deform.hip's range guard decides per CALL; the walks agree to ~1e-7).
+lazy_save = os.environ.get("GFT_DEFORM_LAZY_SAVE", "1") != "0"
 _LAZY_MAX_FRACTION = 0.25        # recomputing that share of the rows costs less than saving all of them
 
-# Rows counted on the device.  The row selection above reads a count back (one blocking read, as the reference's `t[mask]`
-# has), which a stream that is being captured into a HIP graph cannot do.  ``gft_deform_backward_rows`` keeps the count on the
-# device: the forward keeps nothing, the backward marks, ranks and counts the rows with a gradient by kernels, gathers their
-# inputs, recomputes their activations and runs over them -- launches of the capacity whose surplus workgroups return at
-# once.  A captured iteration replayed on other gradients adapts to THEIR rows (the C3 loop from a graph: the backward
-# follows the share of Gaussians a pixel blends, 58 % -> 23 % over the run, instead of staying dense).  Gradients are those of
-# the blocking selection bit for bit (tests/test_deform.py).
-#   "auto" (default): under capture always; eagerly whenever the work buffer (sized for ALL queried points: 17 KB each) stays
-#       below ``_DEVICE_ROWS_MAX_BYTES`` -- the share of rows with a gradient is then learnt WITHOUT a blocking read: every
-#       backward leaves its count in pinned memory and the next forward looks at whatever has arrived.  While that share is
-#       unknown or above ``_DEVICE_ROWS_MAX_FRACTION`` the forward saves its activations and the backward runs dense (and
-#       counts); below it the forward keeps nothing and the backward recomputes the rows that count.  No host read anywhere.
-#   "capture": under capture only (eagerly the blocking selection above);  True: always;  False: never (a captured call
-#       then saves its activations and runs dense).
-# ``GFT_DEFORM_DEVICE_ROWS`` = auto | capture | 1 | 0.
-device_row_count = {"0": False, "1": True, "capture": "capture", "auto": "auto"}.get(_os.environ.get("GFT_DEFORM_DEVICE_ROWS", ""), "auto")
+# `device_row_count` (`GFT_DEFORM_DEVICE_ROWS` = auto | capture | 1 | 0): where the rows with a gradient are counted.  The
+# blocking selection reads the count on the host, which a stream being captured into a graph cannot do;
+# ``gft_deform_backward_rows`` keeps it on the device (launches of the capacity, surplus workgroups return at once): a captured
+# iteration replayed on other gradients follows THEIR rows, with the blocking selection's gradients bit for bit.
+#   "auto" (default): under capture always; eagerly while the work buffer (17 KB per queried point) stays below
+#       ``_DEVICE_ROWS_MAX_BYTES``, the share of rows learnt from the counts the backwards post to pinned memory: no host read.
+#   "capture": under capture only, eagerly the blocking selection;  True: always;  False: never (a captured call runs dense).
+device_row_count = {"0": False, "1": True, "capture": "capture", "auto": "auto"}.get(os.environ.get("GFT_DEFORM_DEVICE_ROWS", ""), "auto")
 _DEVICE_ROWS_MAX_FRACTION = 0.6
 _DEVICE_ROWS_MAX_BYTES = 32 << 30
+
+
+def _choose_route(need_bw, n, capturing, state, rows_work_bytes):
+    """The name of the route a call of n points takes, chosen once in the forward from the module switches, the capture state,
+    the network's ``_save_state`` and the size of the rows work buffer (a number, or a callable asked only where it decides):
+
+    | route       | forward keeps | backward (k: the rows with an upstream gradient, F: _SPARSE_MAX_FRACTION)                    |
+    |-------------|---------------|----------------------------------------------------------------------------------------------|
+    | "none"      | nothing       | raises: the forward ran without gradients                                                    |
+    | "dense"     | activations   | dense over all n rows                                                                        |
+    | "compact"   | activations   | blocking count; ``gft_deform_compact`` + dense over k rows if k <= F n, else dense over n    |
+    | "recompute" | x, t only     | blocking count; saving forward over the k rows (over all n if k > F n), then dense over them |
+    | "count"     | activations   | dense over n; the rows only counted on the device, the count posted to pinned memory         |
+    | "rows"      | x, t only     | ``gft_deform_backward_rows``: the count stays on the device, posted when not capturing       |
+
+    "dense", "compact" and "recompute" leave rows processed / n in ``state["fraction"]`` (eagerly, n >= _SPARSE_MIN_POINTS); the
+    posted counts of "count" and "rows" reach it through `_peek_fraction`.  k = 0 fills the gradients with zeros."""
+    if not need_bw:
+        return "none"
+    if not (sparse_backward and n >= _SPARSE_MIN_POINTS):
+        return "dense"
+    if device_row_count is True or (capturing and device_row_count in ("capture", "auto")):
+        return "rows"
+    if capturing:
+        return "dense"                                   # nothing may be read back: the activations saved, every row
+    if (device_row_count == "auto" and state is not None
+            and (rows_work_bytes() if callable(rows_work_bytes) else rows_work_bytes) <= _DEVICE_ROWS_MAX_BYTES):
+        _peek_fraction(state)
+        frac = state.get("fraction")
+        return "rows" if (lazy_save and frac is not None and frac <= _DEVICE_ROWS_MAX_FRACTION) else "count"
+    frac = state.get("fraction") if state is not None else None
+    if lazy_save and frac is not None and frac <= _LAZY_MAX_FRACTION:
+        return "recompute"
+    return "compact"
 
 
 def _peek_fraction(state):
@@ -123,11 +150,17 @@ def _fill(struct, tensors):
     return struct
 
 
-def _prod(shape):
-    k = 1
-    for d in shape:
-        k *= int(d)
-    return k
+def _flat_grads(shapes, dev):
+    """Zeroed gradients of `shapes` as views of ONE flat buffer, in parameter order: the data-parallel bucket
+    (flat_grad_bucket) is then this memory itself and the all-reduce needs no gather / scatter copies (each view starts on
+    a 16-byte boundary, as a tensor of its own would; the few padding floats stay zero)."""
+    sizes = [math.prod(s) for s in shapes]
+    flat = torch.zeros((sum((k + 3) // 4 * 4 for k in sizes),), device=dev, dtype=torch.float32)
+    grads, o = [], 0
+    for shp, k in zip(shapes, sizes):
+        grads.append(flat[o:o + k].view(shp))
+        o += (k + 3) // 4 * 4
+    return grads
 
 
 class _DeformFn(torch.autograd.Function):
@@ -155,44 +188,21 @@ class _DeformFn(torch.autograd.Function):
                 raise RuntimeError("DeformNetwork parameters must be float32 on %s" % (dev,))
             ps.append(p.detach().contiguous())
         need_bw = any(ctx.needs_input_grad[5:])      # all False under torch.no_grad()
-        # (while the stream is being captured into a graph nothing may be read from the device: the blocking row selection
-        # reads a row count, so a captured call either counts its rows on the device -- below -- or, with
-        # device_row_count = False, saves its activations and runs the dense backward: the same gradients up to summation order)
-        capturing = torch.cuda.is_current_stream_capturing()
-        sparse_ok = bool(need_bw and sparse_backward and n >= _SPARSE_MIN_POINTS)
-        # rows counted on the device (see device_row_count): "rows" = the forward keeps nothing, the backward recomputes the rows
-        # that count; "count" = the forward saves, the backward runs dense and only counts (the share is unknown or large)
-        dev_mode = None
-        if sparse_ok and device_row_count is not False:
-            if device_row_count is True or (capturing and device_row_count in ("capture", "auto")):
-                dev_mode = "rows"
-            elif device_row_count == "auto" and state is not None and lib.gft_deform_rows_work_bytes(n) <= _DEVICE_ROWS_MAX_BYTES:
-                _peek_fraction(state)
-                frac = state.get("fraction")
-                dev_mode = "rows" if (frac is not None and frac <= _DEVICE_ROWS_MAX_FRACTION and lazy_save) else "count"
-        dev_rows = dev_mode == "rows"
-        lazy = bool(sparse_ok and lazy_save and state is not None and dev_mode is None
-                    and state.get("fraction") is not None and state["fraction"] <= _LAZY_MAX_FRACTION and not capturing) or dev_rows
+        route = _choose_route(need_bw, n, torch.cuda.is_current_stream_capturing(), state, lambda: lib.gft_deform_rows_work_bytes(n))
+        keeps_inputs = route in ("recompute", "rows")
         f32 = dict(device=dev, dtype=torch.float32)
         packed = torch.empty((lib.gft_deform_packed_bytes() // 4,), **f32)
-        d_xyz = torch.empty((n, 3), **f32)
-        d_sh = torch.empty((n, 16, 3), **f32)
-        saved = torch.empty((lib.gft_deform_saved_bytes(n) // 4,), **f32) if (need_bw and n > 0 and not lazy) else None
+        d_xyz, d_sh = torch.empty((n, 3), **f32), torch.empty((n, 16, 3), **f32)
+        saved = torch.empty((lib.gft_deform_saved_bytes(n) // 4,), **f32) if (need_bw and n > 0 and not keeps_inputs) else None
         stream = _lib.raw_stream(dev)
         with _lib.on_device(dev):
             _lib.check(lib.gft_deform_pack(stream, xm, tm, C.byref(_fill(_lib.DeformParams(), ps)), packed.data_ptr()))
             _lib.check(lib.gft_deform_forward(stream, xm, tm, n, x_c.data_ptr() if n else None, t_c.data_ptr() if n else None,
-                                              t_stride, packed.data_ptr(), saved.data_ptr() if saved is not None else None,
+                                              t_stride, packed.data_ptr(), ptr(saved),
                                               d_xyz.data_ptr() if n else None, d_sh.data_ptr() if n else None))
-        ctx.n = n
-        ctx.arch = (xm, tm)
-        ctx.shapes = [tuple(p.shape) for p in params]
-        ctx.state = state
-        ctx.lazy = lazy
-        ctx.dev_rows = dev_rows
-        ctx.dev_count = dev_mode == "count"
-        if lazy:
-            ctx.t_stride = t_stride
+        ctx.n, ctx.arch, ctx.t_stride = n, (xm, tm), t_stride
+        ctx.shapes, ctx.state, ctx.route = [tuple(p.shape) for p in params], state, route
+        if keeps_inputs:
             ctx.save_for_backward(packed, x_c, t_c)
         else:
             ctx.save_for_backward(packed, saved if saved is not None else packed.new_empty(0))
@@ -202,108 +212,87 @@ class _DeformFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_dxyz, g_dsh):
         lib = _lib.load()
-        if ctx.lazy:
-            packed, x_c, t_c = ctx.saved_tensors
-            saved = None
-        else:
-            packed, saved = ctx.saved_tensors
-        dev = packed.device
-        n = ctx.n
-        if n > 0 and not ctx.lazy and saved.numel() == 0:
+        packed, *kept = ctx.saved_tensors              # kept: (saved activations,) or (x, t), by the route
+        n, route, dev = ctx.n, ctx.route, packed.device
+        if route == "none" and n > 0:
             raise RuntimeError("DeformNetwork: backward through a forward that ran without gradients")
-        f32 = dict(device=dev, dtype=torch.float32)
-        # the gradients are views of ONE flat buffer, in parameter order: the data-parallel bucket (flat_grad_bucket) is
-        # then this memory itself and the all-reduce needs no gather / scatter copies
-        # (each view starts on a 16-byte boundary, as a tensor of its own would; the few padding floats stay zero)
-        sizes = [_prod(s) for s in ctx.shapes]
-        flat = torch.zeros((sum((k + 3) // 4 * 4 for k in sizes),), **f32)
-        grads, o = [], 0
-        for shp, k in zip(ctx.shapes, sizes):
-            grads.append(flat[o:o + k].view(shp))
-            o += (k + 3) // 4 * 4
+        grads = _flat_grads(ctx.shapes, dev)
         gx = g_dxyz.float().contiguous() if g_dxyz is not None else None
         gs = g_dsh.float().contiguous() if g_dsh is not None else None
-        last_backward_stats.update(points=n, points_processed=n, recomputed=ctx.lazy)
-        last_backward_stats.pop("rows_on_device", None)       # (a count an earlier backward left on the device)
-        n_all = n
-        if ctx.dev_rows:
-            # rows counted on the device: one call, nothing read back (capturable)
-            work = torch.empty((lib.gft_deform_rows_work_bytes(n) // 4,), **f32)
-            rows = torch.empty((1,), device=dev, dtype=torch.int32)
-            ptr = lambda t_: t_.data_ptr() if t_ is not None else None
+        if route == "none" or (route == "compact" and gx is None and gs is None):
+            route = "dense"                             # (no point / no upstream gradient to select rows by)
+        if route == "rows":
+            _backward_rows(lib, ctx, packed, kept, gx, gs, grads)
+        else:
+            k, saved, gx, gs = _SELECT[route](lib, ctx, packed, kept, gx, gs)
+            if route != "count" and ctx.state is not None and n >= _SPARSE_MIN_POINTS and not torch.cuda.is_current_stream_capturing():
+                ctx.state["fraction"] = k / float(n)
+            _set_stats(route, n, k)
+            # the shared tail: the dense backward over the k rows of `saved`, `gx` and `gs`
+            scratch = torch.empty((lib.gft_deform_scratch_bytes(k) // 4,), device=dev, dtype=torch.float32)
             with _lib.on_device(dev):
-                _lib.check(lib.gft_deform_backward_rows(_lib.raw_stream(dev), ctx.arch[0], ctx.arch[1], n, packed.data_ptr(), x_c.data_ptr(),
-                                                        t_c.data_ptr(), ctx.t_stride, ptr(gx), ptr(gs), work.data_ptr(),
-                                                        C.byref(_fill(_lib.DeformParams(), grads)), rows.data_ptr()))
-            last_backward_stats.update(points_processed=None, rows_on_device=rows)
-            _post_count(ctx.state, rows, n_all)
-            return (None, None, None, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[5:]))
-        if ctx.dev_count and (gx is not None or gs is not None):
-            # dense backward over the saved activations; the rows with a gradient are only counted (three small launches, the
-            # count on its way to pinned memory): the next forward decides by it
-            rows = _count_rows_on_device(lib, n, gx, gs, dev)
-            _post_count(ctx.state, rows, n_all)
-            last_backward_stats.pop("rows_on_device", None)
-        if ctx.lazy:
-            n, saved, gx, gs = _recompute_rows(lib, ctx, n, packed, x_c, t_c, gx, gs)
-            last_backward_stats["points_processed"] = n
-        elif (sparse_backward and n >= _SPARSE_MIN_POINTS and (gx is not None or gs is not None) and not ctx.dev_count
-              and not torch.cuda.is_current_stream_capturing()):
-            n, saved, gx, gs = _compact_rows(lib, n, saved, gx, gs)
-            last_backward_stats["points_processed"] = n
-        if ctx.state is not None and n_all >= _SPARSE_MIN_POINTS and not ctx.dev_count and not torch.cuda.is_current_stream_capturing():
-            ctx.state["fraction"] = n / float(n_all)
-        scratch = torch.empty((lib.gft_deform_scratch_bytes(n) // 4,), **f32)
-        stream = _lib.raw_stream(dev)
-        with _lib.on_device(dev):
-            _lib.check(lib.gft_deform_backward(stream, ctx.arch[0], ctx.arch[1], n, packed.data_ptr(), saved.data_ptr() if n else None,
-                                               gx.data_ptr() if (gx is not None and n) else None,
-                                               gs.data_ptr() if (gs is not None and n) else None,
-                                               scratch.data_ptr() if n else None,
-                                               C.byref(_fill(_lib.DeformParams(), grads))))
+                _lib.check(lib.gft_deform_backward(_lib.raw_stream(dev), ctx.arch[0], ctx.arch[1], k, packed.data_ptr(),
+                                                   saved.data_ptr() if k else None, ptr(gx) if k else None, ptr(gs) if k else None,
+                                                   scratch.data_ptr() if k else None, C.byref(_fill(_lib.DeformParams(), grads))))
         return (None, None, None, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[5:]))
 
 
-def _count_rows_on_device(lib, n, gx, gs, dev):
-    """int32 [1] on the device: the number of rows whose upstream gradient holds a value != 0; nothing read back."""
-    mask = torch.empty((n,), device=dev, dtype=torch.uint8)
-    rank = torch.empty((n,), device=dev, dtype=torch.int32)
-    scratch = torch.empty((lib.gft_rows_rank_scratch_bytes(n),), device=dev, dtype=torch.uint8)
+def _backward_rows(lib, ctx, packed, kept, gx, gs, grads):
+    """ "rows": the rows counted on the device -- one call, nothing read back (capturable); finishes the backward itself."""
+    x_c, t_c = kept
+    n, dev = ctx.n, packed.device
+    work = torch.empty((lib.gft_deform_rows_work_bytes(n) // 4,), device=dev, dtype=torch.float32)
     rows = torch.empty((1,), device=dev, dtype=torch.int32)
-    ptr0 = lambda t: t.data_ptr() if t is not None else None
     with _lib.on_device(dev):
-        stream = _lib.raw_stream(dev)
-        _lib.check(lib.gft_rows_any_nonzero(stream, n, 3 if gx is not None else 0, ptr0(gx), 48 if gs is not None else 0, ptr0(gs),
-                                            mask.data_ptr()))
-        _lib.check(lib.gft_rows_rank_dev(stream, n, mask.data_ptr(), rank.data_ptr(), scratch.data_ptr(), rows.data_ptr()))
-    return rows
+        _lib.check(lib.gft_deform_backward_rows(_lib.raw_stream(dev), ctx.arch[0], ctx.arch[1], n, packed.data_ptr(), x_c.data_ptr(),
+                                                t_c.data_ptr(), ctx.t_stride, ptr(gx), ptr(gs), work.data_ptr(),
+                                                C.byref(_fill(_lib.DeformParams(), grads)), rows.data_ptr()))
+    _set_stats("rows", n, None, rows_on_device=rows)
+    _post_count(ctx.state, rows, n)
+
+
+def _count_rows(lib, ctx, packed, kept, gx, gs):
+    """ "count": every row of the saved activations; the rows with a gradient are only counted (three small launches, the
+    count on its way to pinned memory): the next forward decides by it."""
+    n, dev = ctx.n, packed.device
+    if gx is not None or gs is not None:
+        mask = _gradient_mask(lib, n, gx, gs, dev)
+        rank, rows = torch.empty((n,), device=dev, dtype=torch.int32), torch.empty((1,), device=dev, dtype=torch.int32)
+        scratch = torch.empty((lib.gft_rows_rank_scratch_bytes(n),), device=dev, dtype=torch.uint8)
+        with _lib.on_device(dev):
+            _lib.check(lib.gft_rows_rank_dev(_lib.raw_stream(dev), n, mask.data_ptr(), rank.data_ptr(), scratch.data_ptr(), rows.data_ptr()))
+        _post_count(ctx.state, rows, n)
+    return n, kept[0], gx, gs
+
+
+def _gradient_mask(lib, n, gx, gs, dev):
+    """uint8 [n]: 1 for the rows whose upstream gradient holds a value != 0 (a NaN row counts, so a diverged step shows in
+    the weight gradients as it does with the dense backward and in the reference): one pass over the two tensors."""
+    mask = torch.empty((n,), device=dev, dtype=torch.uint8)
+    with _lib.on_device(dev):
+        _lib.check(lib.gft_rows_any_nonzero(_lib.raw_stream(dev), n, 3 if gx is not None else 0, ptr(gx),
+                                            48 if gs is not None else 0, ptr(gs), mask.data_ptr()))
+    return mask
 
 
 def _rows_with_gradient(lib, n, gx, gs, dev):
-    """RowSelection of the rows whose upstream gradient holds a value != 0 (a NaN row counts, so a diverged step shows in
-    the weight gradients as it does with the dense backward and in the reference): one pass over the two tensors."""
+    """RowSelection of the rows with an upstream gradient: their rank and, by one blocking read, their count."""
     from .densify import RowSelection
-    mask = torch.empty((n,), device=dev, dtype=torch.uint8)
-    ptr0 = lambda t: t.data_ptr() if t is not None else None
-    with _lib.on_device(dev):
-        _lib.check(lib.gft_rows_any_nonzero(_lib.raw_stream(dev), n, 3 if gx is not None else 0, ptr0(gx),
-                                            48 if gs is not None else 0, ptr0(gs), mask.data_ptr()))
-    return RowSelection(mask.view(torch.bool))
+    return RowSelection(_gradient_mask(lib, n, gx, gs, dev).view(torch.bool))
 
 
-def _recompute_rows(lib, ctx, n, packed, x_c, t_c, gx, gs):
-    """The forward kept nothing (lazy_save): the saved activations of the rows with an upstream gradient, from a saving
+def _recompute_rows(lib, ctx, packed, kept, gx, gs):
+    """ "recompute": the forward kept nothing; the saved activations of the rows with an upstream gradient, from a saving
     forward over those rows alone (all rows when they turn out to be many), and the gradients of those rows."""
-    dev = packed.device
+    x_c, t_c = kept
+    n, dev = ctx.n, packed.device
     f32 = dict(device=dev, dtype=torch.float32)
-    if n == 0 or (gx is None and gs is None):
-        return 0, None, None, None
-    sel = _rows_with_gradient(lib, n, gx, gs, dev)
-    k = sel.count
+    sel = _rows_with_gradient(lib, n, gx, gs, dev) if n and (gx is not None or gs is not None) else None
+    k = sel.count if sel is not None else 0
     if k == 0:
         return 0, None, None, None
     if k > _SPARSE_MAX_FRACTION * n:
-        k, xs, ts = n, x_c, t_c                                      # dense after all: every row again
+        k, xs, ts = n, x_c, t_c                                     # dense after all: every row again
     else:
         xs = sel.take(x_c)
         ts = t_c if ctx.t_stride == 0 else sel.take(t_c)
@@ -317,27 +306,39 @@ def _recompute_rows(lib, ctx, n, packed, x_c, t_c, gx, gs):
     return k, saved, gx, gs
 
 
-def _compact_rows(lib, n, saved, gx, gs):
-    """Rows of (saved activations, upstream gradients) whose upstream gradient is non-zero, compacted; everything
-    unchanged when most rows count.  `saved` = [n_pad, E] encoding | [8, n_pad, 256] activations | [8, n_pad, 8] ReLU sign
-    words (gft_deform_saved_bytes), n_pad = n rounded up to 192."""
-    sel = _rows_with_gradient(lib, n, gx, gs, saved.device)
+def _compact_rows(lib, ctx, packed, kept, gx, gs):
+    """ "compact": rows of (saved activations, upstream gradients) whose upstream gradient is non-zero, compacted;
+    everything unchanged when most rows count.  `saved` = [n_pad, E] encoding | [8, n_pad, 256] activations | [8, n_pad, 8]
+    ReLU sign words (gft_deform_saved_bytes), n_pad = n rounded up to 192."""
+    n, saved, dev = ctx.n, kept[0], packed.device
+    sel = _rows_with_gradient(lib, n, gx, gs, dev)
     k = sel.count
     if k > _SPARSE_MAX_FRACTION * n:
         return n, saved, gx, gs
     if k == 0:
         return 0, saved, None, None
-    dev = saved.device
     f32 = dict(device=dev, dtype=torch.float32)
     out = torch.empty((lib.gft_deform_saved_bytes(k) // 4,), **f32)
     idx = torch.empty((k,), device=dev, dtype=torch.int32)
     gx_c = torch.empty((k, 3), **f32) if gx is not None else None
     gs_c = torch.empty((k, 16, 3), **f32) if gs is not None else None
-    ptr = lambda t: t.data_ptr() if t is not None else None
     with _lib.on_device(dev):
         _lib.check(lib.gft_deform_compact(_lib.raw_stream(dev), n, k, sel.mask.data_ptr(), sel.rank.data_ptr(), saved.data_ptr(),
                                           ptr(gx), ptr(gs), idx.data_ptr(), out.data_ptr(), ptr(gx_c), ptr(gs_c)))
     return k, out, gx_c, gs_c
+
+
+# route -> (rows processed, their saved activations, their gradients); "rows" has `_backward_rows`
+_SELECT = {"dense": lambda lib, ctx, packed, kept, gx, gs: (ctx.n, kept[0], gx, gs),       # every row, as saved
+           "compact": _compact_rows, "recompute": _recompute_rows, "count": _count_rows}
+
+
+def run_network(net, x, t, params=None):
+    """``d_xyz [n, 3], d_sh [n, 16, 3]`` of ``net`` at (x, t) under autograd.  ``params``: the 24 tensors of ``_param_list``
+    to differentiate in place of the network's own (a detached one receives no gradient)."""
+    if not hasattr(net, "_save_state"):
+        net._save_state = {"fraction": None, "pending": None, "pin": None}       # share of the rows the last backward used
+    return _DeformFn.apply(net.xyz_multires, net.t_multires, net._save_state, x, t, *(_param_list(net) if params is None else params))
 
 
 class DeformNetwork(nn.Module):
@@ -396,9 +397,7 @@ class DeformNetwork(nn.Module):
         are zeros).  ``zeros_as_scalars=True`` returns the Python float 0.0 for those two instead of [n, 4] and [n, 16, 2]
         tensors of zeros -- what train.py:164 passes for a static scene, and what the renderer's additions and
         ``assemble_inputs`` take as well: no 128 bytes per point filled, read and given a gradient for nothing."""
-        if not hasattr(self, "_save_state"):
-            self._save_state = {"fraction": None, "pending": None, "pin": None}      # share of the rows the last backward used
-        d_xyz, d_sh = _DeformFn.apply(self.xyz_multires, self.t_multires, self._save_state, x, t, *_param_list(self))
+        d_xyz, d_sh = run_network(self, x, t)
         if zeros_as_scalars:
             return d_xyz, 0.0, d_sh, 0.0
         n = x.size(0)

@@ -22,7 +22,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .deform import DeformNetwork, _DeformFn, _param_list
+from .deform import DeformNetwork, _param_list, run_network
 
 NAMES = ("d_xyz", "flow_next", "flow_prev")
 
@@ -255,12 +255,10 @@ class DeformQuery:
             empty = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
             return tuple(empty(0, 3) for _ in range(M)), (None if sh_of is None else empty(0, 16, 3))
         x, t = self._inputs(xyz, scene_extent, t_dev, t_host, K, dev)
-        if not hasattr(net, "_save_state"):
-            net._save_state = {"fraction": None, "pending": None, "pin": None}
         params = _param_list(net)
         if sh_of is None:
             params = params[:-6] + [p.detach() for p in params[-6:]]          # r, g, b: no output of theirs is used
-        d_xyz, d_sh = _DeformFn.apply(net.xyz_multires, net.t_multires, net._save_state, x, t, *params)
+        d_xyz, d_sh = run_network(net, x, t, params)
         if combine is None and K == 1:
             outs = (d_xyz,)
         else:

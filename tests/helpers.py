@@ -1,11 +1,32 @@
 """Shared helpers of the parity tests: build a scene, run it through the CPU
 oracle and through the HIP path (public Python API -> C ABI), compare."""
+import contextlib
+
 import numpy as np
 import torch
 
 from gftorf_amd import synth
 
 GRAD_KEYS = ["color", "phasor", "depth", "acc", "depth_distortion"]
+
+
+@contextlib.contextmanager
+def deform_modes(**modes):
+    """Module switches of gftorf_amd.deform set for a block."""
+    from gftorf_amd import deform as D
+    old = {k: getattr(D, k) for k in modes}
+    try:
+        for k, v in modes.items():
+            setattr(D, k, v)
+        yield D
+    finally:
+        for k, v in old.items():
+            setattr(D, k, v)
+
+
+# the blocking selection on exactly the rows with a gradient (with `_save_state = {"fraction": 0.0}`: a forward that keeps
+# nothing, a host read of the count, buffers and launches of exactly that size): the reference of every rows test
+DEFORM_BLOCKING = dict(device_row_count=False, lazy_save=True, _SPARSE_MAX_FRACTION=2.0)
 
 
 # Sensor cameras (the reference hands every colour and ToF camera its own fx, fy, cx, cy: scene/dataset_readers.py:360-375,

@@ -1,6 +1,5 @@
 """Deformation network: oracle vs the reference's golden vectors (CPU),
 HIP path vs oracle (GPU, through the C ABI in include/gftorf_deform.h)."""
-import contextlib
 import functools
 import os
 
@@ -8,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import DEFORM_BLOCKING, deform_modes
 from oracle import deform_ref
 
 # deform.npz: the network as the reference constructs it (scene/deform_model.py:9-16, t_multires = 10: 84 inputs);
@@ -408,15 +408,11 @@ def test_backward_over_rows_with_a_gradient_only(frac, n):
 
     def grads(sparse):
         # (the blocking selection: rows counted by a host read; the rows counted on the device have their own tests below)
-        D.sparse_backward, old = sparse, D.device_row_count
-        D.device_row_count = False
-        try:
+        with deform_modes(sparse_backward=sparse, device_row_count=False):
             net.zero_grad(set_to_none=True)
             d_xyz, _, d_sh, _ = net(x, t)
             torch.autograd.backward([d_xyz, d_sh], [g_dxyz, g_dsh])
             return {k: p.grad.clone() for k, p in net.named_parameters() if p.grad is not None}, dict(D.last_backward_stats)
-        finally:
-            D.sparse_backward, D.device_row_count = True, old
     dense, st_d = grads(False)
     sparse, st_s = grads(True)
     assert st_d == {"points": n, "points_processed": n, "recomputed": False}
@@ -527,15 +523,13 @@ def test_activations_on_demand_give_the_saved_forwards_gradients():
         torch.autograd.backward([d_xyz, d_sh], list(up))
         return {k: p.grad.clone() for k, p in net.named_parameters() if p.grad is not None}, dict(D.last_backward_stats)
 
-    old, old_dev = D.lazy_save, D.device_row_count
-    try:
-        D.device_row_count = "capture"                       # (eagerly the blocking selection: this test's subject)
-        D.lazy_save = False
+    # (device_row_count "capture": eagerly the blocking selection, this test's subject)
+    with deform_modes(device_row_count="capture", lazy_save=False):
         ref_net, _ = _net(12, dev)
         ref_sparse, st = step(ref_net, sparse)
         assert not st["recomputed"] and st["points_processed"] == int(few.sum())
         ref_dense, _ = step(ref_net, (g_dxyz, g_dsh))
-        D.lazy_save = True
+    with deform_modes(device_row_count="capture", lazy_save=True):
         net, _ = _net(12, dev)
         first, st1 = step(net, sparse)                       # nothing known yet: saves
         assert not st1["recomputed"]
@@ -549,27 +543,6 @@ def test_activations_on_demand_give_the_saved_forwards_gradients():
             assert torch.equal(third[k], ref_dense[k]), k
         _, st4 = step(net, (g_dxyz, g_dsh))                  # ... and the next forward saves
         assert not st4["recomputed"]
-    finally:
-        D.lazy_save, D.device_row_count = old, old_dev
-
-
-@contextlib.contextmanager
-def _deform_modes(**modes):
-    """Module switches of gftorf_amd.deform set for a block."""
-    from gftorf_amd import deform as D
-    old = {k: getattr(D, k) for k in modes}
-    try:
-        for k, v in modes.items():
-            setattr(D, k, v)
-        yield D
-    finally:
-        for k, v in old.items():
-            setattr(D, k, v)
-
-
-# the blocking selection on exactly the rows with a gradient (with `_save_state = {"fraction": 0.0}`: a forward that keeps
-# nothing, a host read of the count, buffers and launches of exactly that size): the reference of every rows test
-_BLOCKING = dict(device_row_count=False, lazy_save=True, _SPARSE_MAX_FRACTION=2.0)
 
 
 class _RowsCase:
@@ -603,7 +576,7 @@ class _RowsCase:
         return {k: p.grad for k, p in net.named_parameters() if p.grad is not None}
 
     def blocking(self, m):
-        with _deform_modes(**_BLOCKING) as D:
+        with deform_modes(**DEFORM_BLOCKING) as D:
             self.ref_net._save_state = {"fraction": 0.0}
             grads = self._step(self.ref_net, m)
             st = dict(D.last_backward_stats)
@@ -612,7 +585,7 @@ class _RowsCase:
 
     def on_device(self, m, mode=True, fraction=None):
         """(gradients, the row count left on the device); mode "auto" with the share of rows the loop would have learnt"""
-        with _deform_modes(device_row_count=mode, lazy_save=True) as D:
+        with deform_modes(device_row_count=mode, lazy_save=True) as D:
             if fraction is not None:
                 self.net._save_state = {"fraction": fraction, "pending": None, "pin": None}
             grads = self._step(self.net, m)
@@ -732,10 +705,10 @@ def test_rows_counted_on_the_device_against_the_float64_oracle(k):
         torch.autograd.backward([d_xyz, d_sh], [torch.tensor(gx, device=dev), torch.tensor(gs, device=dev)])
         return {q: p.grad.cpu().numpy() for q, p in net.named_parameters() if p.grad is not None}
 
-    with _deform_modes(device_row_count=False, lazy_save=True) as D:
+    with deform_modes(device_row_count=False, lazy_save=True) as D:
         dense = grads(x[sel], t[sel], g_dxyz[sel], g_dsh[sel])    # (below the row selection's 8192 points: the dense backward)
         assert D.last_backward_stats == {"points": k, "points_processed": k, "recomputed": False}
-    with _deform_modes(device_row_count=True, lazy_save=True) as D:
+    with deform_modes(device_row_count=True, lazy_save=True) as D:
         rows = grads(x, t, g_dxyz, g_dsh)
         assert D.backward_stats() == {"points": n, "points_processed": k, "recomputed": True}
     assert sorted(dense) == sorted(rows) == sorted(q for q, v in ref.items() if v is not None) and len(rows) == 24
@@ -776,15 +749,13 @@ def test_rows_counted_on_the_device_give_the_blocking_selections_gradients(frac,
         torch.autograd.backward([d_xyz, d_sh], [g_dxyz, g_dsh])
         return {k: p.grad.clone() for k, p in net.named_parameters() if p.grad is not None}, dict(D.last_backward_stats)
 
-    old = (D.device_row_count, D.lazy_save, D._SPARSE_MAX_FRACTION)
-    try:
-        # the blocking path on exactly the rows with a gradient: a forward that keeps nothing, rows recomputed
-        D.device_row_count, D.lazy_save, D._SPARSE_MAX_FRACTION = False, True, 2.0
+    # the blocking path on exactly the rows with a gradient: a forward that keeps nothing, rows recomputed
+    with deform_modes(**DEFORM_BLOCKING):
         ref_net, _ = _net(12, dev)
         ref_net._save_state = {"fraction": 0.0}
         ref, st = step(ref_net)
         assert st["recomputed"] and st["points_processed"] == int(keep.sum())
-        D.device_row_count = True
+    with deform_modes(**dict(DEFORM_BLOCKING, device_row_count=True)):
         net, _ = _net(12, dev)
         got, st = step(net)
         assert st["recomputed"] and int(st["rows_on_device"].item()) == int(keep.sum())
@@ -794,8 +765,6 @@ def test_rows_counted_on_the_device_give_the_blocking_selections_gradients(frac,
             assert torch.equal(got[k], ref[k]), k
             if frac == 0.0:
                 assert not got[k].any(), k
-    finally:
-        D.device_row_count, D.lazy_save, D._SPARSE_MAX_FRACTION = old
 
 
 def _captured_replays_follow_the_blocking_selection(n, masks):
@@ -841,7 +810,7 @@ def _captured_replays_follow_the_blocking_selection(n, masks):
         graph.replay()
         got = [None if c is None else c.clone() for c in captured]
         assert int(rows.item()) == int(m.sum())
-        with _deform_modes(**_BLOCKING):
+        with deform_modes(**DEFORM_BLOCKING):
             ref_net._save_state = {"fraction": 0.0}
             ref = run(ref_net)
             assert D.last_backward_stats["recomputed"] and D.last_backward_stats["points_processed"] == int(m.sum())
@@ -906,17 +875,13 @@ def test_the_eager_loop_learns_the_share_of_rows_without_a_host_read():
         torch.cuda.synchronize()                              # (so that the count HAS arrived when the next forward looks)
         return {k: p.grad.clone() for k, p in net.named_parameters() if p.grad is not None}, D.backward_stats()
 
-    old = D.device_row_count
-    try:
-        D.device_row_count = False
-        ref_net, _ = _net(12, dev)
-        D.sparse_backward = False
+    ref_net, _ = _net(12, dev)
+    with deform_modes(device_row_count=False, sparse_backward=False):
         ref_sparse_dense, _ = step(ref_net, sparse)           # dense backward on the sparse gradients
         ref_dense, _ = step(ref_net, dense)
-        D.sparse_backward = True
-        D.device_row_count = True
+    with deform_modes(device_row_count=True, sparse_backward=True):
         ref_rows, _ = step(ref_net, sparse)                   # rows counted on the device (equal to the blocking selection: test above)
-        D.device_row_count = "auto"
+    with deform_modes(device_row_count="auto", sparse_backward=True):
         net, _ = _net(12, dev)
         a, st = step(net, sparse)                             # share unknown: saves, dense, counts
         assert not st["recomputed"] and st["points_processed"] == n
@@ -932,8 +897,6 @@ def test_the_eager_loop_learns_the_share_of_rows_without_a_host_read():
             assert torch.equal(b[k], ref_rows[k]), k
             assert torch.equal(d[k], ref_dense[k]), k
             assert float((c[k] - ref_dense[k]).abs().max()) <= 2e-5 * float(ref_dense[k].abs().max()) + 1e-30, k
-    finally:
-        D.device_row_count, D.sparse_backward = old, True
 
 
 @pytest.mark.gpu
@@ -969,18 +932,52 @@ def test_rows_counted_on_the_device_edge_cases(which):
             torch.autograd.backward([d_xyz, d_sh], [g_dxyz, g_dsh])
         return {k: p.grad.clone() for k, p in net.named_parameters() if p.grad is not None}, D.backward_stats()
 
-    old = (D.device_row_count, D.lazy_save, D._SPARSE_MAX_FRACTION)
-    try:
-        D.device_row_count, D.lazy_save, D._SPARSE_MAX_FRACTION = False, True, 2.0
+    with deform_modes(**DEFORM_BLOCKING):
         ref_net, _ = _net(12, dev)
         ref_net._save_state = {"fraction": 0.0}
         ref, st_ref = step(ref_net)
-        D.device_row_count = True
+    with deform_modes(**dict(DEFORM_BLOCKING, device_row_count=True)):
         net, _ = _net(12, dev)
         got, st = step(net)
-        assert st["points_processed"] == st_ref["points_processed"] == int(keep.sum())
-        assert set(got) == set(ref)
-        for k in ref:
-            assert torch.equal(got[k], ref[k]), k
-    finally:
-        D.device_row_count, D.lazy_save, D._SPARSE_MAX_FRACTION = old
+    assert st["points_processed"] == st_ref["points_processed"] == int(keep.sum())
+    assert set(got) == set(ref)
+    for k in ref:
+        assert torch.equal(got[k], ref[k]), k
+
+
+@pytest.mark.gpu
+def test_every_route_of_the_backward_on_one_call():
+    """One network, 8195 points (above the row selection's 8192, a multiple of no tile), 30 % of the rows with a gradient:
+    a step under the switches that give each route of deform._choose_route.  The three routes that run over the rows with
+    a gradient agree bit for bit, the two that run over every row agree bit for bit, and the two groups agree up to
+    summation order (2e-5 of the max-norm, as test_backward_over_rows_with_a_gradient_only)."""
+    dev = torch.device("cuda:0")
+    n = 8_195
+    x, t = _inputs(n, 4, shared_t=False)
+    xt, tt = torch.tensor(x, device=dev), torch.tensor(t, device=dev)
+    g = torch.Generator().manual_seed(17)
+    keep = (torch.rand((n,), generator=g) < 0.3).to(dev)
+    g_dxyz = torch.randn((n, 3), generator=g).to(dev) * keep[:, None]
+    g_dsh = torch.randn((n, 16, 3), generator=g).to(dev) * keep[:, None, None]
+    assert 0.25 * n < int(keep.sum()) < 0.35 * n
+    net, _ = _net(12, dev)
+    blocking = dict(sparse_backward=True, device_row_count=False)
+    cases = {"dense": (dict(sparse_backward=False, device_row_count=False), None),
+             "compact": (dict(blocking, lazy_save=False), None),
+             "recompute": (dict(blocking, lazy_save=True), 0.2),
+             "count": (dict(sparse_backward=True, device_row_count="auto", lazy_save=True), None),
+             "rows": (dict(sparse_backward=True, device_row_count="auto", lazy_save=True), 0.3)}
+    got = {}
+    for route, (modes, fraction) in cases.items():
+        with deform_modes(**modes) as D:
+            net._save_state = {"fraction": fraction, "pending": None, "pin": None}
+            net.zero_grad(set_to_none=True)
+            d_xyz, _, d_sh, _ = net(xt, tt)
+            torch.autograd.backward([d_xyz, d_sh], [g_dxyz, g_dsh])
+            assert D.last_backward_route == route
+            got[route] = {k: p.grad.clone() for k, p in net.named_parameters() if p.grad is not None}
+            assert len(got[route]) == 24
+    for k in got["dense"]:
+        assert torch.equal(got["recompute"][k], got["compact"][k]) and torch.equal(got["rows"][k], got["compact"][k]), k
+        assert torch.equal(got["count"][k], got["dense"][k]), k
+        assert _rel(got["compact"][k].cpu().numpy(), got["dense"][k].cpu().numpy()) < 2e-5, k

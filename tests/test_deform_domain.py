@@ -23,7 +23,6 @@ octave 9 is |x| = 4096, beyond the fp16 walk's guard, and there the x column its
 output's max-norm.  So a switch lowered, or raised to anything up to 2^20, changes no result beyond rounding, and no
 comparison with float64 at these tolerances can tell; a switch taken out altogether is not seen either, for the same
 reason.  What is pinned is that both paths are right where the reference's scenes put their arguments."""
-import contextlib
 import functools
 import os
 
@@ -31,6 +30,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import deform_modes
 from oracle import deform_ref
 
 FWD_TOL = 3e-6      # as tests/test_deform.py
@@ -68,20 +68,6 @@ def _on_device(x, t, shared_t, dev):
     xt = torch.tensor(x, device=dev)
     tt = torch.tensor(t[:1], device=dev).expand(x.shape[0], -1) if shared_t else torch.tensor(t, device=dev)   # gaussian_model.py:171
     return xt, tt
-
-
-@contextlib.contextmanager
-def _deform_modes(**modes):
-    """Module switches of gftorf_amd.deform set for a block."""
-    from gftorf_amd import deform as D
-    old = {k: getattr(D, k) for k in modes}
-    try:
-        for k, v in modes.items():
-            setattr(D, k, v)
-        yield D
-    finally:
-        for k, v in old.items():
-            setattr(D, k, v)
 
 
 def _check_forward(tag, out, ref, o32, n):
@@ -192,20 +178,20 @@ def test_backward_against_float64(name, tm, n, kind):
     up = lambda a, b: (torch.tensor(a, device=dev), torch.tensor(b, device=dev))
     tag = "%s tm=%d %s" % (name, tm, kind)
     net = _net_of(params, dev, tm)
-    with _deform_modes(sparse_backward=False, device_row_count=False) as D:
+    with deform_modes(sparse_backward=False, device_row_count=False) as D:
         dense = _step(net, xt, tt, *up(g_dxyz, g_dsh))
         assert D.last_backward_stats == {"points": n, "points_processed": n, "recomputed": False}
     _check_grads(tag + " dense", dense, ref_all, o32_all)
     # the blocking selection: a forward that keeps nothing, the count read by the host, the k rows recomputed
     net = _net_of(params, dev, tm)
-    with _deform_modes(sparse_backward=True, device_row_count=False, lazy_save=True, _SPARSE_MAX_FRACTION=2.0, _SPARSE_MIN_POINTS=0) as D:
+    with deform_modes(sparse_backward=True, device_row_count=False, lazy_save=True, _SPARSE_MAX_FRACTION=2.0, _SPARSE_MIN_POINTS=0) as D:
         net._save_state = {"fraction": 0.0}
         blocking = _step(net, xt, tt, *up(s_dxyz, s_dsh))
         assert D.last_backward_stats == {"points": n, "points_processed": k, "recomputed": True}
     _check_grads(tag + " blocking rows", blocking, ref_rows, o32_rows)
     # the rows counted on the device: xyz and t are encoded again by a second forward over the rows that count
     net = _net_of(params, dev, tm)
-    with _deform_modes(sparse_backward=True, device_row_count=True, lazy_save=True, _SPARSE_MIN_POINTS=0) as D:
+    with deform_modes(sparse_backward=True, device_row_count=True, lazy_save=True, _SPARSE_MIN_POINTS=0) as D:
         counted = _step(net, xt, tt, *up(s_dxyz, s_dsh))
         st = dict(D.last_backward_stats)
         assert st["recomputed"] and int(st["rows_on_device"].item()) == k
@@ -276,7 +262,7 @@ def test_head_magnitude_sweep(head_std):
     with torch.no_grad():
         _check_forward(tag + " inference", net(xt, tt), ref, o32, n)
     _check_forward(tag + " saving", net(xt, tt), ref, o32, n)
-    with _deform_modes(sparse_backward=False, device_row_count=False):
+    with deform_modes(sparse_backward=False, device_row_count=False):
         grads = _step(net, xt, tt, torch.tensor(g_dxyz, device=dev), torch.tensor(g_dsh, device=dev))
     _check_grads(tag + " dense", grads, deform_ref.backward(params, x, t, g_dxyz, g_dsh, dtype=np.float64),
                  deform_ref.backward(params, x, t, g_dxyz, g_dsh))
@@ -317,7 +303,7 @@ def test_a_head_of_zero_weights_gives_its_bias_and_no_trunk_gradient(zeroed):
         g_dsh[:, :, 0] = 0
         g_dsh[:, :, 2] = 0
     net.zero_grad(set_to_none=True)
-    with _deform_modes(sparse_backward=False, device_row_count=False):
+    with deform_modes(sparse_backward=False, device_row_count=False):
         torch.autograd.backward([d_xyz, d_sh], [g_dxyz, g_dsh])
     grads = {k: p.grad for k, p in net.named_parameters() if p.grad is not None}
     assert len(grads) == 24

@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import DEFORM_BLOCKING, deform_modes
 from oracle import deform_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -621,22 +622,18 @@ def test_rows_counted_on_the_device_give_the_blocking_selections_gradients(gpu):
         torch.autograd.backward([outs[0], outs[1]], gs)
         return {k: p.grad.clone() for k, p in net.named_parameters() if p.grad is not None}, dict(D.last_backward_stats)
 
-    old = (D.device_row_count, D.lazy_save, D._SPARSE_MAX_FRACTION)
-    try:
-        D.device_row_count, D.lazy_save, D._SPARSE_MAX_FRACTION = False, True, 2.0
+    with deform_modes(**DEFORM_BLOCKING):
         ref_net, _ = _net(12, gpu)
         ref_net._save_state = {"fraction": 0.0}
         ref, st = step(ref_net)
         assert st["points"] == K * n and st["recomputed"] and st["points_processed"] == rows
-        D.device_row_count = True
+    with deform_modes(**dict(DEFORM_BLOCKING, device_row_count=True)):
         net, _ = _net(12, gpu)
         got, st = step(net)
         assert st["points"] == K * n and st["recomputed"] and int(st["rows_on_device"].item()) == rows
         assert len(got) == len(ref) == 18
         for k in ref:
             assert torch.equal(got[k], ref[k]) and bool(got[k].any()), k
-    finally:
-        D.device_row_count, D.lazy_save, D._SPARSE_MAX_FRACTION = old
 
 
 def _flow_step(q, net, xyz, extent, times, combine, gs):
@@ -684,7 +681,7 @@ def test_no_host_sync_and_reproducible(n, gpu):
 def _capture_case(n, gpu, device_rows):
     """The query, a loss and backward captured on static tensors with `times` and `combine` on the device; between replays the
     times, the weights, xyz and the parameters are rewritten in place: every replay against the eager call on those values."""
-    from gftorf_amd import DeformQuery, deform as D
+    from gftorf_amd import DeformQuery
     net, _ = _net(15, gpu)
     others = [deform_ref.random_params(30 + k) for k in range(2)]
     P = 2 * n
@@ -711,10 +708,7 @@ def _capture_case(n, gpu, device_rows):
         loss.backward()
         return [o.detach() for o in outs] + [loss.detach()], {k: p.grad for k, p in net_.named_parameters() if p.grad is not None}
 
-    old = D.device_row_count
-    try:
-        if device_rows:
-            D.device_row_count = True
+    with deform_modes(**(dict(device_row_count=True) if device_rows else {})):
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -742,8 +736,6 @@ def _capture_case(n, gpu, device_rows):
             assert sorted(grads) == sorted(want_grads) and len(grads) == 18
             for name in grads:
                 assert _same_bits(grads[name], want_grads[name]) and bool(grads[name].any()), (k, name)
-    finally:
-        D.device_row_count = old
 
 
 @pytest.mark.gpu
