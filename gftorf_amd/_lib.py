@@ -208,6 +208,11 @@ PCD_ROWS, PCD_MAX_ROW_BYTES, PCD_STATUS_WORDS = 256, 128, 2     # GFT_PCD_ROWS, 
 PCD_MODES = ("torf_init", "ftorf_init", "proxy")                # GFT_PCD_TORF_INIT, GFT_PCD_FTORF_INIT, GFT_PCD_PROXY
 # GFT_PCD_FIELDS: the entries of gft_pcd_unpack's offset table in order
 PCD_FIELDS = ("x", "y", "z", "nx", "ny", "nz", "red", "green", "blue", "phase", "amplitude", "seg_red", "seg_green", "seg_blue")
+# include/gftorf_views.h (the training views on the device; no struct, so the ABI version is unchanged)
+VIEWS_EXPORTS = ["gft_views_layout", "gft_views_draw", "gft_views_select_plane", "gft_views_select_plane_backward"]
+VIEWS_MAX_GROUPS, VIEWS_ALIGN, VIEWS_HEADER_BYTES, VIEWS_CHUNKS = 8, 16, 16, 1024      # GFT_VIEWS_*
+VIEWS_INDEX_WORD, VIEWS_CURSOR_WORD = 0, 1                      # GFT_VIEWS_INDEX_WORD, GFT_VIEWS_CURSOR_WORD
+VIEWS_KINDS = ("f32", "u8")                                     # GFT_VIEWS_F32, GFT_VIEWS_U8
 
 
 def load():
@@ -437,6 +442,18 @@ def load():
     lib.gft_pcd_create.restype = C.c_int
     lib.gft_pcd_create.argtypes = ([C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_int32] + [C.c_void_p] * 12)
+    _longs = C.POINTER(C.c_int64)
+    # F, J, count, kinds, C, H, W, current_bytes, slab_offsets, current_offsets
+    lib.gft_views_layout.restype = C.c_int64
+    lib.gft_views_layout.argtypes = [C.c_int32, C.c_int32, C.c_int32, _ints, _ints, _ints, _ints, _longs, _longs, _longs]
+    # stream, F, J, count, kinds, C, H, W, arena, current, V, index, order, cursor, N, ticket
+    lib.gft_views_draw.restype = C.c_int
+    lib.gft_views_draw.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _ints, _ints, _ints, _ints, C.c_void_p, C.c_void_p,
+                                   C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    # stream, C, plane, x / g_out, index, index_dev, modulo, table, T, out / g_x
+    for fn in (lib.gft_views_select_plane, lib.gft_views_select_plane_backward):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     lib.gft_densify_stats.restype = C.c_int
     lib.gft_densify_stats.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8
     lib.gft_rows_rank_scratch_bytes.restype = C.c_size_t
