@@ -24,9 +24,11 @@ from . import tracks  # noqa: F401
 from . import ply  # noqa: F401
 from . import pcd  # noqa: F401
 from . import views  # noqa: F401
+from . import schedule  # noqa: F401
 from .query import DeformQuery, ftorf_schedule, query_dmlp  # noqa: F401
 from .views import DrawOrder, ViewStore, select_plane  # noqa: F401
+from .schedule import RunSchedule  # noqa: F401
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "GaussianRasterizerPair", "render_pair", "assemble_inputs", "assemble_parameters", "distCUDA2", "FusedAdam", "clip_grad_norm_",
            "DeformNetwork", "REFERENCE_ARCH", "reference_network", "densify",
-           "DeformQuery", "ftorf_schedule", "query_dmlp", "views", "ViewStore", "DrawOrder", "select_plane"]
+           "DeformQuery", "ftorf_schedule", "query_dmlp", "views", "ViewStore", "DrawOrder", "select_plane", "schedule", "RunSchedule"]

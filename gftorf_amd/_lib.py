@@ -213,6 +213,23 @@ VIEWS_EXPORTS = ["gft_views_layout", "gft_views_draw", "gft_views_select_plane",
 VIEWS_MAX_GROUPS, VIEWS_ALIGN, VIEWS_HEADER_BYTES, VIEWS_CHUNKS = 8, 16, 16, 1024      # GFT_VIEWS_*
 VIEWS_INDEX_WORD, VIEWS_CURSOR_WORD = 0, 1                      # GFT_VIEWS_INDEX_WORD, GFT_VIEWS_CURSOR_WORD
 VIEWS_KINDS = ("f32", "u8")                                     # GFT_VIEWS_F32, GFT_VIEWS_U8
+# include/gftorf_schedule.h (the run's schedule on the device; its two structs are new, so the ABI version is unchanged)
+SCHEDULE_EXPORTS = ["gft_schedule_tick"]
+SCHEDULE_MAX_DESTS, SCHEDULE_STATE_WORDS = 1024, 8              # GFT_SCHEDULE_MAX_DESTS, GFT_SCHEDULE_STATE_WORDS
+SCHEDULE_KINDS = ("f64", "f32")                                 # GFT_SCHEDULE_F64, GFT_SCHEDULE_F32
+# GFT_SCHEDULE_*: the int64 words of the state block
+SCHEDULE_COUNTER, SCHEDULE_ITERATION, SCHEDULE_TICKET, SCHEDULE_OVERRUN, SCHEDULE_OVERRUNS = 0, 1, 2, 3, 4
+
+
+class ScheduleDest(C.Structure):
+    """gft_schedule_dest (include/gftorf_schedule.h)"""
+    _fields_ = [("address", _fp), ("column", C.c_int32), ("kind", C.c_int32)]
+
+
+class Schedule(C.Structure):
+    """gft_schedule"""
+    _fields_ = [("state", _fp), ("table", _fp), ("N", C.c_int64), ("C", C.c_int32), ("D", C.c_int32), ("first_iter", C.c_int64),
+                ("dests", _fp), ("bg", _fp), ("n", C.c_int64), ("T", C.c_int64)]
 
 
 def load():
@@ -454,6 +471,9 @@ def load():
     for fn in (lib.gft_views_select_plane, lib.gft_views_select_plane_backward):
         fn.restype = C.c_int
         fn.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+    # stream, schedule
+    lib.gft_schedule_tick.restype = C.c_int
+    lib.gft_schedule_tick.argtypes = [C.c_void_p, C.POINTER(Schedule)]
     lib.gft_densify_stats.restype = C.c_int
     lib.gft_densify_stats.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8
     lib.gft_rows_rank_scratch_bytes.restype = C.c_size_t

@@ -20,7 +20,8 @@ depends on is baked into the launch: ``state["step"]`` is a 0-dim fp32 DEVICE te
 the learning rates are read on the device from a small buffer that every ``step()`` refreshes from ``param_groups`` through
 pinned host memory -- a copy node when captured, so a replay sees whatever ``refresh_lr()`` (or any eager bookkeeping
 that ends in it: the reference's ``update_learning_rate``, scene/gaussian_model.py:294-310, then ``refresh_lr()``) wrote
-there since.  Bias corrections are formed in double precision on the device: N replays leave the parameters N eager
+there since.  ``lr_on_device(True)`` drops that copy: the device buffer is then written by ``schedule.RunSchedule.tick()``,
+itself a node of the graph, and ``lr_slots()`` names its destinations.  Bias corrections are formed in double precision on the device: N replays leave the parameters N eager
 non-capturable steps would (to the rounding of one double ``pow``).  ``step(visibility=mask)`` works in this mode too: the
 mask is read when the kernel runs, so a replay follows the mask's contents of that replay.
 
@@ -115,6 +116,7 @@ class FusedAdam(torch.optim.Adam):
         kw.pop("fused", None)
         self._gft_capturable = bool(kw.pop("capturable", False))
         self._gft_dev = {}              # device -> dict(step, lr, lr_host, factors, used): the buffers of the capturable mode
+        self._gft_lr_on_device = False  # lr_on_device(True): the device slots of the rates belong to a schedule.RunSchedule
         self.last_grad_norm = None      # step(max_grad_norm=...): the gradients' global L2 norm, a 0-dim device tensor
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, **kw)
 
@@ -173,9 +175,42 @@ class FusedAdam(torch.optim.Adam):
         state["step"] = view
         return slot, b
 
+    def lr_on_device(self, on=True):
+        """``lr_on_device(True)``: the learning rates a step reads are whatever the device slots hold -- what the last
+        ``schedule.RunSchedule.tick()`` wrote there (``lr_slots()`` are its destinations).  ``step()`` no longer copies the
+        rates of ``param_groups`` to the device and ``refresh_lr()`` raises: a captured ``{tick; step}`` is the whole
+        statement, and two replays can follow one another with no host work in between.  ``lr_on_device(False)``, the
+        default, is the route through pinned memory described above.  Capturable mode only.  Returns the optimizer."""
+        if on and not self._gft_capturable:
+            raise RuntimeError("gftorf_amd.FusedAdam: lr_on_device(True) needs FusedAdam(capturable=True)")
+        self._gft_lr_on_device = bool(on)
+        return self
+
+    def lr_slots(self):
+        """For every group of ``param_groups``, in order, the device addresses of the float64 learning-rate slots of its
+        parameters (one per parameter tensor that has taken a step; a slot stays with the parameter's state dict, so a
+        re-keyed parameter keeps its slot).  RuntimeError for a parameter without a slot: take one eager ``step()`` first."""
+        if not self._gft_capturable:
+            raise RuntimeError("gftorf_amd.FusedAdam: lr_slots() needs FusedAdam(capturable=True)")
+        out = []
+        for group in self.param_groups:
+            slots = []
+            for p in group["params"]:
+                b = self._gft_dev.get(p.device)
+                slot = self._slot_of(b, self.state[p].get("step")) if b is not None and p in self.state else None
+                if slot is None:
+                    raise RuntimeError("gftorf_amd.FusedAdam: lr_slots(): a parameter of group %r has no slot yet; take one eager "
+                                       "step() first" % (group.get("name", len(out)),))
+                slots.append(b["lr"].data_ptr() + 8 * slot)
+            out.append(slots)
+        return out
+
     def refresh_lr(self):
         """Writes the groups' current learning rates where a captured step reads them (pinned host memory: no device work,
         no synchronisation).  Call it after the scheduler has set ``param_groups[...]["lr"]`` and before the replay."""
+        if self._gft_lr_on_device:
+            raise RuntimeError("gftorf_amd.FusedAdam: refresh_lr() in the lr_on_device(True) mode: the rates are written on the "
+                               "device by schedule.RunSchedule.tick(); change them there (or lr_on_device(False))")
         for group in self.param_groups:
             lr = float(group["lr"])
             for p in group["params"]:
@@ -229,7 +264,8 @@ class FusedAdam(torch.optim.Adam):
                         state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                         state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     slot, b = self._slot(p, state)
-                    b["lr_np"][slot] = lr
+                    if not self._gft_lr_on_device:
+                        b["lr_np"][slot] = lr
                 else:
                     if len(state) == 0:
                         # same state as torch.optim.Adam._init_group
@@ -295,7 +331,8 @@ class FusedAdam(torch.optim.Adam):
                 b = self._buffers(dev)
                 # the learning rates of this step: host values -> device, a copy node under capture (a replay re-reads the pinned
                 # buffer: refresh_lr); once per device
-                if dev not in copied:
+                # (lr_on_device: the slots hold what the schedule's tick wrote)
+                if dev not in copied and not self._gft_lr_on_device:
                     b["lr"].copy_(b["lr_host"], non_blocking=True)
                     copied.add(dev)
                 lrs, steps, factors = (C.c_void_p * n)(), (C.c_void_p * n)(), b["factors"].data_ptr()
