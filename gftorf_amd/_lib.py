@@ -196,6 +196,20 @@ PRESENT_SEISMIC_ROWS = 257                                                      
 # include/gftorf_flowviz.h (the optical-flow debug images; no struct, so the ABI version is unchanged)
 FLOWVIZ_EXPORTS = ["gft_flowviz_blocks", "gft_flowviz_wheel", "gft_flowviz_images"]
 FLOWVIZ_WHEEL_ROWS, FLOWVIZ_IMAGES, FLOWVIZ_RUN = 55, 3, 4      # GFT_FLOWVIZ_WHEEL_ROWS, GFT_FLOWVIZ_IMAGES, GFT_FLOWVIZ_RUN
+# include/gftorf_debugviz.h (the training loop's debug images; no struct, so the ABI version is unchanged)
+DEBUGVIZ_EXPORTS = ["gft_debugviz_blocks", "gft_debugviz_sheet_bytes", "gft_debugviz_images"]
+# GFT_DEBUGVIZ_*: the images of a debug sheet in the order they lie in it: (name, bytes per pixel, shape of an H x W view)
+DEBUGVIZ_IMAGES = (("depth", 4, lambda H, W: (H, W, 4)), ("amp", 1, lambda H, W: (H, W)), ("amp_error", 1, lambda H, W: (H, W)),
+                   ("scattering_phase", 1, lambda H, W: (H, W)), ("scattering_phase_error", 1, lambda H, W: (H, W)),
+                   ("scattering_phase_tof_depth", 1, lambda H, W: (H, W)), ("scattering_phase_tof_depth_error", 1, lambda H, W: (H, W)),
+                   ("scattering_phase_gt", 1, lambda H, W: (H, W)), ("depth_error", 1, lambda H, W: (H, W)),
+                   ("phase_depth", 4, lambda H, W: (H, W, 4)), ("phase_depth_gt", 4, lambda H, W: (H, W, 4)),
+                   ("phase_depth_error", 1, lambda H, W: (H, W)), ("color", 3, lambda H, W: (H, W, 3)),
+                   ("color_gt", 3, lambda H, W: (H, W, 3)), ("color_error", 3, lambda H, W: (H, W, 3)), ("dd", 1, lambda H, W: (H, W)),
+                   ("quad", 4, lambda H, W: (4, H, W)), ("quad_gt", 4, lambda H, W: (4, H, W)), ("quad_error", 4, lambda H, W: (4, H, W)))
+(DEBUGVIZ_HAS_PHASOR, DEBUGVIZ_HAS_GT_PHASOR, DEBUGVIZ_HAS_DEPTH, DEBUGVIZ_HAS_PHASE_DEPTH, DEBUGVIZ_HAS_GT_PHASE_DEPTH, DEBUGVIZ_HAS_DD,
+ DEBUGVIZ_HAS_COLOR, DEBUGVIZ_HAS_QUAD, DEBUGVIZ_HAS_GT_QUAD) = 1, 2, 4, 8, 16, 32, 64, 128, 256
+DEBUGVIZ_ALIGN, DEBUGVIZ_PARTIAL_WORDS, DEBUGVIZ_RANGE_WORDS, DEBUGVIZ_RUN = 16, 16, 8, 4               # GFT_DEBUGVIZ_*
 # include/gftorf_tracks.h (the F-ToRF motion tracks; no struct, so the ABI version is unchanged)
 TRACKS_EXPORTS = ["gft_tracks_integrate", "gft_tracks_table_bytes", "gft_tracks_table"]
 TRACKS_PARTS = ("index", "xy", "motion", "step_ok")             # GFT_TRACKS_*: the parts of a table in the order they lie in it
@@ -423,6 +437,17 @@ def load():
     # stream, H, W, flow, stride, gt, stride, partials, out
     lib.gft_flowviz_images.restype = C.c_int
     lib.gft_flowviz_images.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.gft_debugviz_blocks.restype = C.c_int64
+    lib.gft_debugviz_blocks.argtypes = [C.c_int64]
+    lib.gft_debugviz_sheet_bytes.restype = C.c_int64
+    lib.gft_debugviz_sheet_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
+    # stream, H, W, phasor, stride, planes, gt_phasor, stride, depth, phase_depth, gt_phase_depth, dd, image, stride, gt_image, stride,
+    # gt_quad, stride, permutation, quad_index_dev, quad_index, ranges_dev, ranges_host, znear, zfar, tof_multiplier, partials, sheet
+    lib.gft_debugviz_images.restype = C.c_int
+    lib.gft_debugviz_images.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                        C.POINTER(C.c_int32), C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_float), C.c_float, C.c_float,
+                                        C.c_float, C.c_void_p, C.c_void_p]
     # stream, P, n, T, U, initial_pos, flow, flow_index, K, world_view, mask, rank, H, W, xy, pos_last, motion, mean_z, step_ok
     lib.gft_tracks_integrate.restype = C.c_int
     lib.gft_tracks_integrate.argtypes = ([C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 7 +

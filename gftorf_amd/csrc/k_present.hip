@@ -16,6 +16,7 @@
 #include "gft_tof_depth.h"
 #include "gft_byte_runs.h"
 #include "gft_present_magma.h"
+#include "gft_present_ops.h"
 #include "gft_present_seismic.h"
 #include "gftorf_present.h"
 
@@ -57,41 +58,7 @@ struct PresentArgs {
 
 int64_t prs_blocks(int64_t pixels) { return gft_grid_blocks(pixels, PRS_THREADS, 1, PRS_MAX_BLOCKS); }
 
-// np.minimum / np.maximum: a NaN on either side is the result
-__device__ __forceinline__ float nmin(float a, float b) { return a != a ? a : (b != b ? b : (b < a ? b : a)); }
-__device__ __forceinline__ float nmax(float a, float b) { return a != a ? a : (b != b ? b : (b > a ? b : a)); }
-
-// np.clip(x, 0, 1): a NaN stays
-__device__ __forceinline__ float clip01(float x) { return x < 0.f ? 0.f : (x > 1.f ? 1.f : x); }
-
-// torf_utils.py:11-12; a NaN gives 0
-__device__ __forceinline__ uint32_t to8b(float x)
-{
-    const float s = 255.f * clip01(x);
-    return s == s ? (uint32_t)(int)s : 0u;
-}
-
-// torf_utils.py:21-29 with span = hi - lo: a NaN (0 / 0 of a constant image, a NaN bound) becomes 0
-__device__ __forceinline__ float norm01(float x, float lo, float span)
-{
-    const float n = (x - lo) / span;
-    return clip01(n == n ? n : 0.f);
-}
-
-// to8b(cm.magma(1 - (d - znear) / span)) as one RGBA word: matplotlib's index of a float32 is trunc(x * 256), below 0 the
-// first entry, 256 and above (x == 1 too) the last, a NaN the bad colour
-__device__ __forceinline__ uint32_t magma(const uint32_t* table, float d, float znear, float span)
-{
-    const float x = 1.f - (d - znear) / span;
-    int row;
-    if (x != x) row = 256;
-    else if (x < 0.f) row = 0;
-    else {
-        const float s = x * 256.f;
-        row = s >= 256.f ? 255 : (int)s;
-    }
-    return table[row];
-}
+// nmin, nmax, clip01, to8b, norm01 and magma: gft_present_ops.h
 
 // min or max of the workgroup's values in every thread; sRed has one slot per wave
 template <bool MAX>

@@ -17,6 +17,12 @@ blocking ``.cpu()`` calls, about 130 bytes per pixel -- and forms the images it 
 ``flow_images(flow, gt_flow)``  the three optical-flow images of a direction in the ``pipe.debug`` block (``train.py:380-398``;
     ``csrc/k_flowviz.hip``, ``include/gftorf_flowviz.h``): ``flow_to_image`` of (rendered, target), (target, target) and (target
     - rendered, target) with the in-place edits the three calls share, in two launches; ``ViewSheets.submit_flow`` stages them.
+``debug_images(phasor, gt_phasor, depth, ...)``  the rest of the ``pipe.debug`` block, the ToF branch of ``train.py:295-378``
+    (``csrc/k_debugviz.hip``, ``include/gftorf_debugviz.h``): the depth maps, ``amp`` and the three scattering-phase products with
+    their errors, the colour images, ``dd`` and the quad images with the one normalised quad error, 19 images of 43 bytes per
+    pixel in one sheet, in two launches instead of about twenty blocking ``.cpu()`` copies; ``ViewSheets.submit_debug`` stages
+    them.  The two ToF depths are inputs, as the loop has them, so every statement is an IEEE one and every byte the
+    reference's (tests/test_present_debug.py).
 
 The uint8 images equal the reference's bit for bit wherever its statements are IEEE operations; the one exception is
 ``arctan2`` (in ``depth_tof`` and in the flow images' hue), whose last bits may differ (see tests/test_present.py and
@@ -275,6 +281,189 @@ def flow_images(flow, gt_flow, out=None, _partials=None):
     return {"flow": out[0], "gt": out[1], "error": out[2]}
 
 
+DEBUG_IMAGES = tuple(name for name, _, _ in _lib.DEBUGVIZ_IMAGES)    # the keys, in the order the images lie in a debug sheet
+_DEBUG_EVERY = (_lib.DEBUGVIZ_HAS_PHASOR | _lib.DEBUGVIZ_HAS_GT_PHASOR | _lib.DEBUGVIZ_HAS_DEPTH | _lib.DEBUGVIZ_HAS_PHASE_DEPTH |
+                _lib.DEBUGVIZ_HAS_GT_PHASE_DEPTH | _lib.DEBUGVIZ_HAS_DD | _lib.DEBUGVIZ_HAS_COLOR | _lib.DEBUGVIZ_HAS_QUAD |
+                _lib.DEBUGVIZ_HAS_GT_QUAD)
+
+
+def debug_blocks(pixels):
+    """workgroups of ``debug_images``' launches over an image of `pixels` = rows of its partials; 0 for no pixel"""
+    return int(_lib.load().gft_debugviz_blocks(int(pixels)))
+
+
+def debug_sheet_layout(H, W, groups):
+    """(bytes of the sheet, {image name: byte offset}) of the debug images of an H x W view with the ``_lib.DEBUGVIZ_HAS_*``
+    groups `groups`"""
+    offsets = (C.c_int64 * len(DEBUG_IMAGES))()
+    total = int(_lib.load().gft_debugviz_sheet_bytes(int(H), int(W), int(groups), offsets))
+    if total < 1:
+        raise ValueError("gftorf_amd.present: no debug sheet for H=%d W=%d groups=%d" % (H, W, groups))
+    return total, {name: int(offsets[k]) for k, name in enumerate(DEBUG_IMAGES) if offsets[k] >= 0}
+
+
+def _plane(t, name, size):
+    """an [H, W] plane (``tof.depth_from_tof``'s result) as a [1, H, W] one, sized like the other inputs"""
+    t = _args.tensor(_TAG, t, name)
+    if t.dim() != 2:
+        raise RuntimeError("gftorf_amd.present: %s must be [H, W], got %s" % (name, list(t.shape)))
+    return _planes(t[None], name, 1, 1, size)[0]
+
+
+def debug_images(phasor=None, gt_phasor=None, depth=None, phase_depth=None, gt_phase_depth=None, dd=None, image=None, gt_image=None,
+                 gt_quad=None, *, permutation=(0, 1, 2, 3), quad_index=None, ranges=None, zplanes=None, tof_multiplier=1.0, out=None,
+                 _partials=None):
+    """The debug images of one training iteration, the ToF branch of ``train.py:295-378``, as a dict of uint8 device tensors
+    that are views into one buffer (the sheet; every image starts on a 16-byte boundary of it).  All inputs are float32 on
+    one HIP device and share one H x W; every one is optional, and an image is produced when every input its formula names
+    is given.  With ``amp = phasor[2] * tof_multiplier``, ``gt_amp = gt_phasor[2]``, ``sp = amp * depth ** 2``, ``sp_tof = amp *
+    phase_depth ** 2`` and ``gt_sp = gt_amp * gt_phase_depth ** 2``:
+
+    ``depth`` [1, H, W]: ``depth`` [H, W, 4], the magma map of ``view_images``.
+    ``phasor`` [>= 3, H, W] (plane 2 read in place through the stride): ``amp`` [H, W]; with ``gt_phasor`` [>= 3, H, W]
+        ``amp_error``, normalised by its own min and max; with ``depth`` ``scattering_phase``, with ``phase_depth`` [H, W]
+        ``scattering_phase_tof_depth``; with ``gt_phasor`` and ``gt_phase_depth`` [H, W] their unnormalised
+        ``scattering_phase_error`` / ``scattering_phase_tof_depth_error``.
+    ``gt_phasor`` and ``gt_phase_depth``: ``scattering_phase_gt``.
+    ``phase_depth``, ``gt_phase_depth`` (``tof.depth_from_tof``'s, as ``train.py:188-189`` has them): ``phase_depth``,
+        ``phase_depth_gt`` [H, W, 4]; together ``phase_depth_error``, and with ``depth`` ``depth_error``, each normalised by its
+        own min and max.
+    ``image``, ``gt_image`` [3, H, W], given together: ``color``, ``color_gt``, ``color_error`` [H, W, 3].
+    ``dd`` [1, H, W]: ``dd`` [H, W], normalised by its own min and max.
+    ``phasor`` of exactly 7 planes: ``quad`` [4, H, W]; with ``gt_quad`` [4, H, W] also ``quad_gt`` and ``quad_error``, whose plane
+        i shows ``gt_quad[permutation[i]]`` and is all 0 unless ``permutation[i] == quad_index``.
+
+    ``permutation``: ``scene.tof_permutation``, four host integers in 0..3.  ``quad_index``: ``frame_id % 4`` as an int, or a
+    one-element int32 device tensor read when the kernel runs.  ``ranges``: eight numbers, or a contiguous float32 device
+    tensor [8] read when the kernel runs -- the (lo, hi) of ``amp``, ``scattering_phase``, ``scattering_phase_tof_depth`` and
+    ``scattering_phase_gt``, which ``train.py:317``'s zip makes ``np.min`` / ``np.max`` over the training sequence of ``gt_reals``,
+    ``gt_imags``, ``gt_amps`` (``PhasorRanges.tensor``, in that order) and ``gt_scattering_phases``.  ``zplanes`` = (znear, zfar) of
+    the colour map, by value (``zplanes()``).  ``out``: a uint8 device tensor of at least the sheet's size, 16-byte aligned, to
+    write into; else a new one.  At most two launches; nothing is read on the host, so the call can be captured in a graph,
+    and the bytes are the reference's."""
+    lib = _lib.load()
+    named, size = [], None
+
+    def take(t, name, least, most):
+        nonlocal size
+        t, stride = _planes(t, name, least, most, size)
+        if size is None:
+            size = ((int(t.shape[1]), int(t.shape[2])), name)
+        named.append((t, name))
+        return t, stride
+
+    def take_plane(t, name):
+        nonlocal size
+        t = _plane(t, name, size)
+        if size is None:
+            size = ((int(t.shape[1]), int(t.shape[2])), name)
+        named.append((t, name))
+        return t
+
+    ph = gph = d = pd = gpd = dist = im = gim = gq = None
+    ph_stride = gph_stride = im_stride = gim_stride = gq_stride = planes = 0
+    if (image is None) != (gt_image is None):
+        raise ValueError("gftorf_amd.present: image and gt_image are given together, got only %s"
+                         % ("image" if gt_image is None else "gt_image"))
+    if phasor is not None:
+        ph, ph_stride = take(phasor, "phasor", 3, 1 << 30)
+        planes = int(ph.shape[0])
+    if gt_phasor is not None:
+        gph, gph_stride = take(gt_phasor, "gt_phasor", 3, 1 << 30)
+    if depth is not None:
+        d = take(depth, "depth", 1, 1)[0]
+    if phase_depth is not None:
+        pd = take_plane(phase_depth, "phase_depth")
+    if gt_phase_depth is not None:
+        gpd = take_plane(gt_phase_depth, "gt_phase_depth")
+    if dd is not None:
+        dist = take(dd, "dd", 1, 1)[0]
+    if image is not None:
+        im, im_stride = take(image, "image", 3, 3)
+        gim, gim_stride = take(gt_image, "gt_image", 3, 3)
+    if gt_quad is not None:
+        if planes != 7:
+            raise RuntimeError("gftorf_amd.present: gt_quad needs a phasor of exactly 7 planes, got %s"
+                               % ("none" if ph is None else list(ph.shape)))
+        gq, gq_stride = take(gt_quad, "gt_quad", 4, 4)
+    if not named:
+        raise ValueError("gftorf_amd.present: nothing to show: give phasor, depth, phase_depth, gt_phase_depth, dd or image")
+    groups = ((_lib.DEBUGVIZ_HAS_PHASOR if ph is not None else 0) | (_lib.DEBUGVIZ_HAS_GT_PHASOR if gph is not None else 0) |
+              (_lib.DEBUGVIZ_HAS_DEPTH if d is not None else 0) | (_lib.DEBUGVIZ_HAS_PHASE_DEPTH if pd is not None else 0) |
+              (_lib.DEBUGVIZ_HAS_GT_PHASE_DEPTH if gpd is not None else 0) | (_lib.DEBUGVIZ_HAS_DD if dist is not None else 0) |
+              (_lib.DEBUGVIZ_HAS_COLOR if im is not None else 0) | (_lib.DEBUGVIZ_HAS_QUAD if planes == 7 else 0) |
+              (_lib.DEBUGVIZ_HAS_GT_QUAD if gq is not None else 0))
+    (H, W) = size[0]
+    total, offsets = debug_sheet_layout(H, W, groups)
+    perm, qi_t, qi = None, None, 0
+    if gq is not None:
+        try:
+            vals = [int(k) for k in (permutation.tolist() if hasattr(permutation, "tolist") else permutation)]
+        except (TypeError, ValueError):
+            raise TypeError("gftorf_amd.present: permutation must be four integers, got %r" % (permutation,)) from None
+        if len(vals) != 4 or any(not 0 <= k <= 3 for k in vals):
+            raise ValueError("gftorf_amd.present: permutation must be four integers in 0..3, got %s" % vals)
+        perm = (C.c_int32 * 4)(*vals)
+        if quad_index is None:
+            raise ValueError("gftorf_amd.present: quad_error of gt_quad needs quad_index = frame_id % 4")
+        if isinstance(quad_index, torch.Tensor):
+            qi_t = _args.tensor(_TAG, quad_index, "quad_index", (torch.int32,))
+            if qi_t.numel() != 1:
+                raise RuntimeError("gftorf_amd.present: quad_index must be an integer or a one-element tensor, got %s" % list(qi_t.shape))
+            named.append((qi_t, "quad_index"))
+        else:
+            qi = int(quad_index)
+    rg_t, rg_host = None, None
+    if "amp" in offsets or "scattering_phase_gt" in offsets:
+        words = _lib.DEBUGVIZ_RANGE_WORDS
+        if ranges is None:
+            raise ValueError("gftorf_amd.present: amp and the scattering phases need ranges")
+        if isinstance(ranges, torch.Tensor):
+            rg_t = _args.tensor(_TAG, ranges, "ranges")
+            if tuple(rg_t.shape) != (words,) or not rg_t.is_contiguous():
+                raise RuntimeError("gftorf_amd.present: ranges must be eight numbers or a contiguous tensor [8], got %s" % list(rg_t.shape))
+            named.append((rg_t, "ranges"))
+        else:
+            vals = [float(x) for x in np.asarray(ranges, dtype=np.float32).reshape(-1)]
+            if len(vals) != words:
+                raise RuntimeError("gftorf_amd.present: ranges must be eight numbers or a contiguous tensor [8], got %d numbers" % len(vals))
+            rg_host = (C.c_float * words)(*vals)
+    znear = zfar = 0.0
+    if d is not None or pd is not None or gpd is not None:
+        if zplanes is None:
+            raise ValueError("gftorf_amd.present: the colour map of a depth needs zplanes = (znear, zfar)")
+        znear, zfar = (float(z) for z in zplanes)
+    dev = _args.devices(_TAG, "display", named)
+    if out is None:
+        out = torch.empty((total,), device=dev, dtype=torch.uint8)
+    else:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous():
+            raise TypeError("gftorf_amd.present: out must be a contiguous one-dimensional torch.uint8 tensor")
+        if out.device != dev:
+            raise RuntimeError("gftorf_amd.present: the images are on %s, out on %s" % (dev, out.device))
+        if out.numel() < total or out.data_ptr() % _lib.DEBUGVIZ_ALIGN:
+            raise RuntimeError("gftorf_amd.present: out has %d bytes at an address %s 16-byte aligned, the sheet needs %d aligned bytes"
+                               % (out.numel(), "that is not" if out.data_ptr() % _lib.DEBUGVIZ_ALIGN else "that is", total))
+    rows = debug_blocks(H * W)
+    partials = _partials
+    if partials is None:
+        partials = torch.empty((rows, _lib.DEBUGVIZ_PARTIAL_WORDS), device=dev, dtype=torch.float32)
+    elif (not isinstance(partials, torch.Tensor) or partials.dtype != torch.float32 or partials.device != dev
+          or partials.numel() < rows * _lib.DEBUGVIZ_PARTIAL_WORDS or not partials.is_contiguous() or partials.data_ptr() % 16):
+        raise RuntimeError("gftorf_amd.present: the partials of a %d x %d debug sheet are %d x %d contiguous float32 on %s, 16-byte aligned"
+                           % (H, W, rows, _lib.DEBUGVIZ_PARTIAL_WORDS, dev))
+    with _lib.on_device(dev):
+        _lib.check(lib.gft_debugviz_images(_lib.raw_stream(dev), H, W, _ptr(ph), ph_stride, planes, _ptr(gph), gph_stride, _ptr(d), _ptr(pd),
+                                           _ptr(gpd), _ptr(dist), _ptr(im), im_stride, _ptr(gim), gim_stride, _ptr(gq), gq_stride, perm,
+                                           _ptr(qi_t), qi, _ptr(rg_t), rg_host, znear, zfar, float(tof_multiplier), partials.data_ptr(),
+                                           out.data_ptr()))
+    images = {}
+    for name, bpp, shape in _lib.DEBUGVIZ_IMAGES:
+        if name in offsets:
+            images[name] = out[offsets[name]:offsets[name] + bpp * H * W].view(shape(H, W))
+    return images
+
+
 class PhasorRanges:
     """The normalisation ranges of ``real``, ``imag`` and ``amp``: ``save_input``'s ``np.min`` / ``np.max`` over the whole
     ground-truth sequence (``render.py:46-47, 61``) as a float32 device tensor [6] = (lo, hi) three times::
@@ -402,6 +591,43 @@ class ViewSheets:
         slot["event"].record()
         host = slot["host"].numpy()[:need].reshape(_lib.FLOWVIZ_IMAGES, H, W, 3)
         slot.update(state="flight", tag=tag, arrays={"flow": host[0], "gt": host[1], "error": host[2]})
+        self._order.append(slot)
+
+    def submit_debug(self, tag, **debug):
+        """``debug_images(**debug)`` into a free slot, the sheet's copy to pinned memory and an event, all on the current stream;
+        ``ready`` yields the tag with the images ``debug_images`` returns, as uint8 arrays"""
+        slot = next((s for s in self._slots if s["state"] == "free"), None)
+        if slot is None:
+            raise RuntimeError("gftorf_amd.present: all %d slots of this ViewSheets are in flight; take the finished views with ready()"
+                               % len(self._slots))
+        keys = ("phasor", "gt_phasor", "depth", "phase_depth", "gt_phase_depth", "dd", "image", "gt_image", "gt_quad")
+        first = next((v for v in (debug.get(k) for k in keys) if isinstance(v, torch.Tensor)), None)
+        if first is None or first.dim() not in (2, 3):
+            raise ValueError("gftorf_amd.present: nothing to show: give phasor, depth, dd or image as [C, H, W] tensors, the ToF depths "
+                             "as [H, W] ones")
+        dev = _args.devices(_TAG, "display", [(first, next(k for k in keys if debug.get(k) is first))])
+        H, W = int(first.shape[-2]), int(first.shape[-1])
+        # the largest debug sheet of this size: what the groups leave out is not copied
+        full = debug_sheet_layout(H, W, _DEBUG_EVERY)[0]
+        if slot["device"] is None or slot["device"].numel() < full or slot["device"].device != dev:
+            slot["device"] = torch.empty((full,), device=dev, dtype=torch.uint8)
+            slot["host"] = torch.empty((full,), dtype=torch.uint8, pin_memory=True)
+            # submit() takes a slot whose buffer is large enough with its partials: rows for as many pixels as there are bytes
+            slot["partials"] = torch.empty((max(1, blocks(full)), _lib.PRESENT_PARTIAL_WORDS), device=dev, dtype=torch.float32)
+            slot["event"] = torch.cuda.Event()
+        rows = debug_blocks(H * W)
+        scratch = slot.get("debug_partials")
+        if scratch is None or scratch.shape[0] < rows or scratch.device != dev:
+            scratch = slot["debug_partials"] = torch.empty((rows, _lib.DEBUGVIZ_PARTIAL_WORDS), device=dev, dtype=torch.float32)
+        images = debug_images(out=slot["device"], _partials=scratch, **debug)
+        last = max(images.values(), key=lambda t: t.data_ptr())
+        used = last.data_ptr() - slot["device"].data_ptr() + last.numel()
+        slot["host"][:used].copy_(slot["device"][:used], non_blocking=True)
+        slot["event"].record()
+        host = slot["host"].numpy()
+        base = slot["device"].data_ptr()
+        arrays = {name: host[t.data_ptr() - base:t.data_ptr() - base + t.numel()].reshape(tuple(t.shape)) for name, t in images.items()}
+        slot.update(state="flight", tag=tag, arrays=arrays)
         self._order.append(slot)
 
     def ready(self, wait=False):
