@@ -5,6 +5,8 @@ Drop-in for the reference's ``diff_gaussian_rasterization_w_tof`` extension
 operator API, hand-written gfx950 HIP kernels behind a C ABI
 (include/gftorf_rast.h).  See DESIGN.md.
 """
+from . import reproducible  # noqa: F401  (first: api, flow and deform read the switch; the module is callable)
+from .reproducible import set_reproducible, is_reproducible  # noqa: F401
 from .api import (GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians,  # noqa: F401
                   _RasterizeGaussians)
 from .pair import GaussianRasterizerPair, render_pair  # noqa: F401
@@ -31,4 +33,5 @@ from .schedule import RunSchedule  # noqa: F401
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "GaussianRasterizerPair", "render_pair", "assemble_inputs", "assemble_parameters", "distCUDA2", "FusedAdam", "clip_grad_norm_",
            "DeformNetwork", "REFERENCE_ARCH", "reference_network", "densify",
-           "DeformQuery", "ftorf_schedule", "query_dmlp", "views", "ViewStore", "DrawOrder", "select_plane", "schedule", "RunSchedule"]
+           "DeformQuery", "ftorf_schedule", "query_dmlp", "views", "ViewStore", "DrawOrder", "select_plane", "schedule", "RunSchedule",
+           "reproducible", "set_reproducible", "is_reproducible"]

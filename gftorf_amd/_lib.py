@@ -155,7 +155,10 @@ EXPORTS = [
 FLOW_EXPORTS = ["gft_flow_loss_blocks", "gft_flow_loss_forward", "gft_flow_loss_backward", "gft_flow_points", "gft_flow_project",
                 "gft_flow_project_backward"]
 # include/gftorf_features.h (the feature blend over a drawn frame; no struct, so the ABI version is unchanged)
-FEATURE_EXPORTS = ["gft_render_features", "gft_render_features_backward"]
+FEATURE_EXPORTS = ["gft_render_features", "gft_render_features_backward", "gft_feature_partials_bytes",
+                   "gft_render_features_backward_det"]
+# include/gftorf_detsum.h (the fixed-order sum of the reproducible backwards; no struct, so the ABI version is unchanged)
+DETSUM_EXPORTS = ["gft_detsum_index_bytes", "gft_backward_det"]
 # include/gftorf_reg.h (the per-Gaussian regularisers of the loss; no struct, so the ABI version is unchanged)
 REG_EXPORTS = ["gft_reg_blocks", "gft_reg_result_words", "gft_reg_forward", "gft_reg_backward"]
 REG_PARTIAL_WORDS = 8           # GFT_REG_PARTIAL_WORDS
@@ -363,6 +366,12 @@ def load():
     lib.gft_render_features.argtypes = _feat_frame + [C.c_void_p] * 3
     lib.gft_render_features_backward.restype = C.c_int
     lib.gft_render_features_backward.argtypes = _feat_frame + [C.c_void_p] * 3
+    lib.gft_feature_partials_bytes.restype = C.c_size_t
+    lib.gft_feature_partials_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
+    lib.gft_render_features_backward_det.restype = C.c_int
+    lib.gft_render_features_backward_det.argtypes = _feat_frame + [C.c_void_p] * 4     # dL_dout, index, partials, dL_dfeatures
+    lib.gft_detsum_index_bytes.restype = C.c_size_t
+    lib.gft_detsum_index_bytes.argtypes = [C.c_int32, C.c_int64]
     # stream, n_dxyz, P, pixels, d_xyz, opacity, motion_mask, opacity_is_raw, scaling, scaling_cols, scaling_is_raw, visible,
     # visible_is_radii
     _reg_inputs = ([C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
@@ -552,6 +561,8 @@ def load():
     lib.gft_forward_enqueue.argtypes = [C.c_void_p, C.POINTER(Config), C.POINTER(ForwardIO), C.POINTER(ForwardHints), C.c_void_p]
     lib.gft_backward.restype = C.c_int
     lib.gft_backward.argtypes = [C.c_void_p, C.POINTER(Config), C.POINTER(BackwardIO), C.c_int64]
+    lib.gft_backward_det.restype = C.c_int
+    lib.gft_backward_det.argtypes = [C.c_void_p, C.POINTER(Config), C.POINTER(BackwardIO), C.c_int64, C.c_void_p]
     lib.gft_grads_rezero.restype = C.c_int
     lib.gft_grads_rezero.argtypes = [C.c_void_p, C.POINTER(Config), C.POINTER(BackwardIO)]
     lib.gft_mark_visible.restype = C.c_int

@@ -22,6 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from . import reproducible as _reproducible
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -177,6 +178,7 @@ _instance_hint, _status, _grad_pool, _acc_pool = state.instance_hint, state.stat
 # GFT_BWD_DETERMINISTIC=1: the backward forms its per-Gaussian sums in a fixed order instead of with float atomics
 # (bit-reproducible gradients; several times slower: for tests)
 _DETERMINISTIC = _os.environ.get("GFT_BWD_DETERMINISTIC", "0") != "0"
+_det_keep = None               # tests: a list that receives (partial rows, capacity) of every fixed-order backward
 _HINT_HEADROOM = 1.25
 # Schedule switches (all on; each one off gives the same results slower: INTEGRATION.md section J)
 _TILE_HINTS = _os.environ.get("GFT_TILE_HINTS", "1") != "0"
@@ -958,6 +960,12 @@ def prepare_backward(s, means3D, opac, sh, sh_p, scales, rotations, cov3D, radii
     # (a reused set: the backward zeroes the rows the previous one wrote and this one does not, then writes its own
     # -- cfg.grads_zeroed = 3 -- or writes everything, _GradEntry.write_mode; `sample`: it reports its row count)
     rows_only, sample = entry.write_mode(P) if reused else (False, False)
+    if _reproducible.is_reproducible():
+        # Whether a kept set is reused hangs on reference counts and on row counts posted to pinned memory -- on when the
+        # host looked.  Every per-Gaussian gradient is the same either way, but the two offset gradients are not: the
+        # rows-only kernel sums them per thread over its rows, the full one per wave over the Gaussians (k_preprocess.hip),
+        # two orders.  The reproducible mode always writes in full: one order (and no report, nothing to wait for).
+        rows_only, sample = False, False
     acc_zeroed = acc is not None
     if acc is None:            # second backward through the same forward (retain_graph), or the pybind-level route
         acc = torch.empty((_lib.load().gft_acc_bytes(P) // 4,), device=dev, dtype=torch.float32)
@@ -1023,13 +1031,21 @@ def run_backward(prep, grads_out, geom, binning, img, debug=False):
     cap = prep.cap                     # (known to the forward that made `prep`; else read back from the buffer's size)
     if cap is None:
         cap = binning_capacity(binning, W, H) if P else 0
-    if _DETERMINISTIC and P and cap:
-        # test mode: partial rows per (list entry, quadrant), added in a fixed order (gft_backward_io.det_partials)
+    det_index = None
+    if (_DETERMINISTIC or _reproducible.is_reproducible()) and P and cap:
+        # fixed-order mode (GFT_BWD_DETERMINISTIC alone, or the reproducible mode: read per call, so a captured graph keeps
+        # the mode it was captured under): partial rows per (list entry, quadrant), added in one order
+        # (gft_backward_io.det_partials, include/gftorf_detsum.h)
         # (capturable since round 6: what gave wrong sums from the second replay on was the library's hipMemsetAsync of this
         # buffer -- a large memset node is not ordered against its neighbours when a graph is replayed on this platform; the
         # library clears with a kernel now, gft_api.hip gft_zero_async)
         det = torch.empty((lib.gft_det_partials_bytes(cap, W, H) // 4,), dtype=torch.float32, device=dev)
         io.det_partials = det.data_ptr()
+        if _reproducible.det_reduce() == "grid":
+            # the rows added across the chip (csrc/k_detsum.hip); "serial": the one-workgroup comparator, same bits
+            det_index = torch.empty((lib.gft_detsum_index_bytes(P, cap) // 4,), dtype=torch.int32, device=dev)
+        if _det_keep is not None:
+            _det_keep.append((det, cap))
     cpu_args = cpu_deep_copy_tuple(prep.debug_args + tuple(grads_out) + (geom, binning, img)) if debug else None
     lease, pool_entry = prep.acc_lease, prep.pool_entry
     if lease is not None:
@@ -1037,7 +1053,10 @@ def run_backward(prep, grads_out, geom, binning, img, debug=False):
     try:
         with _lib.on_device(dev):
             stream = _lib.raw_stream(dev)
-            _lib.check(lib.gft_backward(stream, C.byref(prep.cfg), C.byref(io), cap))
+            if det_index is not None:
+                _lib.check(lib.gft_backward_det(stream, C.byref(prep.cfg), C.byref(io), cap, det_index.data_ptr()))
+            else:
+                _lib.check(lib.gft_backward(stream, C.byref(prep.cfg), C.byref(io), cap))
         if pool_entry is not None and not prep.cfg.grads_accumulate:
             pool_entry.valid = True    # every row of the kept gradient tensors is defined now (_GradEntry)
         if lease is not None and prep.cfg.acc_zeroed == 2:

@@ -2,6 +2,7 @@
 // stage sequencing, stream handling, error strings, per-stage HIP-event timing.
 // No torch headers; stateless between calls except for the opt-in profiler.
 #include "gft_internal.h"
+#include "gftorf_detsum.h"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -26,7 +27,7 @@ extern "C" const char* gft_last_error(void) { return g_err; }
 extern "C" int gft_abi_version(void) { return GFT_ABI_VERSION; }
 // ids a point_list sized for `binning_instances` holds: one head slot per tile + the pool (tile-pull binning), which
 // is also what whole-frame binning needs (binning_instances ids)
-static size_t point_list_slots(int64_t binning_instances, int32_t W, int32_t H)
+size_t gft_point_list_slots(int64_t binning_instances, int32_t W, int32_t H)
 {
     if (binning_instances <= 0) return 0;
     const size_t T = (size_t)((W + GFT_TILE_X - 1) / GFT_TILE_X) * (size_t)((H + GFT_TILE_Y - 1) / GFT_TILE_Y);
@@ -34,7 +35,7 @@ static size_t point_list_slots(int64_t binning_instances, int32_t W, int32_t H)
 }
 extern "C" size_t gft_det_partials_bytes(int64_t binning_instances, int32_t W, int32_t H)
 {
-    return point_list_slots(binning_instances, W, H) * 4 * GFT_ACC_STRIDE * sizeof(float);
+    return gft_point_list_slots(binning_instances, W, H) * 4 * GFT_ACC_STRIDE * sizeof(float);
 }
 // inverse of gft_binning_bytes for capacities that are multiples of 64 (what a caller that only holds the buffer needs)
 extern "C" int64_t gft_binning_capacity(size_t bytes, int32_t W, int32_t H)
@@ -783,7 +784,34 @@ extern "C" int gft_forward_enqueue(void* hip_stream, const gft_config* cfg, cons
 }
 
 // ---- backward -----------------------------------------------------------------
+static int backward_impl(void* hip_stream, const gft_config* cfg, const gft_backward_io* io, int64_t num_rendered,
+                         uint32_t* det_index);
+
 extern "C" int gft_backward(void* hip_stream, const gft_config* cfg, const gft_backward_io* io, int64_t num_rendered)
+{
+    return backward_impl(hip_stream, cfg, io, num_rendered, nullptr);
+}
+
+// include/gftorf_detsum.h
+extern "C" size_t gft_detsum_index_bytes(int32_t P, int64_t binning_instances)
+{
+    return (gft_detsum_index_words(P, binning_instances) * sizeof(uint32_t) + GFT_ALIGN - 1) / GFT_ALIGN * GFT_ALIGN;
+}
+
+extern "C" int gft_backward_det(void* hip_stream, const gft_config* cfg, const gft_backward_io* io, int64_t num_rendered,
+                                void* index)
+{
+    if (io && !io->det_partials && cfg && cfg->P > 0 && num_rendered > 0)
+        return gft_fail("gft_backward_det: io->det_partials is NULL");
+    if (((uintptr_t)index & 3u) != 0) return gft_fail("gft_backward_det: index must be 4-byte aligned");
+    // (the index holds list positions + 1 in 32 bits)
+    if (index && cfg && gft_point_list_slots(num_rendered, cfg->W, cfg->H) >= 0xffffffffull)
+        return gft_fail("gft_backward_det: the frame's id list is too long for the index");
+    return backward_impl(hip_stream, cfg, io, num_rendered, (uint32_t*)index);
+}
+
+static int backward_impl(void* hip_stream, const gft_config* cfg, const gft_backward_io* io, int64_t num_rendered,
+                         uint32_t* det_index)
 {
     if (check_config(cfg)) return 1;
     if (!io) return gft_fail("gft_backward: io is NULL");
@@ -836,7 +864,7 @@ extern "C" int gft_backward(void* hip_stream, const gft_config* cfg, const gft_b
     }
     if (num_rendered > 0) {
         StageTimer t(s, ST_RENDER_BWD);
-        GFT_STAGE(s, cfg, "render_bwd", gft_launch_render_bwd(s, *cfg, *io, g, im, b, lazy_sort_enabled(), (uint32_t)num_rendered));
+        GFT_STAGE(s, cfg, "render_bwd", gft_launch_render_bwd(s, *cfg, *io, g, im, b, lazy_sort_enabled(), (uint32_t)num_rendered, det_index));
     }
     {
         StageTimer t(s, ST_PRE_BWD);

@@ -213,8 +213,21 @@ hipError_t gft_launch_tail_build(hipStream_t s, const gft_config& c, const gft_f
 hipError_t gft_launch_render_fwd(hipStream_t s, const gft_config& c, const gft_forward_io& io,
                                  const GeomView& g, const ImgView& im, const BinView& b, bool check_cap, uint32_t cap,
                                  int lazy, bool pull, bool segmented = true);
+// det_index: the fixed-order mode (io.det_partials) adds its rows with the grid-wide sum (k_detsum.hip); NULL: k_acc_reduce_det
 hipError_t gft_launch_render_bwd(hipStream_t s, const gft_config& c, const gft_backward_io& io,
-                                 const GeomView& g, const ImgView& im, const BinView& b, bool lazy, uint32_t cap);
+                                 const GeomView& g, const ImgView& im, const BinView& b, bool lazy, uint32_t cap,
+                                 uint32_t* det_index = nullptr);
+// the fixed-order sum of stored partial rows (include/gftorf_detsum.h; k_detsum.hip).  rows: [list slot][4][stride], stride 8
+// or 16, the first nv values of a row summed into out[g * out_stride + k]; accumulate: added to what `out` holds (rows of
+// Gaussians without a tile are not touched), else `out` is written in full.  index: gft_detsum_index_words(P, cap) words.
+size_t gft_detsum_index_words(int32_t P, int64_t binning_instances);
+size_t gft_point_list_slots(int64_t binning_instances, int32_t W, int32_t H);    // ids a point_list of that capacity holds (gft_api.hip)
+hipError_t gft_launch_detsum(hipStream_t s, int P, int W, int H, const GeomView& g, const ImgView& im, const BinView& b,
+                             uint32_t cap, const float* rows, int stride, int nv, float* out, int out_stride, bool accumulate,
+                             uint32_t* index);
+// the comparator with the strides as arguments: one workgroup, tile after tile; clears `out` first
+hipError_t gft_launch_detsum_serial(hipStream_t s, int P, int W, int H, const ImgView& im, const BinView& b, uint32_t cap,
+                                    const float* rows, int stride, int nv, float* out, int out_stride);
 hipError_t gft_launch_preprocess_bwd(hipStream_t s, const gft_config& c, const gft_backward_io& io,
                                      const GeomView& g);
 hipError_t gft_launch_grads_rezero(hipStream_t s, const gft_config& c, const gft_backward_io& io);

@@ -15,6 +15,9 @@
 //                  row with one atomic wave instruction (C = 3: three lanes) or two (C = 6: three lanes each) -- either way
 //                  one 64-byte line per entry (atomic lines are what this chip rations)
 //   k_feat_out<C>  the rows, unpadded, into dL_dfeatures [P, C].
+//   k_feat_bwd_det<C>  the same walk, but the reduced row of every (list entry, quadrant) is STORED at the entry's position in
+//                  point_list (rows of FEAT_ROW floats, as RenderBwdArgs.det does for the rasterizer); the rows are then
+//                  added in the one order of include/gftorf_detsum.h (k_detsum.hip): bit-reproducible gradients
 #include "gft_internal.h"
 #include "gft_render_walk.h"
 #include "gftorf_features.h"
@@ -39,7 +42,7 @@ struct FeatArgs {
     int64_t bsc, bsy, bsx;
     float* __restrict__ out;             // forward: [C][H][W]
     const float* __restrict__ g_out;     // backward: [C][H][W]
-    float* __restrict__ acc;             // backward: [P][FEAT_ROW]
+    float* __restrict__ acc;             // backward: [P][FEAT_ROW]; fixed-order backward: the partial rows [list slot][4][FEAT_ROW]
 };
 
 // unit v = 4 tile + quadrant; workgroups are dealt round-robin over the 8 XCDs: every XCD gets a contiguous run of units,
@@ -89,8 +92,8 @@ __device__ __forceinline__ void feat_stage(const float* __restrict__ feat, uint3
     }
 }
 
-// The walk of quadrant v, shared by both directions.
-template <int C, bool BWD>
+// The walk of quadrant v, shared by both directions.  DET (backward only): an entry's sums are stored, not added.
+template <int C, bool BWD, bool DET = false>
 __device__ __forceinline__ void feat_walk(const FeatArgs& a, const int v, const int lane, float4* sA, float4* sF, uint32_t* sId)
 {
     static_assert(C == 3 || C == 6, "feature blend: C is 3 or 6");
@@ -131,8 +134,8 @@ __device__ __forceinline__ void feat_walk(const FeatArgs& a, const int v, const 
             const float4 a0 = a.rec_a[2 * id], a1 = a.rec_a[2 * id + 1];
             sA[2 * lane] = a0;
             sA[2 * lane + 1] = a1;
-            if constexpr (BWD) sId[lane] = id;
-            else feat_stage<C>(a.feat, id, sF, lane);
+            if constexpr (BWD && !DET) sId[lane] = id;
+            else if constexpr (!BWD) feat_stage<C>(a.feat, id, sF, lane);
             reach = gft_splat_reaches_box(a0, a1, box.x, box.y, box.z, box.w);
         }
         uint64_t m = to_sgpr(wave_ballot(reach));
@@ -161,18 +164,28 @@ __device__ __forceinline__ void feat_walk(const FeatArgs& a, const int v, const 
             } else {
                 // 64 pixels -> the C sums of this entry; afterwards lane 16 r holds value r (C = 3) or values 2 r, 2 r + 1
                 // (C = 6): one (C = 3) or two (C = 6) atomic instructions of three lanes add them to the Gaussian's row
-                float* row = a.acc + (size_t)sId[j] * FEAT_ROW;
+                float* row;
+                if constexpr (DET) row = a.acc + ((size_t)(r0 + (uint32_t)(base + j)) * 4 + quad) * FEAT_ROW;
+                else row = a.acc + (size_t)sId[j] * FEAT_ROW;
                 if constexpr (C == 3) {
                     const float t = feat_swap16_add(feat_swap32_add(w * s[0], w * s[2]), feat_swap32_add(w * s[1], 0.f));
                     const float u = feat_row_sum(t);
-                    if ((lane & 15) == 0 && (lane >> 4) < 3) atomicAdd(row + (lane >> 4), u);
+                    if ((lane & 15) == 0 && (lane >> 4) < 3) {
+                        if constexpr (DET) row[lane >> 4] = u;
+                        else atomicAdd(row + (lane >> 4), u);
+                    }
                 } else {
                     const float s0 = feat_swap32_add(w * s[0], w * s[4]), s1 = feat_swap32_add(w * s[1], w * s[5]);
                     const float s2 = feat_swap32_add(w * s[2], 0.f), s3 = feat_swap32_add(w * s[3], 0.f);
                     const float u0 = feat_row_sum(feat_swap16_add(s0, s2)), u1 = feat_row_sum(feat_swap16_add(s1, s3));
                     if ((lane & 15) == 0 && (lane >> 4) < 3) {
-                        atomicAdd(row + 2 * (lane >> 4), u0);
-                        atomicAdd(row + 2 * (lane >> 4) + 1, u1);
+                        if constexpr (DET) {
+                            row[2 * (lane >> 4)] = u0;
+                            row[2 * (lane >> 4) + 1] = u1;
+                        } else {
+                            atomicAdd(row + 2 * (lane >> 4), u0);
+                            atomicAdd(row + 2 * (lane >> 4) + 1, u1);
+                        }
                     }
                 }
             }
@@ -211,6 +224,17 @@ __global__ __launch_bounds__(64) void k_feat_bwd(FeatArgs a)
     const int v = feat_unit((int)blockIdx.x, V);
     if (v >= V) return;
     feat_walk<C, true>(a, v, (int)threadIdx.x, sA, nullptr, sId);
+}
+
+template <int C>
+__global__ __launch_bounds__(64) void k_feat_bwd_det(FeatArgs a)
+{
+    __shared__ float4 sA[RB * 2];
+    if (a.ctrl[GFT_CTRL_TOTAL] > a.cap) return;
+    const int V = 4 * a.T;
+    const int v = feat_unit((int)blockIdx.x, V);
+    if (v >= V) return;
+    feat_walk<C, true, true>(a, v, (int)threadIdx.x, sA, nullptr, nullptr);
 }
 
 template <int C>
@@ -296,5 +320,43 @@ extern "C" int gft_render_features_backward(void* hip_stream, const gft_config* 
     const int blocks = (int)((n + 255) / 256);
     if (C == 3) hipLaunchKernelGGL(k_feat_out<3>, dim3(blocks), dim3(256), 0, s, cfg->P, (const float*)acc, dL_dfeatures);
     else hipLaunchKernelGGL(k_feat_out<6>, dim3(blocks), dim3(256), 0, s, cfg->P, (const float*)acc, dL_dfeatures);
+    return launched(who);
+}
+
+extern "C" size_t gft_feature_partials_bytes(int64_t binning_instances, int32_t W, int32_t H)
+{
+    return gft_point_list_slots(binning_instances, W, H) * 4 * FEAT_ROW * sizeof(float);
+}
+
+extern "C" int gft_render_features_backward_det(void* hip_stream, const gft_config* cfg, const void* geom, const void* img,
+                                                const void* binning, int64_t binning_instances, int32_t C,
+                                                const float* dL_dout, void* index, float* partials, float* dL_dfeatures)
+{
+    const char* who = "gft_render_features_backward_det";
+    FeatArgs a;
+    if (feat_args(a, who, cfg, geom, img, binning, binning_instances, C)) return 1;
+    if (cfg->P == 0) return 0;
+    if (!dL_dout || !dL_dfeatures || (binning_instances > 0 && !partials)) return gft_fail("%s: NULL argument", who);
+    if (((uintptr_t)index & 3u) != 0) return gft_fail("%s: index must be 4-byte aligned", who);
+    if (index && gft_point_list_slots(binning_instances, cfg->W, cfg->H) >= 0xffffffffull)
+        return gft_fail("%s: the frame's id list is too long for the index", who);
+    gft_layout L;
+    gft_compute_layout(cfg->P, cfg->W, cfg->H, binning_instances, &L);
+    const GeomView g = gft_geom_view(const_cast<void*>(geom), L);
+    const ImgView im = gft_img_view(const_cast<void*>(img), L);
+    const BinView b = gft_bin_view(const_cast<void*>(binning), L);
+    a.g_out = dL_dout; a.acc = partials;
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (binning_instances > 0) {
+        // rows of (entry, quadrant) pairs no pixel touched must read as zero
+        const hipError_t e = gft_zero_async(partials, gft_feature_partials_bytes(binning_instances, cfg->W, cfg->H), s);
+        if (e != hipSuccess) return gft_fail("%s: %s", who, hipGetErrorString(e));
+        if (C == 3) hipLaunchKernelGGL(k_feat_bwd_det<3>, dim3(feat_blocks(a)), dim3(64), 0, s, a);
+        else hipLaunchKernelGGL(k_feat_bwd_det<6>, dim3(feat_blocks(a)), dim3(64), 0, s, a);
+    }
+    const hipError_t e = index
+        ? gft_launch_detsum(s, cfg->P, cfg->W, cfg->H, g, im, b, a.cap, partials, FEAT_ROW, C, dL_dfeatures, C, false, (uint32_t*)index)
+        : gft_launch_detsum_serial(s, cfg->P, cfg->W, cfg->H, im, b, a.cap, partials, FEAT_ROW, C, dL_dfeatures, C);
+    if (e != hipSuccess) return gft_fail("%s: %s", who, hipGetErrorString(e));
     return launched(who);
 }

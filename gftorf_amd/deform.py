@@ -24,6 +24,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from . import reproducible as _reproducible
 from ._args import ptr
 
 _D, _W, _SH_DEGREE = 8, 256, 3
@@ -88,6 +89,16 @@ def _choose_route(need_bw, n, capturing, state, rows_work_bytes):
     | "count"     | activations   | dense over n; the rows only counted on the device, the count posted to pinned memory         |
     | "rows"      | x, t only     | ``gft_deform_backward_rows``: the count stays on the device, posted when not capturing       |
 
+    | switch                                | effect on the table                                                                  |
+    |---------------------------------------|--------------------------------------------------------------------------------------|
+    | ``gftorf_amd.reproducible`` mode on   | eagerly "auto" behaves as "capture": "count" / "rows" only under capture or by       |
+    |                                       | ``device_row_count = True``; `_peek_fraction` is never asked                         |
+
+    With the mode on the route is a function of the module switches, the capture state, n, the work buffer's size and
+    ``state["fraction"]`` as the blocking selections left it: whether a posted count has reached pinned memory by now
+    (``Event.query()``) decided between "rows" and "count" -- two splits of the weight-gradient sums, so two summation orders.
+    "capture" is the simplest rule without that question; it costs the blocking read the mode's user accepts.
+
     "dense", "compact" and "recompute" leave rows processed / n in ``state["fraction"]`` (eagerly, n >= _SPARSE_MIN_POINTS); the
     posted counts of "count" and "rows" reach it through `_peek_fraction`.  k = 0 fills the gradients with zeros."""
     if not need_bw:
@@ -98,7 +109,7 @@ def _choose_route(need_bw, n, capturing, state, rows_work_bytes):
         return "rows"
     if capturing:
         return "dense"                                   # nothing may be read back: the activations saved, every row
-    if (device_row_count == "auto" and state is not None
+    if (device_row_count == "auto" and not _reproducible.is_reproducible() and state is not None
             and (rows_work_bytes() if callable(rows_work_bytes) else rows_work_bytes) <= _DEVICE_ROWS_MAX_BYTES):
         _peek_fraction(state)
         frac = state.get("fraction")

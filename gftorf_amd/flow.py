@@ -22,6 +22,7 @@ import math
 import torch
 
 from . import _args, _lib
+from . import reproducible as _reproducible
 from ._args import ptr as _ptr
 
 
@@ -183,7 +184,8 @@ def project_flow(points2d_curr, points3d_curr, flow3d, viewpoint_cam):
 
 class _RenderFlows(torch.autograd.Function):
     """One rasterizer forward with ``colors_precomp = flow_a`` (its image is what that call returns), the second flow blended
-    over the same frame by ``k_feat_fwd<3>``; backward: one ``k_feat_bwd`` over both images (``include/gftorf_features.h``)."""
+    over the same frame by ``k_feat_fwd<3>``; backward: one ``k_feat_bwd`` over both images (``include/gftorf_features.h``) --
+    in the reproducible mode (``gftorf_amd.reproducible``) ``k_feat_bwd_det`` and the fixed-order sum instead."""
 
     @staticmethod
     def forward(ctx, s, means3D, opacities, scales, rotations, flow_a, flow_b):
@@ -222,11 +224,22 @@ class _RenderFlows(torch.autograd.Function):
         g = g.detach().float().contiguous()
         n = int(g.shape[0])
         dev = geom.device
-        acc = torch.empty((cfg.P, 8), device=dev, dtype=torch.float32)
         grad = torch.empty((cfg.P, n), device=dev, dtype=torch.float32)
+        stream_args = (C.byref(cfg), *frame, n, g.data_ptr())
         with _lib.on_device(dev):
-            _lib.check(lib.gft_render_features_backward(_lib.raw_stream(dev), C.byref(cfg), *frame, n, g.data_ptr(),
-                                                        acc.data_ptr(), grad.data_ptr()))
+            if _reproducible.is_reproducible():
+                # the fixed-order backward (read per call: a captured graph keeps the mode it was captured under): every
+                # (entry, quadrant) row is stored and the rows are added in one order (include/gftorf_detsum.h)
+                cap, W, H = frame[3], int(cfg.W), int(cfg.H)
+                partials = torch.empty((lib.gft_feature_partials_bytes(cap, W, H) // 4,), device=dev, dtype=torch.float32)
+                index = None
+                if _reproducible.det_reduce() == "grid":
+                    index = torch.empty((lib.gft_detsum_index_bytes(cfg.P, cap) // 4,), device=dev, dtype=torch.int32)
+                _lib.check(lib.gft_render_features_backward_det(_lib.raw_stream(dev), *stream_args, _ptr(index),
+                                                                partials.data_ptr() if cap else None, grad.data_ptr()))
+            else:
+                acc = torch.empty((cfg.P, 8), device=dev, dtype=torch.float32)
+                _lib.check(lib.gft_render_features_backward(_lib.raw_stream(dev), *stream_args, acc.data_ptr(), grad.data_ptr()))
         if all(want):
             return None, None, None, None, None, grad[:, :3], grad[:, 3:]
         return (None, None, None, None, None) + ((grad, None) if want[0] else (None, grad))

@@ -40,10 +40,26 @@ int gft_render_features(void* hip_stream, const gft_config* cfg, const void* geo
 
 /* dL_dfeatures [P, C] (written in full: zeros for Gaussians no pixel blended) from dL_dout [C, H, W].  acc: scratch of
  * P * 8 floats, any contents (cleared here by a kernel): the sums are added there with float atomics, one 32-byte row per
- * Gaussian, so two runs agree to rounding, not bit for bit. */
+ * Gaussian, in the order the additions arrive: two runs of this call agree to rounding, not bit for bit.  The call below
+ * is the one whose runs agree in every bit. */
 int gft_render_features_backward(void* hip_stream, const gft_config* cfg, const void* geom, const void* img,
                                  const void* binning, int64_t binning_instances, int32_t C, const float* dL_dout, float* acc,
                                  float* dL_dfeatures);
+
+/* The fixed-order backward: the same walk and the same per-(entry, quadrant) sums, produced by the same reduction, but every
+ * sum is stored -- partials[(p * 4 + quadrant) * 8 + c], p the entry's position in the frame's id list -- and the rows are
+ * added in the one order gftorf_detsum.h states.  Same inputs, same bits, however the workgroups were scheduled; the values
+ * agree with the call above to rounding.
+ *   partials: scratch of gft_feature_partials_bytes(binning_instances, W, H) bytes (128 per list slot; host-only size
+ *             function), any contents: cleared here by a kernel (may be NULL when binning_instances is 0);
+ *   index:    scratch of gft_detsum_index_bytes(cfg->P, binning_instances) bytes (gftorf_detsum.h) for the grid-wide sum, or
+ *             NULL for the one-workgroup comparator (same bits, far slower);
+ *   dL_dfeatures [P, C]: written in full, zeros for Gaussians no pixel blended; a frame that did not fit its binning buffer
+ *             leaves it untouched, as above.  P = 0 returns at once.  No host read, no memset: capturable. */
+size_t gft_feature_partials_bytes(int64_t binning_instances, int32_t W, int32_t H);
+int gft_render_features_backward_det(void* hip_stream, const gft_config* cfg, const void* geom, const void* img,
+                                     const void* binning, int64_t binning_instances, int32_t C, const float* dL_dout,
+                                     void* index, float* partials, float* dL_dfeatures);
 
 #ifdef __cplusplus
 }

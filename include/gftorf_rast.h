@@ -221,7 +221,7 @@ typedef struct gft_backward_io {
     float* dL_drotations;   /* [P,4]  required iff scales != NULL */
     float* dL_dphase_offset;/* [1] (written by the library); NULL together with dL_ddc_offset = not wanted (saves a reduction launch) */
     float* dL_ddc_offset;   /* [1] */
-    /* optional: deterministic reduction (tests).  A buffer of gft_det_partials_bytes(binning_instances) bytes: every
+    /* optional: deterministic reduction (the fixed-order mode).  A buffer of gft_det_partials_bytes(binning_instances) bytes: every
      * (list entry, pixel quadrant) then stores its 16-float partial row there instead of adding it with float atomics,
      * and one workgroup adds the rows tile by tile, entries in list order, quadrants 0..3: two runs give bit-identical
      * gradients (the reference's atomicAdd sums, backward.cu:795-886, have no defined order).  NULL = float atomics. */
@@ -409,7 +409,8 @@ int gft_forward_enqueue(void* hip_stream, const gft_config* cfg, const gft_forwa
 /* The backward of the forward whose scratch buffers `io` carries.  Gradient sums are added with float atomics
  * (as in the reference), so two runs agree to rounding, not bit for bit.  GFT_BWD_SPLIT=0 in the environment
  * keeps one wave per pixel quadrant (default: deep quadrants are walked by up to eight waves).
- * With io->det_partials the sums are formed in a fixed order instead (bit-reproducible, slower: a test mode). */
+ * With io->det_partials the sums are formed in a fixed order instead (bit-reproducible; gftorf_detsum.h states the order
+ * and gft_backward_det adds the rows across the chip instead of in one workgroup). */
 int gft_backward(void* hip_stream, const gft_config* cfg,
                  const gft_backward_io* io, int64_t binning_instances);
 
