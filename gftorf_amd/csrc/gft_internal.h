@@ -48,7 +48,7 @@ struct ImgView {
     uint32_t* tile_max;   // [T][4] deepest contributor per 8x8 quadrant
     uint32_t* ctrl;       // [GFT_CTRL_WORDS], directly followed by tile_cnt, tile_cut, super_tab (cleared together by k_preprocess_fwd)
     uint32_t* tile_cnt;   // [T]  instances per tile
-    uint32_t* tile_cut;   // [T]  tile-pull binning: last depth bin inside the sorted head; GFT_NO_TAIL when the head is the whole list
+    uint32_t* tile_cut;   // [T]  tile-pull binning: first depth bin behind the sorted head; GFT_NO_TAIL when the head is the whole list
     uint32_t* super_tab;  // [4][GFT_SUPER_CELLS] tile-pull binning: per (copy, supertile, depth slab) entry counters and scatter cursors; per (supertile, slab) entry count and list start
     uint32_t* tile_cursor;// [T]
     uint32_t* tile_order; // [T] tiles by backward weight, heaviest first

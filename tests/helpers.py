@@ -834,3 +834,60 @@ def row_errors(ref, got, rows):
         own = float(np.abs(r[~named]).max())
         out[("ordinary", k)] = (float(np.abs(q[~named] - r[~named]).max()), own, own)
     return out
+
+
+# Frames whose tile grid takes tile-pull binning's other paths (tests/pull_ref.py: supertiles of 4 x 4 .. 16 x 16 tiles, depth
+# slabs, the staged scatter): frame_scene's 200 rows -- the giant reaches every tile, so every supertile has an entry, the last
+# partial one included -- and a dense cluster on the image centre, which at 1025 x 1025 is the corner shared by four 4 x 4
+# supertiles.  Under the planes 0.45 / 6.05 a depth bin is 2^13 float steps and a slab of 1024 bins one octave of depth: the
+# cluster's z range chooses the slabs.  name -> (W, H, cluster); cluster: small_scene's P, spread, z_lo, z_hi.
+# What each scene reaches is asserted on the oracle in tests/test_pull_ref.py.
+BIG_GRIDS = {
+    "all": (1025, 1025, dict(P=20000, spread=0.05, z_lo=0.46, z_hi=5.5)),
+    "near": (1025, 1025, dict(P=12000, spread=0.06, z_lo=0.46, z_hi=1.6)),
+    "mid": (1025, 1025, dict(P=12000, spread=0.06, z_lo=2.0, z_hi=3.4)),
+    "far": (1025, 1025, dict(P=12000, spread=0.06, z_lo=3.7, z_hi=5.5)),
+    "row": (32784, 16, dict(P=20000, spread=0.004, z_lo=0.46, z_hi=5.5)),
+    "col": (16, 32784, dict(P=20000, spread=0.004, z_lo=0.46, z_hi=5.5)),
+    "s8": (65552, 16, dict(P=20000, spread=0.002, z_lo=0.46, z_hi=5.5)),
+    "s16": (131088, 16, dict(P=20000, spread=0.001, z_lo=0.46, z_hi=5.5)),
+    # (P = 20000 as in "all" puts one pixel of one Gaussian on the blend's alpha threshold: the device blends it, the oracle does
+    # not, in both binning modes, and dL/dscales is off by 3.5e-4 of its max-norm -- no yardstick for a bound of 3e-4)
+    "edge": (1024, 1024, dict(P=18000, spread=0.05, z_lo=0.46, z_hi=5.5)),
+    "fallback": (262160, 16, dict(P=5000, spread=0.001, z_lo=0.46, z_hi=5.5)),
+}
+BIG_GRID_LOW_OPACITY = ("all", "row")       # also drawn with every opacity 0.05: nothing saturates, every tile with a tail flags
+_BIG_GRID = {}
+
+
+def big_grid_scene(W, H, cluster, opacity=None):
+    """frame_scene(W, H) and a cluster small_scene(scale_lo=0.004, scale_hi=0.03, **cluster), rows concatenated, one camera.
+    opacity: every row's opacity."""
+    sc = frame_scene(W, H)
+    cl = small_scene(W=W, H=H, seed=23, scale_lo=0.004, scale_hi=0.03, **cluster)
+    assert all(np.array_equal(sc["cam"][k], cl["cam"][k]) for k in ("viewmatrix", "projmatrix"))
+    g = {k: np.concatenate([v, cl["gaussians"][k]]) for k, v in sc["gaussians"].items()}
+    if opacity is not None:
+        g["opacities"] = np.full_like(g["opacities"], opacity)
+    return dict(sc, cfg=dict(sc["cfg"], P=g["means3D"].shape[0]), gaussians=g)
+
+
+def big_grid(name):
+    """The scene of BIG_GRIDS[name], or of "name@opacity".  Built once; nobody writes to it."""
+    if name not in _BIG_GRID:
+        base, _, op = name.partition("@")
+        W, H, cluster = BIG_GRIDS[base]
+        _BIG_GRID[name] = big_grid_scene(W, H, cluster, opacity=float(op) if op else None)
+    return _BIG_GRID[name]
+
+
+def big_grid_reference(oracle, name, backward=False):
+    """(scene, the oracle's forward, its backward or None) of big_grid(name).  Computed once; nobody writes to it."""
+    sc = big_grid(name)
+    if ("f", name) not in _BIG_GRID:
+        _BIG_GRID[("f", name)] = run_oracle(oracle, sc, backward=False)[0]
+    f = _BIG_GRID[("f", name)]
+    if backward and ("b", name) not in _BIG_GRID:
+        gr = sc["grads"]
+        _BIG_GRID[("b", name)] = oracle.backward(f, gr["color"], gr["phasor"], gr["depth"], gr["acc"], gr["depth_distortion"])
+    return sc, f, _BIG_GRID.get(("b", name))

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import helpers as Hh
+import pull_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -183,22 +184,33 @@ def test_preprocess_and_binning_bit_exact(name, mode, oracle, gpu):
     check_preprocess_and_binning_bit_exact(Hh.small_scene(**SCENES[name]), mode, oracle, gpu)
 
 
-def check_preprocess_and_binning_bit_exact(scene, mode, oracle, gpu):
+def check_preprocess_and_binning_bit_exact(scene, mode, oracle, gpu, f=None):
     """test_preprocess_and_binning_bit_exact's measure on any scene (tests/test_gpu_hostile.py runs it on degenerate Gaussians
-    and on extreme frame shapes)."""
-    f, _ = Hh.run_oracle(oracle, scene, backward=False)
+    and on extreme frame shapes, tests/test_gpu_big_grids.py on tile grids with depth slabs).  f: the oracle's forward of the
+    scene, where the caller has it.
+
+    Tile-pull binning's bookkeeping is held to tests/pull_ref.py's model of k_tile_pull, which follows the supertile shape and
+    the slab count the library uses (GFT_SLABS included): tile_cnt, front_len and tile_cut of EVERY tile, exactly.  k_tail_build
+    reads tile_cut and never writes it (it moves `ranges` to the pool), so the cut's value is compared on flagged tiles too."""
+    if f is None:
+        f, _ = Hh.run_oracle(oracle, scene, backward=False)
     st = raw_forward(scene, gpu, mode=mode)
     og = f.geom
     vis = og["radii"] > 0
     pull = st["pull"]
-    assert pull == (mode == 1 and st["lazy"])
+    shape = pull_ref.super_shape(scene["cfg"]["W"], scene["cfg"]["H"])
+    assert pull == (mode == 1 and st["lazy"] and pull_ref.tile_pull_ok(shape))
     # integer decisions
     np.testing.assert_array_equal(st["radii"], og["radii"])
     np.testing.assert_array_equal(st["tiles"], og["tiles_touched"])
     assert st["R"] == f.num_rendered == int(st["ctrl"][0])
     lens = f.ranges[:, 1] - f.ranges[:, 0]
-    if os.environ.get("GFT_SLABS", "1") in ("", "0", "1"):
-        np.testing.assert_array_equal(st["tile_cnt"], lens)      # (small frames: one depth slab, every tile scans its whole list)
+    model = pull_ref.head_model_of(f, scene, shape) if pull else None
+    # (one depth slab, and whole-frame binning: every tile counts its whole list; with several slabs a tile stops at the one
+    # that covers its head)
+    np.testing.assert_array_equal(st["tile_cnt"], model.tile_cnt if pull else lens)
+    if pull and shape.K == 1:
+        np.testing.assert_array_equal(st["tile_cnt"], lens)
     if not pull:
         assert int(st["ctrl"][2]) == int(lens.max())
     W, H = scene["cfg"]["W"], scene["cfg"]["H"]
@@ -240,18 +252,20 @@ def check_preprocess_and_binning_bit_exact(scene, mode, oracle, gpu):
             k = int(st["front_len"][t])
             r0, r1 = int(st["ranges"][t, 0]), int(st["ranges"][t, 1])
             assert k <= b - a and k <= 2048
-            assert (int(st["tile_cut"][t]) == 0xffffffff) == (k == b - a), "tile %d" % t
-            one_slab = os.environ.get("GFT_SLABS", "1") in ("", "0", "1")      # (small frames: one depth slab unless forced)
-            if b - a <= 2048 and one_slab:
+            # the head: the scanned hits when there are at most 2048, else whole bins up to the one where the count reaches
+            # 940; a bin that overshoots 1024 is left out unless the head would be shorter than 512 (pull_ref.head_model)
+            assert k == int(model.front_len[t]), "head length of tile %d: %d, model %d" % (t, k, int(model.front_len[t]))
+            tail = bool(model.has_tail[t])          # a part of the list behind the head, or a later slab of the supertile with entries
+            assert (int(st["tile_cut"][t]) == 0xffffffff) == (not tail), "tile %d" % t
+            assert int(st["tile_cut"][t]) == int(model.cut[t]), "cut of tile %d: %d, model %d" % (t, int(st["tile_cut"][t]), int(model.cut[t]))
+            if not tail or shape.K == 1:
+                assert (k == b - a) == (not tail), "tile %d" % t
+            if b - a <= 2048 and shape.K == 1:
                 assert k == b - a       # the tile has seen its whole list (with several slabs it stops at the one that covers the head)
-            elif k < b - a:
-                # whole bins up to the one where the count reaches 940; a bin that overshoots 1024 is left out unless
-                # the head would be shorter than 512
-                assert k <= 1024 or k <= 2048
             got = pl[r0:r1]
             listed[got] = True
             np.testing.assert_array_equal(got[:k], ref[:k], err_msg="head of tile %d" % t)
-            if st["unit_flag"][t].any() and k < b - a:
+            if st["unit_flag"][t].any() and tail:
                 assert r0 >= lens.size * 2048, "a completed list lives in the pool"
                 assert is_subsequence(got[k:], ref[k:]), "culled tail of tile %d" % t
             else:
@@ -731,7 +745,14 @@ def test_tile_pull_matches_whole_frame_binning(name, oracle, gpu):
     from gftorf_amd import _lib, api
     if not _lib.load().gft_lazy_sort():
         pytest.skip("GFT_LAZY_SORT=0: whole-frame binning only")
-    scene = Hh.small_scene(seed=23, **BIN_CASES[name])
+    check_tile_pull_matches_whole_frame_binning(Hh.small_scene(seed=23, **BIN_CASES[name]), oracle, gpu,
+                                                rtol=3e-5 if name.startswith("big_grid") else 1e-5)
+
+
+def check_tile_pull_matches_whole_frame_binning(scene, oracle, gpu, rtol=1e-5, reference=None):
+    """test_tile_pull_matches_whole_frame_binning's measure on any scene.  rtol: the gradients' bound between the two modes;
+    reference: the oracle's (forward, backward) of the scene, where the caller has them."""
+    from gftorf_amd import api
     # (one wave per quadrant in both: the segment-parallel forward cuts a list by its length, and the sorted heads of the
     # two binning modes differ in length -- the sums would agree to rounding, not bit for bit)
     with render_mode(0):
@@ -749,8 +770,8 @@ def test_tile_pull_matches_whole_frame_binning(name, oracle, gpu):
             for k in ref_grads:
                 if ref_grads[k] is not None:
                     # (sums in another order of the atomics: the 1080p cases' rotation rows were seen at 1.4e-5)
-                    Hh.assert_close(k, ref_grads[k], grads[k], rtol_max=3e-5 if name.startswith("big_grid") else 1e-5)
-    f, b = Hh.run_oracle(oracle, scene)
+                    Hh.assert_close(k, ref_grads[k], grads[k], rtol_max=rtol)
+    f, b = reference if reference is not None else Hh.run_oracle(oracle, scene)
     check_outputs(f, ref_out)
     check_grads(b, grads, scene)
 
@@ -795,40 +816,11 @@ def test_hinted_tiles_sort_their_whole_list(gpu, oracle):
     with render_mode(0):
         fog = Hh.small_scene(seed=21, P=40000, W=64, H=64, scale_lo=0.01, scale_hi=0.05, opacity=0.02)
         f, _ = Hh.run_oracle(oracle, fog, backward=False)
-        lens = (f.ranges[:, 1] - f.ranges[:, 0]).astype(np.int64)
-        T = lens.size
-        long_tiles = lens > 2048
-        assert long_tiles.any()
-        # no schedule yet (all zero): the lazy route, and the words it leaves say "every long tile walked past its head"
-        h = torch.zeros((T,), device=gpu, dtype=torch.int32)
-        st0 = raw_forward(fog, gpu, mode=1, hints=h)
-        assert st0["pull"] and st0["unit_flag"].any(1)[long_tiles].all()
-        assert (st0["hints"][long_tiles] != 0).all() and not st0["hints"][~long_tiles].any()
-        # with that schedule
-        st = raw_forward(fog, gpu, mode=1, hints=h)
-        assert not st["unit_flag"].any() and int(st["ctrl"][4]) == 0                   # nobody flags
-        assert (st["tile_cut"][long_tiles] == 0xffffffff).all()
-        np.testing.assert_array_equal(st["front_len"], lens)                           # every list complete after the pull kernel
-        assert (st["ranges"][long_tiles, 0] >= T * 2048).all()                         # whole lists live in the pool
-        assert int(st["ctrl"][6]) == int(lens[long_tiles].sum())                       # pool slots taken = the whole lists
-        for t in range(T):
-            a, e = int(st["ranges"][t, 0]), int(st["ranges"][t, 1])
-            np.testing.assert_array_equal(st["point_list"][a:e], f.point_list[int(f.ranges[t, 0]):int(f.ranges[t, 1])], err_msg="tile %d" % t)
-        assert (st["hints"][long_tiles] != 0).any(1).all()                             # still nothing saturates: the schedule stays
-        np.testing.assert_array_equal(st["planes"], st0["planes"])
-        np.testing.assert_array_equal(st["pixels"], st0["pixels"])
+        h = check_scheduled_tiles_sort_their_whole_list(fog, f, gpu)
         # a frame that saturates early under the same (now wrong) schedule: whole lists all the same, and the words go back to 0
         opaque = Hh.small_scene(seed=21, P=30000, W=64, H=64, scale_lo=0.02, scale_hi=0.1, opacity=0.9)
         fo, _ = Hh.run_oracle(oracle, opaque, backward=False)
-        lo = (fo.ranges[:, 1] - fo.ranges[:, 0]).astype(np.int64)
-        assert (lo > 2048).any()
-        h.fill_(0x01010101)
-        so = raw_forward(opaque, gpu, mode=1, hints=h)
-        np.testing.assert_array_equal(so["front_len"], lo)
-        assert not so["hints"].any() and not so["unit_flag"].any()
-        ref = raw_forward(opaque, gpu, mode=1)
-        np.testing.assert_array_equal(so["planes"], ref["planes"])
-        np.testing.assert_array_equal(so["pixels"], ref["pixels"])
+        check_all_ones_schedule_sorts_whole_lists(opaque, fo, gpu, saturates=True)
         # a single depth bin with more keys than the bin counts carry (bytes): the hinted tile takes the lazy route
         flat = Hh.small_scene(seed=23, **SCENES["long_lists_flat"])
         h2 = torch.full((4,), 0x01010101, device=gpu, dtype=torch.int32)
@@ -836,6 +828,59 @@ def test_hinted_tiles_sort_their_whole_list(gpu, oracle):
         ref = raw_forward(flat, gpu, mode=1)
         np.testing.assert_array_equal(sf["front_len"], ref["front_len"])
         np.testing.assert_array_equal(sf["planes"], ref["planes"])
+
+
+def check_scheduled_tiles_sort_their_whole_list(fog, f, gpu):
+    """The first part of test_hinted_tiles_sort_their_whole_list's measure, on any frame where nothing saturates (f: the
+    oracle's forward of it; under render_mode(0)): without a schedule every tile with a tail flags and marks itself; with that
+    schedule every list is sorted whole by the pull kernel.  Returns the schedule's tensor.  A tile has a tail when its list is
+    longer than one placement -- and, on a grid with depth slabs, when its head stops in front of a slab that holds entries of
+    its supertile (pull_ref.head_model; with one slab these are the lists above 2048)."""
+    lens = (f.ranges[:, 1] - f.ranges[:, 0]).astype(np.int64)
+    T = lens.size
+    long_tiles = lens > 2048
+    assert long_tiles.any()
+    tails = pull_ref.head_model_of(f, fog).has_tail
+    assert (tails[long_tiles]).all()
+    if pull_ref.super_shape(fog["cfg"]["W"], fog["cfg"]["H"]).K == 1:
+        np.testing.assert_array_equal(tails, long_tiles)
+    # no schedule yet (all zero): the lazy route, and the words it leaves say "every long tile walked past its head"
+    h = torch.zeros((T,), device=gpu, dtype=torch.int32)
+    st0 = raw_forward(fog, gpu, mode=1, hints=h)
+    assert st0["pull"] and st0["unit_flag"].any(1)[tails].all()
+    assert (st0["hints"][tails] != 0).all() and not st0["hints"][~tails].any()
+    # with that schedule
+    st = raw_forward(fog, gpu, mode=1, hints=h)
+    assert not st["unit_flag"].any() and int(st["ctrl"][4]) == 0                   # nobody flags
+    assert (st["tile_cut"][tails] == 0xffffffff).all()
+    np.testing.assert_array_equal(st["front_len"], lens)                           # every list complete after the pull kernel
+    assert (st["ranges"][long_tiles, 0] >= T * 2048).all()                         # whole lists live in the pool
+    assert int(st["ctrl"][6]) == int(lens[long_tiles].sum())                       # pool slots taken = the whole lists
+    for t in range(T):
+        a, e = int(st["ranges"][t, 0]), int(st["ranges"][t, 1])
+        np.testing.assert_array_equal(st["point_list"][a:e], f.point_list[int(f.ranges[t, 0]):int(f.ranges[t, 1])], err_msg="tile %d" % t)
+    assert (st["hints"][tails] != 0).any(1).all()                                  # still nothing saturates: the schedule stays
+    np.testing.assert_array_equal(st["planes"], st0["planes"])
+    np.testing.assert_array_equal(st["pixels"], st0["pixels"])
+    return h
+
+
+def check_all_ones_schedule_sorts_whole_lists(scene, f, gpu, saturates):
+    """The second part of that measure, on any frame (under render_mode(0)): under a schedule that marks every tile, every list is
+    sorted whole, nobody flags, and the images are those of the frame without a schedule bit for bit.  saturates: every
+    quadrant saturates inside a normal head -- the words then go back to 0."""
+    lo = (f.ranges[:, 1] - f.ranges[:, 0]).astype(np.int64)
+    assert (lo > 2048).any()
+    h = torch.full((lo.size,), 0x01010101, device=gpu, dtype=torch.int32)
+    so = raw_forward(scene, gpu, mode=1, hints=h)
+    np.testing.assert_array_equal(so["front_len"], lo)
+    assert not so["unit_flag"].any()
+    if saturates:
+        assert not so["hints"].any()
+    ref = raw_forward(scene, gpu, mode=1)
+    np.testing.assert_array_equal(so["planes"], ref["planes"])
+    np.testing.assert_array_equal(so["pixels"], ref["pixels"])
+    return so
 
 
 @pytest.mark.parametrize("name", list(BIN_CASES))
@@ -847,7 +892,14 @@ def test_tile_hints_do_not_change_results(name, oracle, gpu):
     from gftorf_amd import _lib, api
     if not _lib.load().gft_lazy_sort():
         pytest.skip("GFT_LAZY_SORT=0: whole-frame binning only")
-    scene = Hh.small_scene(seed=23, **BIN_CASES[name])
+    check_tile_hints_do_not_change_results(Hh.small_scene(seed=23, **BIN_CASES[name]), oracle, gpu,
+                                           rtol=3e-5 if name.startswith("big_grid") else 1e-5)
+
+
+def check_tile_hints_do_not_change_results(scene, oracle, gpu, rtol=1e-5, reference=None):
+    """test_tile_hints_do_not_change_results's measure on any scene.  rtol: the gradients' bound between schedules; reference:
+    the oracle's (forward, backward) of the scene, where the caller has them."""
+    from gftorf_amd import api
     rng = np.random.default_rng(5)
     with render_mode(0):
         keep = api._TILE_HINTS
@@ -904,10 +956,10 @@ def test_tile_hints_do_not_change_results(name, oracle, gpu):
                 if ref_grads[k] is not None:
                     # (the same terms in another order of the atomics: 1e-5 of the max-norm on the small frames; the 1080p
                     # cases' rotation rows -- long sums that cancel -- were seen at 1.4e-5)
-                    Hh.assert_close(k, ref_grads[k], grads[k], rtol_max=3e-5 if name.startswith("big_grid") else 1e-5)
+                    Hh.assert_close(k, ref_grads[k], grads[k], rtol_max=rtol)
     api._force_whole_lists = None
     api._force_cell_sched = None
-    f, b = Hh.run_oracle(oracle, scene)
+    f, b = reference if reference is not None else Hh.run_oracle(oracle, scene)
     check_outputs(f, out)
     check_grads(b, grads, scene)
 
