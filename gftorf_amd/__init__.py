@@ -18,6 +18,7 @@ from . import densify  # noqa: F401
 from . import loss  # noqa: F401
 from . import flow  # noqa: F401
 from . import reg  # noqa: F401
+from . import rigid  # noqa: F401
 from . import tof  # noqa: F401
 from . import query  # noqa: F401
 from . import metrics  # noqa: F401
@@ -30,8 +31,10 @@ from . import schedule  # noqa: F401
 from .query import DeformQuery, ftorf_schedule, query_dmlp  # noqa: F401
 from .views import DrawOrder, ViewStore, select_plane  # noqa: F401
 from .schedule import RunSchedule  # noqa: F401
+from .rigid import Neighbours, find_knn, isometry_loss, rigid_terms, rigidity_loss  # noqa: F401
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "GaussianRasterizerPair", "render_pair", "assemble_inputs", "assemble_parameters", "distCUDA2", "FusedAdam", "clip_grad_norm_",
            "DeformNetwork", "REFERENCE_ARCH", "reference_network", "densify",
            "DeformQuery", "ftorf_schedule", "query_dmlp", "views", "ViewStore", "DrawOrder", "select_plane", "schedule", "RunSchedule",
-           "reproducible", "set_reproducible", "is_reproducible"]
+           "reproducible", "set_reproducible", "is_reproducible",
+           "rigid", "Neighbours", "find_knn", "rigidity_loss", "isometry_loss", "rigid_terms"]

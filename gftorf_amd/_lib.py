@@ -163,6 +163,10 @@ DETSUM_EXPORTS = ["gft_detsum_index_bytes", "gft_backward_det"]
 REG_EXPORTS = ["gft_reg_blocks", "gft_reg_result_words", "gft_reg_forward", "gft_reg_backward"]
 REG_PARTIAL_WORDS = 8           # GFT_REG_PARTIAL_WORDS
 REG_MEANS, REG_COUNTS, REG_RECIPS, REG_TOTAL = 0, 4, 6, 10      # GFT_REG_*: words of the result block
+# include/gftorf_rigid.h (exact K-NN, the rigidity and isometry priors; no struct, so the ABI version is unchanged)
+RIGID_EXPORTS = ["gft_rigid_knn_scratch_bytes", "gft_rigid_knn", "gft_rigid_blocks", "gft_rigid_result_words", "gft_rigid_forward",
+                 "gft_rigid_backward"]
+RIGID_MAX_K, RIGID_PARTIAL_WORDS, RIGID_MEANS, RIGID_TOTAL = 32, 2, 0, 2           # GFT_RIGID_*
 # include/gftorf_tof.h (the ToF depth and the training log's scalars; no struct, so the ABI version is unchanged)
 TOF_EXPORTS = ["gft_tof_depth", "gft_tof_log_blocks", "gft_tof_log_row"]
 TOF_PARTIAL_WORDS = 12          # GFT_TOF_PARTIAL_WORDS
@@ -385,6 +389,21 @@ def load():
     lib.gft_reg_forward.argtypes = _reg_inputs + [C.c_void_p] + _reg_weights + [C.c_void_p, C.c_void_p]
     lib.gft_reg_backward.restype = C.c_int
     lib.gft_reg_backward.argtypes = _reg_inputs + _reg_weights + [C.c_void_p] * 6
+    lib.gft_rigid_knn_scratch_bytes.restype = C.c_size_t
+    lib.gft_rigid_knn_scratch_bytes.argtypes = [C.c_int32]
+    # stream, P, K, points, idx, dist2, scratch
+    lib.gft_rigid_knn.restype = C.c_int
+    lib.gft_rigid_knn.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.gft_rigid_blocks.restype = C.c_int64
+    lib.gft_rigid_blocks.argtypes = [C.c_int64, C.c_int32]
+    lib.gft_rigid_result_words.restype = C.c_int64
+    lib.gft_rigid_result_words.argtypes = []
+    # stream, P, K, idx, w, prev, curr, d0, weights_dev, w_rigid, w_iso, partials, result
+    lib.gft_rigid_forward.restype = C.c_int
+    lib.gft_rigid_forward.argtypes = [C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 6 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p]
+    # stream, P, K, idx, offsets, edges, w, prev, curr, d0, weights_dev, w_rigid, w_iso, g_loss, g_curr, g_prev
+    lib.gft_rigid_backward.restype = C.c_int
+    lib.gft_rigid_backward.argtypes = [C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 8 + [C.c_float, C.c_float] + [C.c_void_p] * 3
     # stream, pixels, tof, plane_stride, depth_range_dev, depth_range, phase_offset_dev, phase_offset, out
     lib.gft_tof_depth.restype = C.c_int
     lib.gft_tof_depth.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_float, C.c_void_p]

@@ -17,8 +17,11 @@
 //   k_knn_search  : one workgroup per 256 consecutive (spatially close) points: the box table is
 //                   walked once per workgroup, a box that any lane still needs is staged in LDS
 //                   (12 KB) and scanned with broadcast reads
+//   k_knn_search_k: the same walk with the K <= 32 nearest neighbours kept, indices and squared
+//                   distances (include/gftorf_rigid.h: gft_rigid_knn)
 #include "gft_internal.h"
 #include "gftorf_knn.h"
+#include "gftorf_rigid.h"
 
 #include <cfloat>
 
@@ -346,6 +349,148 @@ __global__ __launch_bounds__(KNN_BLOCK) void k_knn_search(int P, const float* __
     if (in) out[order[j]] = (best[0] + best[1] + best[2]) / 3.0f;
 }
 
+// ---- the K nearest neighbours themselves (include/gftorf_rigid.h: gft_rigid_knn) ------------------
+// A lane keeps its K best (squared distance, original index) pairs in KP registers each, ascending by (distance, index).
+// KP is 8, 16 or 32; the KP - K slots in front hold a pair smaller than any candidate, which never moves, so the K-th
+// best is slot KP - 1 and every list index is a compile-time constant (no scratch).  keep3's carry walk, on pairs.
+template <int KP>
+__device__ __forceinline__ void keepk(float dist, int id, float (&bd)[KP], int (&bi)[KP])
+{
+#pragma unroll
+    for (int j = 0; j < KP; j++) {
+        if (bd[j] > dist || (bd[j] == dist && bi[j] > id)) {
+            const float t = bd[j];
+            const int u = bi[j];
+            bd[j] = dist; bi[j] = id;
+            dist = t; id = u;
+        }
+    }
+}
+
+template <int KP>
+__device__ __forceinline__ void knn_list_reset(int K, float (&bd)[KP], int (&bi)[KP])
+{
+#pragma unroll
+    for (int j = 0; j < KP; j++) {
+        const bool pad = j < KP - K;
+        bd[j] = pad ? -1.0f : FLT_MAX;          // a squared distance is never negative
+        bi[j] = pad ? -1 : 0x7fffffff;
+    }
+}
+
+// as k_knn_search: one workgroup per 256 consecutive placed points, the box table walked once per workgroup.  A box is
+// skipped only when its distance to the query exceeds the K-th best so far (or the first bound): a box AT that distance
+// may still hold an equally distant point of a smaller index.
+template <int KP>
+__global__ __launch_bounds__(KNN_BLOCK) void k_knn_search_k(int P, int K, const float* __restrict__ placed,
+                                                            const uint32_t* __restrict__ order,
+                                                            const Bounds* __restrict__ boxes, int32_t* __restrict__ out_idx,
+                                                            float* __restrict__ out_dist2)
+{
+    __shared__ float s_pts[KNN_BOX * 3];
+    __shared__ int s_id[KNN_BOX];
+    __shared__ uint32_t s_any;
+    const int tid = threadIdx.x;
+    const int j = blockIdx.x * KNN_BLOCK + tid;
+    const bool in = j < P;
+    float px = 0.f, py = 0.f, pz = 0.f;
+    if (in) { px = placed[3 * (size_t)j]; py = placed[3 * (size_t)j + 1]; pz = placed[3 * (size_t)j + 2]; }
+    float bd[KP];
+    int bi[KP];
+    knn_list_reset<KP>(K, bd, bi);
+    // first bound from the +-K neighbours along the placement order: P > K, so the window holds at least K other points
+    if (in) {
+        const int lo = max(0, j - K), hi = min(P - 1, j + K);
+        for (int i = lo; i <= hi; i++) {
+            if (i == j) continue;
+            const float dx = placed[3 * (size_t)i] - px, dy = placed[3 * (size_t)i + 1] - py, dz = placed[3 * (size_t)i + 2] - pz;
+            const float dist = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+            if (dist < bd[KP - 1]) keepk<KP>(dist, i, bd, bi);     // (the ids of this pass are never read)
+        }
+    }
+    const float reject = bd[KP - 1];
+    knn_list_reset<KP>(K, bd, bi);
+    const int nboxes = (P + KNN_BOX - 1) / KNN_BOX;
+    for (int b = 0; b < nboxes; b++) {
+        bool want = false;
+        if (in) {
+            const float d = box_point_dist2(boxes[b], px, py, pz);
+            want = !(d > reject || d > bd[KP - 1]);
+        }
+        if (tid == 0) s_any = 0;
+        __syncthreads();
+        if (want) s_any = 1;                                     // benign race: every writer stores 1
+        __syncthreads();
+        if (s_any) {                                             // uniform per workgroup
+            const int first = b * KNN_BOX, cnt = min(KNN_BOX, P - first);
+            for (int k = tid; k < cnt * 3; k += KNN_BLOCK) s_pts[k] = placed[3 * (size_t)first + k];
+            for (int k = tid; k < cnt; k += KNN_BLOCK) s_id[k] = (int)order[first + k];
+            __syncthreads();
+            if (want) {
+                for (int k = 0; k < cnt; k++) {
+                    if (first + k == j) continue;                // self, by index
+                    // keep3's expression, bit for bit
+                    const float dx = s_pts[3 * k] - px, dy = s_pts[3 * k + 1] - py, dz = s_pts[3 * k + 2] - pz;
+                    const float dist = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+                    const int id = s_id[k];
+                    // (dist <= reject: the first bound already holds K other points; without it a lane inserts whatever
+                    // the first boxes hold, and an insertion by one lane costs the whole wave its KP steps)
+                    if (dist <= reject && (dist < bd[KP - 1] || (dist == bd[KP - 1] && id < bi[KP - 1]))) keepk<KP>(dist, id, bd, bi);
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (in) {
+        const size_t row = (size_t)order[j] * (size_t)K;
+#pragma unroll
+        for (int k = 0; k < KP; k++) {
+            const int c = k - (KP - K);
+            if (c >= 0) { out_idx[row + c] = bi[k]; out_dist2[row + c] = bd[k]; }
+        }
+    }
+}
+
+// the scratch of a call, and the kernels up to the box table
+struct KnnScratch {
+    uint32_t *codes, *order, *tk, *tv, *hist, *ticket;
+    float* placed;
+    Bounds *boxes, *partial, *bounds;
+};
+
+KnnScratch knn_scratch(int32_t P, void* scratch)
+{
+    const size_t p = (size_t)P;
+    const size_t nboxes = (p + KNN_BOX - 1) / KNN_BOX;
+    const size_t nrs = (p + RS_CHUNK - 1) / RS_CHUNK;
+    KnnScratch v;
+    char* b = (char*)scratch;
+    v.codes = (uint32_t*)b;               b += p * 4;
+    v.order = (uint32_t*)b;               b += p * 4;
+    v.tk = (uint32_t*)b;                  b += p * 4;
+    v.tv = (uint32_t*)b;                  b += p * 4;
+    v.placed = (float*)b;                 b += p * 12;
+    b = (char*)(((uintptr_t)b + 255) & ~(uintptr_t)255);
+    v.boxes = (Bounds*)b;                 b += nboxes * sizeof(Bounds);
+    v.hist = (uint32_t*)b;                b += 256 * nrs * 4;
+    v.partial = (Bounds*)b;               b += 256 * sizeof(Bounds);
+    v.bounds = (Bounds*)b;                b += sizeof(Bounds);
+    v.ticket = (uint32_t*)b;
+    return v;
+}
+
+int knn_place(hipStream_t s, int32_t P, const float* points, const KnnScratch& v, const char* who)
+{
+    GFT_CHECK_HIP(gft_zero_async(v.ticket, 4, s));
+    const int blocks = (P + KNN_BLOCK - 1) / KNN_BLOCK, nboxes = (P + KNN_BOX - 1) / KNN_BOX;
+    hipLaunchKernelGGL(k_knn_bounds, dim3(blocks < 256 ? blocks : 256), dim3(KNN_BLOCK), 0, s, P, points, v.partial, v.ticket, v.bounds);
+    hipLaunchKernelGGL(k_knn_codes, dim3(blocks), dim3(KNN_BLOCK), 0, s, P, points, v.bounds, v.codes, v.order);
+    const hipError_t e = radix_sort_pairs(s, P, v.codes, v.order, v.tk, v.tv, v.hist, 30);
+    if (e != hipSuccess) return gft_fail("%s: sort: %s", who, hipGetErrorString(e));
+    hipLaunchKernelGGL(k_knn_boxes, dim3(nboxes), dim3(KNN_BOX), 0, s, P, points, v.order, v.placed, v.boxes);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" size_t gft_knn_scratch_bytes(int32_t P)
@@ -364,30 +509,26 @@ extern "C" int gft_knn_mean_dist2(void* hip_stream, int32_t P, const float* poin
     if (P == 0) return 0;
     if (!points || !mean_dist2 || !scratch) return gft_fail("gft_knn_mean_dist2: NULL pointer");
     hipStream_t s = (hipStream_t)hip_stream;
-    const size_t p = (size_t)P;
-    const int nboxes = (P + KNN_BOX - 1) / KNN_BOX;
-    const size_t nrs = (p + RS_CHUNK - 1) / RS_CHUNK;
-    char* b = (char*)scratch;
-    uint32_t* codes = (uint32_t*)b;               b += p * 4;
-    uint32_t* order = (uint32_t*)b;               b += p * 4;
-    uint32_t* tk = (uint32_t*)b;                  b += p * 4;
-    uint32_t* tv = (uint32_t*)b;                  b += p * 4;
-    float* placed = (float*)b;                    b += p * 12;
-    b = (char*)(((uintptr_t)b + 255) & ~(uintptr_t)255);
-    Bounds* boxes = (Bounds*)b;                   b += (size_t)nboxes * sizeof(Bounds);
-    uint32_t* hist = (uint32_t*)b;                b += 256 * nrs * 4;
-    Bounds* partial = (Bounds*)b;                 b += 256 * sizeof(Bounds);
-    Bounds* bounds = (Bounds*)b;                  b += sizeof(Bounds);
-    uint32_t* ticket = (uint32_t*)b;
-    GFT_CHECK_HIP(gft_zero_async(ticket, 4, s));
-    const int blocks = (P + KNN_BLOCK - 1) / KNN_BLOCK;
-    hipLaunchKernelGGL(k_knn_bounds, dim3(blocks < 256 ? blocks : 256), dim3(KNN_BLOCK), 0, s, P, points, partial, ticket, bounds);
-    hipLaunchKernelGGL(k_knn_codes, dim3(blocks), dim3(KNN_BLOCK), 0, s, P, points, bounds, codes, order);
-    hipError_t e = radix_sort_pairs(s, P, codes, order, tk, tv, hist, 30);
-    if (e != hipSuccess) return gft_fail("gft_knn_mean_dist2: sort: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(k_knn_boxes, dim3(nboxes), dim3(KNN_BOX), 0, s, P, points, order, placed, boxes);
-    hipLaunchKernelGGL(k_knn_search, dim3(blocks), dim3(KNN_BLOCK), 0, s, P, placed, order, boxes, mean_dist2);
-    e = hipGetLastError();
-    if (e != hipSuccess) return gft_fail("gft_knn_mean_dist2: %s", hipGetErrorString(e));
-    return 0;
+    const KnnScratch v = knn_scratch(P, scratch);
+    if (knn_place(s, P, points, v, "gft_knn_mean_dist2")) return 1;
+    hipLaunchKernelGGL(k_knn_search, dim3((P + KNN_BLOCK - 1) / KNN_BLOCK), dim3(KNN_BLOCK), 0, s, P, v.placed, v.order, v.boxes, mean_dist2);
+    return gft_launched("gft_knn_mean_dist2");
+}
+
+extern "C" size_t gft_rigid_knn_scratch_bytes(int32_t P) { return gft_knn_scratch_bytes(P); }
+
+extern "C" int gft_rigid_knn(void* hip_stream, int32_t P, int32_t K, const float* points, int32_t* idx, float* dist2, void* scratch)
+{
+    if (K < 1 || K > GFT_RIGID_MAX_K) return gft_fail("gft_rigid_knn: K=%d is outside 1..%d", K, GFT_RIGID_MAX_K);
+    if (P <= K) return gft_fail("gft_rigid_knn: P=%d points have no %d other points each", P, K);
+    if ((int64_t)P * K > 0x7fffffffll) return gft_fail("gft_rigid_knn: P * K = %lld is too large", (long long)P * K);
+    if (!points || !idx || !dist2 || !scratch) return gft_fail("gft_rigid_knn: NULL pointer");
+    hipStream_t s = (hipStream_t)hip_stream;
+    const KnnScratch v = knn_scratch(P, scratch);
+    if (knn_place(s, P, points, v, "gft_rigid_knn")) return 1;
+    const dim3 grid((P + KNN_BLOCK - 1) / KNN_BLOCK), block(KNN_BLOCK);
+    if (K <= 8) hipLaunchKernelGGL(k_knn_search_k<8>, grid, block, 0, s, P, K, v.placed, v.order, v.boxes, idx, dist2);
+    else if (K <= 16) hipLaunchKernelGGL(k_knn_search_k<16>, grid, block, 0, s, P, K, v.placed, v.order, v.boxes, idx, dist2);
+    else hipLaunchKernelGGL(k_knn_search_k<32>, grid, block, 0, s, P, K, v.placed, v.order, v.boxes, idx, dist2);
+    return gft_launched("gft_rigid_knn");
 }
