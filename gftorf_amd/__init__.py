@@ -26,6 +26,7 @@ from . import present  # noqa: F401
 from . import tracks  # noqa: F401
 from . import ply  # noqa: F401
 from . import pcd  # noqa: F401
+from . import png  # noqa: F401
 from . import views  # noqa: F401
 from . import schedule  # noqa: F401
 from .query import DeformQuery, ftorf_schedule, query_dmlp  # noqa: F401

@@ -229,6 +229,9 @@ PCD_ROWS, PCD_MAX_ROW_BYTES, PCD_STATUS_WORDS = 256, 128, 2     # GFT_PCD_ROWS, 
 PCD_MODES = ("torf_init", "ftorf_init", "proxy")                # GFT_PCD_TORF_INIT, GFT_PCD_FTORF_INIT, GFT_PCD_PROXY
 # GFT_PCD_FIELDS: the entries of gft_pcd_unpack's offset table in order
 PCD_FIELDS = ("x", "y", "z", "nx", "ny", "nz", "red", "green", "blue", "phase", "amplitude", "seg_red", "seg_green", "seg_blue")
+# include/gftorf_png.h (PNG files formed on the device; its one struct is new, so the ABI version is unchanged)
+PNG_EXPORTS = ["gft_png_bound", "gft_png_scratch_bytes", "gft_png_encode"]
+PNG_SEGMENT, PNG_MAX_IMAGES, PNG_CHUNK_SLOT = 32768, 64, 32800  # GFT_PNG_SEGMENT, GFT_PNG_MAX_IMAGES, GFT_PNG_CHUNK_SLOT
 # include/gftorf_views.h (the training views on the device; no struct, so the ABI version is unchanged)
 VIEWS_EXPORTS = ["gft_views_layout", "gft_views_draw", "gft_views_select_plane", "gft_views_select_plane_backward"]
 VIEWS_MAX_GROUPS, VIEWS_ALIGN, VIEWS_HEADER_BYTES, VIEWS_CHUNKS = 8, 16, 16, 1024      # GFT_VIEWS_*
@@ -240,6 +243,12 @@ SCHEDULE_MAX_DESTS, SCHEDULE_STATE_WORDS = 1024, 8              # GFT_SCHEDULE_M
 SCHEDULE_KINDS = ("f64", "f32")                                 # GFT_SCHEDULE_F64, GFT_SCHEDULE_F32
 # GFT_SCHEDULE_*: the int64 words of the state block
 SCHEDULE_COUNTER, SCHEDULE_ITERATION, SCHEDULE_TICKET, SCHEDULE_OVERRUN, SCHEDULE_OVERRUNS = 0, 1, 2, 3, 4
+
+
+class PngImage(C.Structure):
+    """gft_png_image (include/gftorf_png.h)"""
+    _fields_ = [("src", _fp), ("row_stride", C.c_int64), ("out_offset", C.c_int64), ("H", C.c_int32), ("W", C.c_int32),
+                ("channels", C.c_int32), ("reserved", C.c_int32)]
 
 
 class ScheduleDest(C.Structure):
@@ -492,6 +501,14 @@ def load():
     # stream, rows, row0, K_file, chunk, count, dests, widths, table
     lib.gft_ply_unpack.restype = C.c_int
     lib.gft_ply_unpack.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, _ptrs, _ints, _ints]
+    lib.gft_png_bound.restype = C.c_int64
+    lib.gft_png_bound.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.gft_png_scratch_bytes.restype = C.c_int64
+    lib.gft_png_scratch_bytes.argtypes = [C.c_int32, C.POINTER(PngImage)]
+    # stream, count, images, level, out, out_bytes, sizes, scratch, scratch_bytes
+    lib.gft_png_encode.restype = C.c_int
+    lib.gft_png_encode.argtypes = [C.c_void_p, C.c_int32, C.POINTER(PngImage), C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                   C.c_int64]
     # stream, mode, H, W, stride, tof, rendered, rendered_f64, view, width_m, height_m, znear, depth_range_dev, depth_range,
     # phase_offset_dev, phase_offset, xyz, dist, amp, sh_color, color, sh_amp, amplitude, status
     lib.gft_pcd_unproject.restype = C.c_int
